@@ -17,11 +17,16 @@ value = scenarios processed by all ranks / max-over-ranks time of the K timed st
 
 Workload: storm (data/smps/storm, reference spInput), 1,000,000 i.i.d. synthetic scenarios
 from storm.sto drawn on the device, |V| = 4096 real LP duals.  Strong scaling: the 1M
-scenarios are split over the ranks.  After the timed region: a parity spot check of 4096
-scenarios per x point against the C oracle (LP objectives, cut alpha/beta) and the CPU
-baseline (C port, primary-basis and pooled warm starts).
+scenarios are split over the ranks.
 
-Run:  python bench.py [--gpus N --steps K --warmup W]
+A plain run sets up, warms up, times the K steps and prints the result line.  --dump-outputs DIR
+also writes what the last timed step returned (the cut, the incumbent objective sums, the new
+vertex count) as DIR/<name>.npy; the inputs are the same from run to run.  --full adds, after the
+timed region: the trajectory steps, a parity spot check of 4096 scenarios per x point against the
+C oracle (LP objectives, cut alpha/beta), the keyed-push check and the CPU baseline (C port,
+primary-basis and pooled warm starts).
+
+Run:  python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full]
       python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...
 """
 from __future__ import annotations
@@ -139,7 +144,17 @@ def main():
     ap.add_argument("--importance-scale", type=float, default=0.0,
                     help="s > 0: importance sampling of NORMAL elements from N(mu, (s sigma)^2) with "
                          "likelihood-ratio weights passed as add_scenario! weights (host draws)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned (cut alpha / beta / weight mark, incumbent "
+                         "objective sums, new vertex count per epigraph; with --no-dedup the objectives and "
+                         "statuses) as DIR/<name>.npy, float64")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run the legs that take runs of their own: the --trajectory "
+                         "steps, the parity spot check (--spot), the keyed-push check and the CPU baseline "
+                         "(--cpu-seconds, --cpu-pool, --no-cpu); without it they are off whatever those options say")
     args = ap.parse_args()
+    if not args.full:
+        args.trajectory, args.spot, args.no_cpu = 0, 0, True
 
     rank = int(os.environ.get("RANK", "0"))
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -326,6 +341,7 @@ def main():
         return time.perf_counter() - t0
 
     step_obj = {"value": None}   # incumbent objective of the last step
+    step_out = {}                # what the last step returned, per epigraph (--dump-outputs)
     heads_at = {}    # first pool bases at each x point (the pooled CPU baseline starts from the same bases)
 
     def step(xx, rec=None, per_x_stats=True):
@@ -342,11 +358,14 @@ def main():
             ctx.invalidate_x()
         alpha = 0.0
         objective = 0.0
+        step_out.clear()
+        step_out.update(x=xx, cuts=[], obj_sums=[], new_vertices=[], lp=[])
         for epi_e, tw in zip(epis, total_weights):
             if args.no_dedup:
-                twosd.solve_batch(epi_e, xx, 0, n_local, want_pi=False)
+                o_, _, _, st_ = twosd.solve_batch(epi_e, xx, 0, n_local, want_pi=False)
+                step_out["lp"].append((o_, st_))
             else:
-                twosd.solve_push(epi_e, xx, 0, n_local, want_obj=False)
+                step_out["new_vertices"].append(twosd.solve_push(epi_e, xx, 0, n_local, want_obj=False)[2])
                 if world > 1:
                     # exchange (2) at the SD volume: two new vertices per epigraph (the candidate
                     # and incumbent duals of sd_iteration!, algorithm.jl:46-54) all-gathered
@@ -359,10 +378,14 @@ def main():
             # reduction of the solve; across ranks all-reduced together with the cut partials)
             obj_sums = ctx.last_objective()
             if world == 1:
-                alpha += twosd.build_sasa_cut(epi_e, xx, V, args.tie_rel).alpha / E
+                cut = twosd.build_sasa_cut(epi_e, xx, V, args.tie_rel)
+                a_, b_, wm_ = cut.alpha, cut.beta, cut.weight_mark
             else:
-                a_, _, obj_sums = sdist.build_cut_sharded(ctx, epi_e, xx, tw, args.tie_rel, device, extra=obj_sums)
-                alpha += a_ / E
+                a_, b_, obj_sums = sdist.build_cut_sharded(ctx, epi_e, xx, tw, args.tie_rel, device, extra=obj_sums)
+                wm_ = tw
+            alpha += a_ / E
+            step_out["cuts"].append((a_, b_, wm_))
+            step_out["obj_sums"].append(tuple(obj_sums))
             objective += obj_sums[0] / obj_sums[1] / E
             if rec:
                 rec()      # per-epigraph kernel timings (HIP events of the last calls)
@@ -423,6 +446,8 @@ def main():
         elapsed = float(t.item())
     K = args.steps
     ms_step = 1e3 * elapsed / K
+    if args.dump_outputs and rank == 0 and K > 0:
+        dump_outputs(args.dump_outputs, step_out, args.seed)
     value = N * K / elapsed
 
     # trajectory: K distinct consecutive SD candidates (no revisits), each step refreshing at its
@@ -578,6 +603,28 @@ def main():
         print(json.dumps(out), flush=True)
     if world > 1:
         torch.distributed.destroy_process_group()
+
+
+def dump_outputs(d, so, seed, max_lp=1 << 21):
+    """What the last timed step returned, as d/<name>.npy (float64, one row per epigraph).  The
+    per-scenario LP results of --no-dedup are written whole up to max_lp scenarios per epigraph,
+    else as a fixed sample of max_lp of them drawn with `seed`."""
+    os.makedirs(d, exist_ok=True)
+    arrs = {"x": np.asarray(so["x"], dtype=np.float64),
+            "cut_alpha": np.array([c[0] for c in so["cuts"]], dtype=np.float64),
+            "cut_beta": np.array([c[1] for c in so["cuts"]], dtype=np.float64),
+            "cut_weight_mark": np.array([c[2] for c in so["cuts"]], dtype=np.float64),
+            "objective_sums": np.array(so["obj_sums"], dtype=np.float64)}
+    if so["new_vertices"]:
+        arrs["new_vertices"] = np.array(so["new_vertices"], dtype=np.float64)
+    if so["lp"]:
+        n = len(so["lp"][0][0])
+        max_lp = max(1, max_lp // len(so["lp"]))
+        pick = np.sort(np.random.default_rng(seed).choice(n, max_lp, replace=False)) if n > max_lp else slice(None)
+        arrs["lp_objective"] = np.array([o[pick] for o, _ in so["lp"]], dtype=np.float64)
+        arrs["lp_status"] = np.array([st[pick] for _, st in so["lp"]], dtype=np.float64)
+    for name, a in arrs.items():
+        np.save(os.path.join(d, name + ".npy"), a)
 
 
 def sd_points(cor, tim, sp2, sto, positions, x_ev, iters, seed, device):

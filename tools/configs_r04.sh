@@ -7,7 +7,7 @@ mkdir -p gpurun_out
 OUT=gpurun_out/configs_r04.jsonl
 : > $OUT
 run() {
-  timeout -k 10 400 python bench.py --no-cpu --steps 8 --warmup 1 --trajectory 0 "$@" > gpurun_out/cfg.json 2> gpurun_out/cfg.err || { echo "failed: $*"; tail -5 gpurun_out/cfg.err; return 1; }
+  timeout -k 10 400 python bench.py --full --no-cpu --steps 8 --warmup 1 --trajectory 0 "$@" > ${OUT%/*}/cfg.json 2> ${OUT%/*}/cfg.err || { echo "failed: $*"; tail -5 ${OUT%/*}/cfg.err; return 1; }
   tail -1 gpurun_out/cfg.json >> $OUT
   python3 -c "
 import json

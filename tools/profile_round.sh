@@ -10,7 +10,7 @@ OUT=gpurun_out/$TAG
 mkdir -p $OUT
 export TMPDIR=/tmp
 SHORT="--scenarios $NS --no-cpu --spot 0"
-timeout -k 10 600 python bench.py --scenarios $NS > $OUT/bench.json 2> $OUT/bench.err || { echo "bench failed $?"; exit 1; }
+timeout -k 10 600 python bench.py --full --scenarios $NS > $OUT/bench.json 2> $OUT/bench.err || { echo "bench failed $?"; exit 1; }
 tail -1 $OUT/bench.json | cut -c1-400
 timeout -k 10 420 rocprofv3 --kernel-trace --stats -d $OUT/trace -o run --output-format csv -- python3 bench.py $SHORT --steps 4 --warmup 1 > $OUT/trace_bench.json 2> $OUT/trace.err || { echo "trace failed $?"; exit 1; }
 timeout -k 10 420 rocprofv3 --pmc FETCH_SIZE -d $OUT/pmc_fetch -o run --output-format csv -- python3 bench.py $SHORT --steps 1 --warmup 0 > /dev/null 2> $OUT/pmc_fetch.err || { echo "pmc fetch failed $?"; exit 1; }
