@@ -153,18 +153,34 @@ __device__ __forceinline__ uint64_t h_uniform(uint64_t v) {
     return ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(v >> 32)) << 32) |
            (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)v);
 }
-// register-array element p = 64 * slot + lane (p uniform)
+// H_SLOT_SWITCH(s, N, body): body for the wave-uniform slot s in [0, N), N <= 64, with the slot a
+// compile-time constant SL inside it: a switch, which the compiler lowers to a tree of scalar
+// compare-and-branch pairs (about log2 N taken per call), so a register array is touched at a
+// constant index and stays in registers.  (A select chain over the array is folded by the compiler
+// into a dynamically indexed access, which sends the whole array to scratch -- as are cases that
+// differ only in the index, hence the opaque copy of the element in every body below, and as is the
+// same tree built from a recursive template with a lambda per leaf; a linear `if (c == s)` chain
+// costs one compare-and-branch per slot.)
+#define H_SLOT_CASE(c, N, ...) case c: if constexpr ((c) < (N)) { constexpr int SL = (c) < (N) ? (c) : 0; __VA_ARGS__ } break;
+#define H_SLOT_CASE8(b, N, ...)                                                                       \
+    H_SLOT_CASE(b, N, __VA_ARGS__) H_SLOT_CASE(b + 1, N, __VA_ARGS__) H_SLOT_CASE(b + 2, N, __VA_ARGS__)  \
+    H_SLOT_CASE(b + 3, N, __VA_ARGS__) H_SLOT_CASE(b + 4, N, __VA_ARGS__) H_SLOT_CASE(b + 5, N, __VA_ARGS__) \
+    H_SLOT_CASE(b + 6, N, __VA_ARGS__) H_SLOT_CASE(b + 7, N, __VA_ARGS__)
+#define H_SLOT_SWITCH(s, N, ...)                                                                       \
+    switch (s) {                                                                                      \
+        H_SLOT_CASE8(0, N, __VA_ARGS__) H_SLOT_CASE8(8, N, __VA_ARGS__) H_SLOT_CASE8(16, N, __VA_ARGS__)  \
+        H_SLOT_CASE8(24, N, __VA_ARGS__) H_SLOT_CASE8(32, N, __VA_ARGS__) H_SLOT_CASE8(40, N, __VA_ARGS__) \
+        H_SLOT_CASE8(48, N, __VA_ARGS__) H_SLOT_CASE8(56, N, __VA_ARGS__)                               \
+    }
+// register-array element p = 64 * slot + lane (p uniform): one readlane in the slot's case
 template <int R>
 __device__ __forceinline__ int h_get_row_i(const int (&a)[R], int p) {
-    // one readlane per slot and a scalar select: a select chain over a[t] is folded by the
-    // compiler into a dynamically indexed load, which sends the whole array to scratch
-    const int slot = p >> 6;
     int v = 0;
-#pragma unroll
-    for (int t = 0; t < R; ++t) {
-        const int u = __builtin_amdgcn_readlane(a[t], p & 63);
-        v = (t == slot) ? u : v;
-    }
+    H_SLOT_SWITCH(__builtin_amdgcn_readfirstlane(p >> 6), R, {
+        int u = a[SL];
+        asm volatile("" : "+v"(u));
+        v = __builtin_amdgcn_readlane(u, p & 63);
+    })
     return v;
 }
 
@@ -453,97 +469,148 @@ __global__ void __launch_bounds__(256, TWOSD_HYPER_WPE(R)) lp_hyper_kernel(Hyper
             if (K >= P.kcap) { status = TWOSD_LP_ITER_LIMIT; break; }
             const double delta = lr.p0;
 
-            // ---- 2. BTRAN: u = e_r' E_K..E_1 (u dense in LDS), rho = u' B0^{-1}
-            if (lane == (r & 63)) ut[r] = 1.0;
-            h_wave_sync();
-            // etas in groups of EG: the group's entries (first 64 of each) are loaded together, and
-            // the next group's loads are issued before this group is applied (two register sets,
-            // ping-pong), so the memory round trips overlap the sequential steps
-            {
-                auto apply = [&](int tg, const int (&gi)[EG], const double (&gv)[EG], const int (&gn)[EG], const int (&go)[EG]) {
-#pragma unroll
-                    for (int g = 0; g < EG; ++g) {
-                        const int tt = tg - g;
-                        if (tt < 0) break;
-                        const double ug = gv[g] != 0.0 ? ut[gi[g]] : 0.0;
-                        // a dead eta: u is zero on all its rows (u holds only r and the pivot rows
-                        // set so far), so u . eta_t = 0 and u[p_t] -- one of those rows (the pivot
-                        // entry 1 / alpha_r is never zero) -- is zero already: nothing to write.
-                        // (Skipped, the pivot row keeps its zero instead of being rewritten with a
-                        // zero of either sign; every later use tests u != 0.)
-                        if (gn[g] <= 64 && __builtin_amdgcn_ballot_w64(ug != 0.0) == 0) {
-                            nops += gn[g];
-                            continue;
-                        }
-                        double acc = ug * gv[g];
-                        for (int e = 64 + lane; e < gn[g]; e += 64) acc = fma(ut[eidx[go[g] + e]], evals[go[g] + e], acc);
-                        acc = wsum(acc);
-                        nops += gn[g];
-                        if (lane == 0) ut[etap[tt]] = acc;
-                        h_wave_sync();
-                    }
-                };
-                int ai[EG], an[EG], ao[EG], bi[EG], bn[EG], bo[EG];
-                double av[EG], bv[EG];
-                if (K <= 2 * EG) {   // short file (storm: most solves): one group in flight at a time
-                    for (int tg = K - 1; tg >= 0; tg -= EG) {
-                        eta_group(tg, -1, ai, av, an, ao);
-                        apply(tg, ai, av, an, ao);
-                    }
-                } else {
-                    eta_group(K - 1, -1, ai, av, an, ao);
-                    for (int tg = K - 1; tg >= 0;) {
-                        eta_group(tg - EG, -1, bi, bv, bn, bo);
-                        apply(tg, ai, av, an, ao);
-                        tg -= EG;
-                        if (tg < 0) break;
-                        eta_group(tg - EG, -1, ai, av, an, ao);
-                        apply(tg, bi, bv, bn, bo);
-                        tg -= EG;
-                    }
-                }
-            }
-            STAMP(2)
-            // rho = u' B0^{-1} as one segmented scatter over the nonzero rows of u, which sit at r
-            // and at the eta pivot rows, in the fixed order r, etap[K-1], ..., etap[0] (64 rows per
-            // batch; deterministic accumulation order).  A row that appears again later (pivoted
-            // more than once) contributes at its first position only; each row is zeroed after.
-            for (int b0 = 0; b0 <= K; b0 += 64) {
-                const int jj = b0 + lane;
-                const int gp = jj <= K ? (jj == 0 ? r : (int)etap[K - jj]) : -1;
-                const int nbt = K + 1 - b0 < 64 ? K + 1 - b0 : 64;
-                bool dup = false;
-                for (int i = 0; i < nbt - 1; ++i) dup |= (i < lane) & (__builtin_amdgcn_readlane(gp, i) == gp);
-                double up = 0.0;
-                int p0 = 0, len = 0;
-                if (gp >= 0 && !dup) {
-                    up = ut[gp];
-                    if (up != 0.0) {
-                        p0 = brptr[gp];
-                        len = brptr[gp + 1] - p0;
-                    }
-                }
-                nops += h_seg_scatter(p0, len, up, P.brcol, P.brval, rho, smark, lane);
-                h_wave_sync();
-                if (gp >= 0) ut[gp] = 0.0;
-                h_wave_sync();
-            }
-            STAMP(3)
-
             // ---- 3. pricing: alpha'_j = s_j rho' a_j for every column as a scatter over the
             // nonzeros of rho (~6 % of the rows on storm).  alpha lives in LDS over the ut/rho space
             // (both zero here once rho is in registers).  (A column-wise variant -- dot products over
             // [W I]'s columns -- measured no faster even on ssn's denser rho.)
-            double rv[R];
+            // The pricing list holds the nonzero rows of rho = e_r' B^{-1} (ascending) and their
+            // values, 64 per batch in LDS (lsti, lstv); one batch (nb rows): their W rows (CSR)
+            // scattered 64 entries per wave step (h_seg_scatter).
+            auto price_batch = [&](int nb) {
+                h_wave_sync();
+                int p0 = 0, len = 0;
+                double gr = 0.0;
+                if (lane < nb) {
+                    const int gi = lsti[lane];
+                    gr = lstv[lane];
+                    p0 = P.wcp[gi];
+                    len = P.wcp[gi + 1] - p0;
+                    // slack of row i: entry 1 in row i only, folded by its sign (G row: -1)
+                    alpha[n + gi] = P.btype[n + gi] == BT_G ? -gr : gr;
+                }
+                nops += h_seg_scatter(p0, len, gr, P.wcc, P.wcv, alpha, smark, lane) + nb;
+                h_wave_sync();   // the list is rewritten by the next batch
+            };
+            // First pivot of a start (K = 0, about one pivot in 4.5 on storm): no eta yet, so u = e_r
+            // and rho is row r of B_p^{-1} itself -- the scatter below would add 1.0 * brval to a zero
+            // (the same bits), and the row's brcol entries are distinct and ascending (every producer
+            // of the CSR writes them so), which is the list's order.  A row of at most 64 entries goes
+            // straight into the list (entries stored as zeros dropped, as the dense read-back drops
+            // them); ut / rho are never touched and stay zero, as the general path leaves them.
+            int rp0 = 0, rlen = 65;
+            if (K == 0) {
+                rp0 = __builtin_amdgcn_readfirstlane(brptr[r]);
+                rlen = __builtin_amdgcn_readfirstlane(brptr[r + 1]) - rp0;
+            }
+            if (rlen <= 64) {
+                int gi = 0;
+                double gr = 0.0;
+                if (lane < rlen) {
+                    gi = P.brcol[rp0 + lane];
+                    gr = P.brval[rp0 + lane];
+                }
+                const uint64_t nzm = __ballot(gr != 0.0);
+                if (gr != 0.0) {
+                    const int pos = h_prefix_count(nzm);
+                    lsti[pos] = gi;
+                    lstv[pos] = gr;
+                }
+                nops += rlen;
+                if (nzm != 0) price_batch(__popcll(nzm));
+            } else {
+                // ---- 2. BTRAN: u = e_r' E_K..E_1 (u dense in LDS), rho = u' B0^{-1}
+                if (lane == (r & 63)) ut[r] = 1.0;
+                h_wave_sync();
+                // the rows of rho's first scatter batch (r, then the eta pivot rows) are known before the
+                // etas run: their CSR bounds are loaded over the eta loop instead of after it
+                const int gp0 = lane <= K ? (lane == 0 ? r : (int)etap[K - lane]) : -1;
+                int bp0 = 0, bp1 = 0;
+                if (gp0 >= 0) {
+                    bp0 = brptr[gp0];
+                    bp1 = brptr[gp0 + 1];
+                }
+                // etas in groups of EG: the group's entries (first 64 of each) are loaded together, and
+                // the next group's loads are issued before this group is applied (two register sets,
+                // ping-pong), so the memory round trips overlap the sequential steps
+                {
+                    auto apply = [&](int tg, const int (&gi)[EG], const double (&gv)[EG], const int (&gn)[EG], const int (&go)[EG]) {
 #pragma unroll
-            for (int t = 0; t < R; ++t) rv[t] = rho[64 * t + lane];
-            h_wave_sync();
+                        for (int g = 0; g < EG; ++g) {
+                            const int tt = tg - g;
+                            if (tt < 0) break;
+                            const double ug = gv[g] != 0.0 ? ut[gi[g]] : 0.0;
+                            // a dead eta: u is zero on all its rows (u holds only r and the pivot rows
+                            // set so far), so u . eta_t = 0 and u[p_t] -- one of those rows (the pivot
+                            // entry 1 / alpha_r is never zero) -- is zero already: nothing to write.
+                            // (Skipped, the pivot row keeps its zero instead of being rewritten with a
+                            // zero of either sign; every later use tests u != 0.)
+                            if (gn[g] <= 64 && __builtin_amdgcn_ballot_w64(ug != 0.0) == 0) {
+                                nops += gn[g];
+                                continue;
+                            }
+                            double acc = ug * gv[g];
+                            for (int e = 64 + lane; e < gn[g]; e += 64) acc = fma(ut[eidx[go[g] + e]], evals[go[g] + e], acc);
+                            acc = wsum(acc);
+                            nops += gn[g];
+                            if (lane == 0) ut[etap[tt]] = acc;
+                            h_wave_sync();
+                        }
+                    };
+                    int ai[EG], an[EG], ao[EG], bi[EG], bn[EG], bo[EG];
+                    double av[EG], bv[EG];
+                    if (K <= 2 * EG) {   // short file (storm: most solves): one group in flight at a time
+                        for (int tg = K - 1; tg >= 0; tg -= EG) {
+                            eta_group(tg, -1, ai, av, an, ao);
+                            apply(tg, ai, av, an, ao);
+                        }
+                    } else {
+                        eta_group(K - 1, -1, ai, av, an, ao);
+                        for (int tg = K - 1; tg >= 0;) {
+                            eta_group(tg - EG, -1, bi, bv, bn, bo);
+                            apply(tg, ai, av, an, ao);
+                            tg -= EG;
+                            if (tg < 0) break;
+                            eta_group(tg - EG, -1, ai, av, an, ao);
+                            apply(tg, bi, bv, bn, bo);
+                            tg -= EG;
+                        }
+                    }
+                }
+                STAMP(2)
+                // rho = u' B0^{-1} as one segmented scatter over the nonzero rows of u, which sit at r
+                // and at the eta pivot rows, in the fixed order r, etap[K-1], ..., etap[0] (64 rows per
+                // batch; deterministic accumulation order).  A row that appears again later (pivoted
+                // more than once) contributes at its first position only; each row is zeroed after.
+                for (int b0 = 0; b0 <= K; b0 += 64) {
+                    const int jj = b0 + lane;
+                    const int gp = b0 == 0 ? gp0 : (jj <= K ? (int)etap[K - jj] : -1);
+                    const int nbt = K + 1 - b0 < 64 ? K + 1 - b0 : 64;
+                    bool dup = false;
+                    for (int i = 0; i < nbt - 1; ++i) dup |= (i < lane) & (__builtin_amdgcn_readlane(gp, i) == gp);
+                    double up = 0.0;
+                    int p0 = 0, len = 0;
+                    if (gp >= 0 && !dup) {
+                        up = ut[gp];
+                        if (up != 0.0) {
+                            p0 = b0 == 0 ? bp0 : brptr[gp];
+                            len = (b0 == 0 ? bp1 : brptr[gp + 1]) - p0;
+                        }
+                    }
+                    nops += h_seg_scatter(p0, len, up, P.brcol, P.brval, rho, smark, lane);
+                    h_wave_sync();
+                    if (gp >= 0) ut[gp] = 0.0;
+                    h_wave_sync();
+                }
+                STAMP(3)
+                // rho into registers, its LDS space back to zero; the nonzero rows (ascending) are
+                // compacted into the list, 64 per batch
+                double rv[R];
 #pragma unroll
-            for (int t = 0; t < R; ++t) rho[64 * t + lane] = 0.0;
-            h_wave_sync();
-            // the nonzero rows of rho (ascending) are compacted into the LDS list, 64 per batch, and
-            // the batch's W rows (CSR) scattered 64 entries per wave step (h_seg_scatter)
-            {
+                for (int t = 0; t < R; ++t) rv[t] = rho[64 * t + lane];
+                h_wave_sync();
+#pragma unroll
+                for (int t = 0; t < R; ++t) rho[64 * t + lane] = 0.0;
+                h_wave_sync();
                 uint64_t mk[R];
                 int tot = 0;
 #pragma unroll
@@ -562,20 +629,7 @@ __global__ void __launch_bounds__(256, TWOSD_HYPER_WPE(R)) lp_hyper_kernel(Hyper
                         }
                         base += __popcll(mk[t]);
                     }
-                    h_wave_sync();
-                    const int nb = tot - b0 < 64 ? tot - b0 : 64;
-                    int p0 = 0, len = 0;
-                    double gr = 0.0;
-                    if (lane < nb) {
-                        const int gi = lsti[lane];
-                        gr = lstv[lane];
-                        p0 = P.wcp[gi];
-                        len = P.wcp[gi + 1] - p0;
-                        // slack of row i: entry 1 in row i only, folded by its sign (G row: -1)
-                        alpha[n + gi] = P.btype[n + gi] == BT_G ? -gr : gr;
-                    }
-                    nops += h_seg_scatter(p0, len, gr, P.wcc, P.wcv, alpha, smark, lane) + nb;
-                    h_wave_sync();   // the list is rewritten by the next batch
+                    price_batch(tot - b0 < 64 ? tot - b0 : 64);
                 }
             }
             h_wave_sync();
@@ -651,10 +705,31 @@ __global__ void __launch_bounds__(256, TWOSD_HYPER_WPE(R)) lp_hyper_kernel(Hyper
             }
             const double thetaD = eq.p0 / eq.key;   // d'_q / a'_q = d_q / a_q
             // d'_j -= thetaD a'_j over the slots with a nonzero alpha', alpha back to zero (ut / rho
-            // all zero after); an all-zero slot would leave d' unchanged but for the sign of a zero
+            // all zero after); an all-zero slot would leave d' unchanged but for the sign of a zero.
+            // FTRAN's operands for the first 64 nonzeros of a_q are three dependent memory round trips
+            // (colptr[q], then rowidx / val, then bcp) that read nothing this loop writes: each is issued
+            // at a third of the loop and has returned by the next, instead of all three after it.  (Vector
+            // loads through an opaque copy of q: scalar loads would share the LDS reads' wait counter.)
+            int fq = q;
+            asm volatile("" : "+v"(fq));
+            const bool fcol = q < n;   // a structural column; a slack has its single entry 1 in row q - n
+            int fn0 = 0, fn1 = 1, fcc = 0, fp0 = 0, fp1 = 0;
+            double ffa = 0.0;
             apf = alpha[lane];
 #pragma unroll
             for (int c = 0; c < C; ++c) {
+                if (c == 0 && fcol) {
+                    fn0 = P.colptr[fq];
+                    fn1 = P.colptr[fq + 1];
+                }
+                if (c == C / 3 && lane < fn1 - fn0) {
+                    fcc = fcol ? P.rowidx[fn0 + lane] : q - n;
+                    ffa = fcol ? P.val[fn0 + lane] : 1.0;
+                }
+                if (c == (2 * C) / 3 && lane < fn1 - fn0) {
+                    fp0 = bcp[fcc];
+                    fp1 = bcp[fcc + 1];
+                }
                 const double av = apf;
                 if (c + 1 < C) apf = alpha[64 * (c + 1) + lane];
                 if ((snz >> c) & 1) {
@@ -670,14 +745,16 @@ __global__ void __launch_bounds__(256, TWOSD_HYPER_WPE(R)) lp_hyper_kernel(Hyper
             // B0^{-1} under the nonzeros of a_q as one segmented scatter (lane j: nonzero np0 + j),
             // 64 nonzeros per batch, then the etas
             {
-                const int np0 = q >= n ? 0 : P.colptr[q], np1 = q >= n ? 1 : P.colptr[q + 1];
-                for (int pw0 = np0; pw0 < np1; pw0 += 64) {
+                const int np0 = __builtin_amdgcn_readfirstlane(fn0), np1 = __builtin_amdgcn_readfirstlane(fn1);
+                // the first batch's operands arrived over the dual update (lanes past np1: p0 = len = 0)
+                nops += h_seg_scatter(fp0, fp1 - fp0, ffa, P.bci, P.bcv, ut, smark, lane);
+                for (int pw0 = np0 + 64; pw0 < np1; pw0 += 64) {
                     const int pw = pw0 + lane;
                     int p0 = 0, len = 0;
                     double fa = 0.0;
                     if (pw < np1) {
-                        const int cc = q >= n ? q - n : P.rowidx[pw];
-                        fa = q >= n ? 1.0 : P.val[pw];
+                        const int cc = P.rowidx[pw];
+                        fa = P.val[pw];
                         p0 = bcp[cc];
                         len = bcp[cc + 1] - p0;
                     }
@@ -744,11 +821,11 @@ __global__ void __launch_bounds__(256, TWOSD_HYPER_WPE(R)) lp_hyper_kernel(Hyper
             const double thetaP = delta / arq;
             const double inv_arq = 1.0 / arq;
             float wrr = 0.0f;
-#pragma unroll
-            for (int t = 0; t < R; ++t) {
-                const float u = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, wd[t]), r & 63));
-                wrr = (t == (r >> 6)) ? u : wrr;
-            }
+            H_SLOT_SWITCH(__builtin_amdgcn_readfirstlane(r >> 6), R, {
+                int u = __builtin_bit_cast(int, wd[SL]);
+                asm volatile("" : "+v"(u));
+                wrr = __builtin_bit_cast(float, __builtin_amdgcn_readlane(u, r & 63));
+            })
             int cnt = 0;
 #pragma unroll
             for (int t = 0; t < R; ++t) cnt += __popcll(__ballot(col[t] != 0.0));
@@ -787,26 +864,30 @@ __global__ void __launch_bounds__(256, TWOSD_HYPER_WPE(R)) lp_hyper_kernel(Hyper
             // reduced cost of the leaving variable: -sg thetaD, folded by its sign (a G-row
             // slack leaves to its upper bound 0: s = -1); of q: 0
             {
-                const int ls = leaving >> 6, qs = q >> 6;
+                const int ls = __builtin_amdgcn_readfirstlane(leaving >> 6), qs = __builtin_amdgcn_readfirstlane(q >> 6);
                 const double dlv = (delta > 0) == ((lh & 3) == BT_G) ? thetaD : -thetaD;
                 const bool lme = lane == (leaving & 63), qme = lane == (q & 63);
-                // one slot each (ls, qs uniform): scalar branches, two selects in all
-#pragma unroll
-                for (int c = 0; c < C; ++c) {
-                    if (c == ls) d[c] = lme ? dlv : d[c];
-                    if (c == qs) d[c] = qme ? 0.0 : d[c];
-                }
+                // one slot each (ls, qs uniform; the leaving column first, as ever): two selects in all
+                H_SLOT_SWITCH(ls, C, {
+                    double v = lme ? dlv : d[SL];
+                    asm volatile("" : "+v"(v));
+                    d[SL] = v;
+                })
+                H_SLOT_SWITCH(qs, C, {
+                    double v = qme ? 0.0 : d[SL];
+                    asm volatile("" : "+v"(v));
+                    d[SL] = v;
+                })
                 if (lme) bmask &= ~(1ull << ls);
                 if (qme) bmask |= 1ull << qs;
-                if (lane == (r & 63)) {
-                    const int rs = r >> 6;
+                {
                     const int nh = q * 4 + (int)P.btype[q];
-#pragma unroll
-                    for (int t = 0; t < R; ++t) {
-                        int v = (t == rs) ? nh : hb[t];
-                        asm volatile("" : "+v"(v));   // per-slot select kept: no dynamic store into hb
-                        hb[t] = v;
-                    }
+                    const bool rme = lane == (r & 63);
+                    H_SLOT_SWITCH(__builtin_amdgcn_readfirstlane(r >> 6), R, {
+                        int v = rme ? nh : hb[SL];
+                        asm volatile("" : "+v"(v));
+                        hb[SL] = v;
+                    })
                 }
             }
             ++it;
