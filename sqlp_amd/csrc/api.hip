@@ -287,7 +287,7 @@ static void free_template(twosd_ctx *c) {
     dfree(c->d_xbase); dfree(c->d_queue); dfree(c->d_lpstats);
     dfree(c->d_obj); dfree(c->d_pi); dfree(c->d_pi_rep); dfree(c->d_y); dfree(c->d_status); dfree(c->d_iters); dfree(c->d_ops); dfree(c->d_etan);
     dfree(c->d_dvtmp);
-    dfree(c->d_bnnz); dfree(c->d_sel_cinf); dfree(c->d_sel_ptr); dfree(c->d_sel_code); c->sel_code_cap = 0; dfree(c->d_head_out); dfree(c->d_pool_pick); dfree(c->d_cpick); dfree(c->d_order); dfree(c->d_sort_tmp);
+    dfree(c->d_bnnz); dfree(c->d_sel_cinf); dfree(c->d_sel_ptr); dfree(c->d_sel_code); c->sel_code_cap = 0; dfree(c->d_head_out); dfree(c->d_pool_pick); dfree(c->d_cpick); dfree(c->d_order); dfree(c->d_sort_tmp); dfree(c->d_qrec); c->qrec_cap = 0;
     dfree(c->d_cand); dfree(c->d_sel_key); dfree(c->d_sel_pkey); dfree(c->d_sel_ppick); c->sel_pcap = 0; c->key_cap = 0; c->pool_l1 = c->pool_ncand = 0; c->order_cap = 0; c->sort_tmp_bytes = 0; c->head_cap = 0; c->pick_cap = 0; c->pool.clear();
     dfree(c->d_dist_kind); dfree(c->d_dist_off); dfree(c->d_dist_val); dfree(c->d_dist_prob); dfree(c->d_dist_p0);
     dfree(c->d_dist_p1); dfree(c->d_dist_tmpl); c->has_dist = false;
@@ -2441,14 +2441,43 @@ int twosd::run_lp_ex(twosd_ctx *c, const double *x, const double *d_dv, int N, c
             }
             H.pool_pick = c->d_pool_pick;
         }
+        if (!list && c->d_kslot && getenv("TWOSD_DEBUG")) {
+            // w, the widest ELL slot of a start basis: the x_B warm start walks w columns
+            std::vector<int> ks((size_t)H.npool * (R + 1));
+            HIPCHK(hipMemcpy(ks.data(), c->d_kslot, sizeof(int) * ks.size(), hipMemcpyDeviceToHost));
+            std::vector<int> ws(H.npool);
+            double mean = 0;
+            for (int p = 0; p < H.npool; ++p) {
+                int w = 0;
+                for (int t = 0; t < R; ++t) w = std::max(w, ks[(size_t)p * (R + 1) + t + 1] - ks[(size_t)p * (R + 1) + t]);
+                ws[p] = w;
+                mean += w;
+            }
+            std::sort(ws.begin(), ws.end());
+            fprintf(stderr, "LP start: ELL width w over %d bases: min %d, median %d, mean %.2f, p90 %d, max %d\n", H.npool, ws.front(),
+                    ws[ws.size() / 2], mean / H.npool, ws[ws.size() * 9 / 10], ws.back());
+        }
         HIPCHK(hipEventRecord(c->ev[0], c->stream));
+        const int *order = nullptr;
         if (list) {
-            H.order = o.d_list;
+            order = o.d_list;
         } else if (H.npool > 1) {
             if ((rc = select_pool(c, d_dv, N, c->d_pool_pick, 0))) return rc;
-            H.order = c->d_order;
+            order = c->d_order;
         }
         HIPCHK(hipEventRecord(c->ev[2], c->stream));
+        // one record per queue position (its scenario and start basis), so that a wave learns both
+        // from its claim in one load; part of the timed LP launch.  Neither an order nor a pool:
+        // position q is scenario q from the primary basis and the kernel reads no record.
+        if (order || H.npool > 1) {
+            if ((size_t)NL > c->qrec_cap) {
+                const size_t cap = std::max<size_t>(NL, 1024);
+                if ((rc = dalloc(&c->d_qrec, cap))) return rc;
+                c->qrec_cap = cap;
+            }
+            HIPCHK(launch_queue_records(order, H.npool > 1 ? c->d_pool_pick : nullptr, c->d_qrec, NL, c->stream));
+            H.qrec = c->d_qrec;
+        }
         HIPCHK(launch_hyper(R, CH, H, nblocks, hyper_lds_bytes(R, CH, kmax, c->k), c->stream));
         HIPCHK(hipEventRecord(c->ev[1], c->stream));
         HIPCHK(hipStreamSynchronize(c->stream));

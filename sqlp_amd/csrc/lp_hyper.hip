@@ -289,31 +289,60 @@ __global__ void __launch_bounds__(256, TWOSD_HYPER_WPE(R)) lp_hyper_kernel(Hyper
     // served first by the blocks with blockIdx % qgroups == g (one XCD under the round-robin
     // block placement, speed only), so the waves that share a pool basis share one L2.  A wave
     // whose range is exhausted moves on to the next range (never back: exhausted stays exhausted).
-    // The claim of the next queue position, its scenario (order) and its pool pick are three
-    // dependent global round trips; they are software-pipelined across scenarios: the claim is
-    // issued when a scenario starts and resolved after its x_B loads (which it overlaps), the
-    // order load is issued then and resolved after the pivot loop, where the pick load is issued.
+    // A wave learns its next scenario through three dependent global round trips: the claim of a
+    // queue position, that position's record (scenario and start basis: qrec, gathered before the
+    // launch), and the slot bounds of that basis.  They are software-pipelined across scenarios and
+    // retired at waits that exist anyway, into SGPRs or the LDS slice (a VGPR held over the pivot
+    // loop is spilled, and the spill waits for the load at once):
+    //   epilogue of scenario i - 1   claims the position of i + 1, with the loads of that epilogue
+    //   start of scenario i          loads the record of i + 1 with the start state of i; retired
+    //                                after the ELL walk into SGPRs (s_nx, pb_nx)
+    //   epilogue of scenario i       loads the deltas and the slot bounds of i + 1 with the q_j of
+    //                                the objective and parks them in LDS (the bounds in the pricing
+    //                                list's rows, free between the last pivot of one scenario and
+    //                                the first of the next)
     const int G = CP.qgroups;
     const int g0 = blockIdx.x % G;
     int gt = 0;
+    int q_lo = 0, q_hi = 0;   // the positions of range group_of(gt) (gt < G)
     auto group_of = [&](int gi) { return g0 + gi < G ? g0 + gi : g0 + gi - G; };
+    auto range_set = [&]() {   // (two 64-bit divisions: once per range, not per claim)
+        const int g = group_of(gt);
+        q_lo = (int)(((long long)P.N * g) / G);
+        q_hi = (int)(((long long)P.N * (g + 1)) / G);
+    };
+    auto claim_issue = [&]() -> int {   // lane 0: the claimed offset within range group_of(gt), in flight
+        int t = 0;
+        if (lane == 0 && gt < G) t = atomicAdd(CP.queue + group_of(gt) * kQueueStride, 1);
+        return t;
+    };
     auto claim_sync = [&]() -> int {   // next position, moving on to the next range when one is exhausted
         for (; gt < G; ++gt) {
-            const int g = group_of(gt);
-            const int lo = (int)(((long long)P.N * g) / G), hi = (int)(((long long)P.N * (g + 1)) / G);
-            int t = 0;
-            if (lane == 0) t = atomicAdd(CP.queue + g * kQueueStride, 1);
-            t = __builtin_amdgcn_readfirstlane(__shfl(t, 0));
-            if (lo + t < hi) return lo + t;
+            range_set();
+            const int t = __builtin_amdgcn_readfirstlane(claim_issue());
+            if (q_lo + t < q_hi) return q_lo + t;
         }
         return -1;
     };
+    auto claim_resolve = [&](int t_claim) -> int {   // the position of a claim issued by claim_issue
+        if (gt >= G) return -1;
+        const int t = __builtin_amdgcn_readfirstlane(t_claim);
+        if (q_lo + t < q_hi) return q_lo + t;
+        ++gt;   // the range is exhausted (rare): claim from the next one
+        return claim_sync();
+    };
     int q_nx = claim_sync();
-    int s_nx = q_nx < 0 ? -1 : (CP.order ? __builtin_amdgcn_readfirstlane(CP.order[q_nx]) : q_nx);
-    int pb_nx = (s_nx >= 0 && CP.npool > 1) ? __builtin_amdgcn_readfirstlane(CP.pool_pick[s_nx]) : 0;
+    int q_n2 = q_nx >= 0 ? claim_resolve(claim_issue()) : -1;   // the position after q_nx
+    int s_nx = q_nx, pb_nx = 0;
+    if (q_nx >= 0 && CP.qrec) {
+        const int2 rc = CP.qrec[q_nx];
+        s_nx = __builtin_amdgcn_readfirstlane(rc.x);
+        pb_nx = __builtin_amdgcn_readfirstlane(rc.y);
+    }
+    if (q_nx >= 0 && lane <= R) lsti[lane] = CP.kslot[pb_nx * (R + 1) + lane];
     // coef_e(x) dv_e of a scenario into LDS (dvl is read by the x_B gathers only).  With k <= 128
-    // the next scenario's deltas are loaded when its index is known (after the pivot loop) and
-    // written at the end of the epilogue, so the load overlaps the epilogue
+    // the next scenario's deltas are loaded after the pivot loop and written once the objective's
+    // q_j, issued after them, have returned
     auto dv_fill = [&](int sn) {
         const double *dvs = CP.dv + (size_t)sn * P.k;
         for (int e = lane; e < P.k; e += 64) dvl[e] = CP.kcoef[e] * dvs[e];
@@ -325,10 +354,7 @@ __global__ void __launch_bounds__(256, TWOSD_HYPER_WPE(R)) lp_hyper_kernel(Hyper
         const int qpos = q_nx;
         int s = s_nx;                                    // grouped by pool basis
         int pb = pb_nx;                                  // warm-start basis (pool_select_kernel; 0 without a pool)
-        // claim of the following position, resolved after this scenario's x_B loads
-        int t_claim = 0;
-        if (lane == 0 && gt < G) t_claim = atomicAdd(CP.queue + group_of(gt) * kQueueStride, 1);
-
+        q_nx = q_n2;                                     // claimed over the previous epilogue
         if (!dv_pf) dv_fill(s);
         h_wave_sync();
         // x_B of pool basis p at this scenario: xbase_p + sum_e coef_e B_p^{-1}[i][row_e] dv_e
@@ -357,9 +383,34 @@ __global__ void __launch_bounds__(256, TWOSD_HYPER_WPE(R)) lp_hyper_kernel(Hyper
             brptr = A->brptr + (size_t)pb * (MP + 1);
             bcp = A->bcp + (size_t)pb * (MP + 1);
             const double *xb = A->xbase + (size_t)pb * MP;
+            const int *hbp = A->hb0 + (size_t)pb * MP;
+            const double *d0p = A->d0 + (size_t)pb * 64 * C;
             const double *kv = A->kv;
             const int *kix = A->kix;
-            const int ksv = ln <= R ? A->kslot[pb * (R + 1) + ln] : 0;
+            // Everything that depends on pb alone is issued in one go -- the slot bounds, x_base, the
+            // heads, d0 and the basic mask -- and the first ELL batch follows as soon as the bounds are
+            // there, so the start state shares the wait of that batch instead of taking three round
+            // trips of its own (bounds, then x_base / heads, then d0 after the walk).
+            int ksv = 0;
+            if (attempt == 0) {   // parked by the previous epilogue; a retry (pb = 0) loads its own
+                if (ln <= R) ksv = lsti[ln];
+            } else if (ln <= R) {
+                ksv = A->kslot[pb * (R + 1) + ln];
+            }
+            double d0r[C];
+#pragma unroll
+            for (int t = 0; t < R; ++t) {
+                xB[t] = xb[64 * t + ln];
+                hb[t] = hbp[64 * t + ln];
+                wd[t] = 1.0f;
+            }
+#pragma unroll
+            for (int c = 0; c < C; ++c) d0r[c] = d0p[64 * c + ln];
+            bmask = A->basic0[pb * 64 + ln];
+            // the record of the next position, in flight over the walk
+            const bool has_rec = A->qrec != nullptr;
+            int2 rcn = make_int2(0, 0);
+            if (attempt == 0 && q_nx >= 0 && has_rec) rcn = A->qrec[q_nx];
             int eb[R], len[R];
             int w = 0;
 #pragma unroll
@@ -367,60 +418,55 @@ __global__ void __launch_bounds__(256, TWOSD_HYPER_WPE(R)) lp_hyper_kernel(Hyper
                 eb[t] = __builtin_amdgcn_readlane(ksv, t);
                 len[t] = __builtin_amdgcn_readlane(ksv, t + 1) - eb[t];
                 w = len[t] > w ? len[t] : w;
-                xB[t] = xb[64 * t + ln];
-                hb[t] = A->hb0[(size_t)pb * MP + 64 * t + ln];
-                wd[t] = 1.0f;
             }
             nops += (unsigned)(__builtin_amdgcn_readlane(ksv, R) - eb[0]) * 64u;
-            // columns u .. u + XU - 1 of every slot per round trip (all their loads issued before the
-            // first is used), applied in increasing u per row: the same fma order as a per-row walk
+            // columns u .. u + XU - 1 of every slot per round trip.  The loads of a batch are issued
+            // unconditionally (a slot that has no column u reads entry 0 of the ELL, which exists
+            // whenever w > 0, and its term is dropped), all of them before the first is used; then all
+            // the LDS gathers of the batch; then the fmas in increasing u per row: the same fma order
+            // and operands as a per-row walk.
             for (int u0 = 0; u0 < w; u0 += XU) {
-                double kvv[XU][R];
+                double kvv[XU][R], dg[XU][R];
                 int kiv[XU][R];
 #pragma unroll
                 for (int uu = 0; uu < XU; ++uu)
 #pragma unroll
                     for (int t = 0; t < R; ++t) {
                         const int u = u0 + uu;
-                        kvv[uu][t] = 0.0;
-                        kiv[uu][t] = 0;
-                        if (u < len[t]) {
-                            kvv[uu][t] = kv[(size_t)(eb[t] + u) * 64 + ln];
-                            kiv[uu][t] = kix[(size_t)(eb[t] + u) * 64 + ln];
-                        }
+                        const size_t e = u < len[t] ? (size_t)(eb[t] + u) : 0;
+                        kvv[uu][t] = kv[e * 64 + ln];
+                        kiv[uu][t] = kix[e * 64 + ln];
                     }
+                // (scheduling fences: left alone, the scheduler pairs every gather with its fma and
+                // waits for each LDS read on its own)
+                __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
                 for (int uu = 0; uu < XU; ++uu)
 #pragma unroll
-                    for (int t = 0; t < R; ++t)
-                        if (u0 + uu < len[t]) xB[t] = fma(kvv[uu][t], dvl[kiv[uu][t]], xB[t]);
+                    for (int t = 0; t < R; ++t) dg[uu][t] = dvl[kiv[uu][t]];
+                __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+                for (int uu = 0; uu < XU; ++uu)
+#pragma unroll
+                    for (int t = 0; t < R; ++t) {
+                        const double v = fma(kvv[uu][t], dg[uu][t], xB[t]);
+                        xB[t] = u0 + uu < len[t] ? v : xB[t];
+                    }
             }
             // the per-slot sign masks from an opaque copy of ubm: hoisted out of the scenario loop
             // they would be 28 loop-invariant 64-bit values, spilled and re-read every scenario
             uint64_t ub = ubm;
             asm volatile("" : "+v"(ub));
 #pragma unroll
-            for (int c = 0; c < C; ++c)
-                d[c] = h_flip(A->d0[(size_t)pb * 64 * C + 64 * c + ln], ((ub >> c) & 1) << 63);
-            bmask = A->basic0[pb * 64 + ln];
+            for (int c = 0; c < C; ++c) d[c] = h_flip(d0r[c], ((ub >> c) & 1) << 63);
+            if (attempt == 0 && q_nx >= 0) {
+                s_nx = has_rec ? __builtin_amdgcn_readfirstlane(rcn.x) : q_nx;
+                pb_nx = has_rec ? __builtin_amdgcn_readfirstlane(rcn.y) : 0;
+            }
         }
         K = 0; status = TWOSD_LP_OPTIMAL; eoff = 0;
         if (lane == 0) etaoff[0] = 0;
         h_wave_sync();
-        if (attempt == 0) {
-            // the claim has returned with the x_B loads: the next position (a range exhausted:
-            // claim from the next one, rare), then its scenario's order entry in flight
-            if (gt < G) {
-                const int g = group_of(gt);
-                const int hi = (int)(((long long)P.N * (g + 1)) / G), lo = (int)(((long long)P.N * g) / G);
-                const int t = __builtin_amdgcn_readfirstlane(__shfl(t_claim, 0));
-                if (lo + t < hi) q_nx = lo + t;
-                else { ++gt; q_nx = claim_sync(); }
-            } else {
-                q_nx = -1;
-            }
-            if (q_nx >= 0) s_nx = CP.order ? CP.order[q_nx] : q_nx;   // resolved after the pivot loop
-        }
         STAMP(0)
 
         // the first-64 entries of etas t0, t0 + dir, ..., t0 + (EG - 1) dir that exist (0 <= t < K).
@@ -519,7 +565,13 @@ __global__ void __launch_bounds__(256, TWOSD_HYPER_WPE(R)) lp_hyper_kernel(Hyper
                 if (nzm != 0) price_batch(__popcll(nzm));
             } else {
                 // ---- 2. BTRAN: u = e_r' E_K..E_1 (u dense in LDS), rho = u' B0^{-1}
-                if (lane == (r & 63)) ut[r] = 1.0;
+                {
+                    // (1.0 built here: as a loop invariant it is kept in a register pair over the whole
+                    // scenario loop, spilled, and reloaded from scratch on the pivot path)
+                    double one = 1.0;
+                    asm volatile("" : "+v"(one));
+                    if (lane == (r & 63)) ut[r] = one;
+                }
                 h_wave_sync();
                 // the rows of rho's first scatter batch (r, then the eta pivot rows) are known before the
                 // etas run: their CSR bounds are loaded over the eta loop instead of after it
@@ -645,6 +697,7 @@ __global__ void __launch_bounds__(256, TWOSD_HYPER_WPE(R)) lp_hyper_kernel(Hyper
             // branch), and the slots with any nonzero alpha' are noted for the dual update: on
             // storm ~9 of the 28 slots hold an eligible column and ~18 a nonzero alpha' per pivot.
             double bnu = INFINITY, bde = 1.0;
+            asm volatile("" : "+v"(bde));   // built here, as the 1.0 of BTRAN
             Mask elm = 0, sel = 0, snz = 0;
             double apf = alpha[lane];
 #pragma unroll
@@ -894,25 +947,28 @@ __global__ void __launch_bounds__(256, TWOSD_HYPER_WPE(R)) lp_hyper_kernel(Hyper
             h_wave_sync();
             STAMP(8)
         }
-        if (attempt == 0 && q_nx >= 0) {   // the next scenario and its pool pick (in flight over the epilogue)
-            s_nx = __builtin_amdgcn_readfirstlane(s_nx);
-            if (CP.npool > 1) pb_nx = CP.pool_pick[s_nx];
-        }
         if (status == TWOSD_LP_OPTIMAL || pb == 0 || !CP.retry) break;
         if (lane == 0 && CP.retries) atomicAdd(CP.retries, 1ull);   // rare: counted for the bench line
         pb = 0;
         }   // attempt
-        // the next scenario's coef_e and dv_e, e = lane, lane + 64 (multiplied at the LDS write)
+        // the next scenario's coef_e and dv_e, e = lane, lane + 64 (multiplied at the LDS write), and
+        // the slot bounds of its start basis: in flight over the epilogue, with the q_j loads
         double dvn0 = 0.0, dvn1 = 0.0, kcn0 = 0.0, kcn1 = 0.0;
-        if (dv_pf && q_nx >= 0) {
+        int ksn = 0, t_claim = 0;
+        if (q_nx >= 0) {
             const auto *A = h_args();
-            const double *dvs = A->dv + (size_t)s_nx * P.k;
-            if (lane < P.k) { dvn0 = dvs[lane]; kcn0 = A->kcoef[lane]; }
-            if (lane + 64 < P.k) { dvn1 = dvs[lane + 64]; kcn1 = A->kcoef[lane + 64]; }
+            t_claim = claim_issue();   // the position after the next one
+            if (lane <= R) ksn = A->kslot[pb_nx * (R + 1) + lane];
+            if (dv_pf) {
+                const double *dvs = A->dv + (size_t)s_nx * P.k;
+                if (lane < P.k) { dvn0 = dvs[lane]; kcn0 = A->kcoef[lane]; }
+                if (lane + 64 < P.k) { dvn1 = dvs[lane + 64]; kcn1 = A->kcoef[lane + 64]; }
+            }
         }
 
         // ---- objective, dual-vertex key, vertex recovery pi = c_B' B^{-1}
         double objv = NAN;
+        unsigned long long keyv = 0;
         if (status == TWOSD_LP_OPTIMAL) {
             // the q_j of all slots loaded together (one pointer, clamped indices), summed in slot order
             const double *qc = CP.q;
@@ -929,6 +985,22 @@ __global__ void __launch_bounds__(256, TWOSD_HYPER_WPE(R)) lp_hyper_kernel(Hyper
                 ob = (hb[t] >= 0 && j < n) ? fma(qv[t], xB[t], ob) : ob;
             }
             objv = wsum(ob);
+        }
+        // the loads issued above have returned with the q_j: the claimed position into an SGPR, the
+        // next scenario's deltas and slot bounds into LDS (dvl is read by the x_B gathers only)
+        q_n2 = -1;
+        if (q_nx >= 0) {
+            q_n2 = claim_resolve(t_claim);
+            if (lane <= R) lsti[lane] = ksn;
+            if (dv_pf) {
+                if (lane < P.k) dvl[lane] = kcn0 * dvn0;
+                if (lane + 64 < P.k) dvl[lane + 64] = kcn1 * dvn1;
+            }
+        }
+        // (a fence: without one the compiler sinks these writes below the output stores, where
+        // their operands' wait also waits for the stores)
+        h_wave_sync();
+        if (status == TWOSD_LP_OPTIMAL) {
             if (CP.vkey) {
                 // key of the dual: pi_i = -d_{n+i} is the reduced cost of row i's slack, kept
                 // current in registers by every pivot (fixed E-row slacks included; unfolded here,
@@ -968,7 +1040,7 @@ __global__ void __launch_bounds__(256, TWOSD_HYPER_WPE(R)) lp_hyper_kernel(Hyper
                 }
 #pragma unroll
                 for (int o = 32; o > 0; o >>= 1) h += __shfl_xor(h, o);
-                if (lane == 0) CP.vkey[s] = h;
+                keyv = h;
             }
         }
         if constexpr (FULL) {
@@ -1074,20 +1146,28 @@ __global__ void __launch_bounds__(256, TWOSD_HYPER_WPE(R)) lp_hyper_kernel(Hyper
             }
         }
         }   // FULL
-        if (lane == 0) {
-            CP.obj[s] = objv;
-            CP.status[s] = status;
-            CP.iters[s] = it;
-            if (CP.ops) CP.ops[s] = (long long)nops;
-            if (CP.etan) CP.etan[s] = eoff;   // the eta-arena entries this solve wrote (12 B each)
-            if (CP.npool > 1) CP.pool_pick[s] = pb;   // 0 if the pool start was retried
-        }
-        if (dv_pf && q_nx >= 0) {
-            if (lane < P.k) dvl[lane] = kcn0 * dvn0;
-            if (lane + 64 < P.k) dvl[lane + 64] = kcn1 * dvn1;
+        {
+            // the per-scenario outputs: their pointers sit side by side in the argument block (one
+            // scalar load), the stores go out back to back
+            const auto *A = h_args();
+            double *const o_obj = A->obj;
+            int *const o_status = A->status, *const o_iters = A->iters, *const o_etan = A->etan, *const o_pick = A->pool_pick;
+            long long *const o_ops = A->ops;
+            unsigned long long *const o_key = A->vkey;
+            // (the scenario as an SGPR value: the store addresses are formed here, on the scalar
+            // unit, not from a 64-bit vector copy of s that is spilled and reloaded for every store)
+            const int su = __builtin_amdgcn_readfirstlane(s);
+            if (lane == 0) {
+                o_obj[su] = objv;
+                o_status[su] = status;
+                o_iters[su] = it;
+                if (o_ops) o_ops[su] = (long long)nops;
+                if (o_etan) o_etan[su] = eoff;   // the eta-arena entries this solve wrote (12 B each)
+                if (o_pick) o_pick[su] = pb;     // 0 if the pool start was retried
+                if (o_key && status == TWOSD_LP_OPTIMAL) o_key[su] = keyv;
+            }
         }
         h_wave_sync();
-        pb_nx = __builtin_amdgcn_readfirstlane(pb_nx);
         STAMP(9)
     }
     STAMP_FLUSH
@@ -1399,6 +1479,20 @@ hipError_t launch_pool_select(const PoolSelParams &p, hipStream_t s) {
     const int G = p.pkey ? pool_select_split(p.N, p.npool) : 1;
     hipLaunchKernelGGL(pool_select_kernel, dim3(nb, G), dim3(64 * kSelWaves), pool_select_lds_bytes(p.k), s, p);
     if (G > 1) hipLaunchKernelGGL(pool_select_merge_kernel, dim3((p.N + 255) / 256), dim3(256), 0, s, p.N, G, p.pkey, p.ppick, p.pick, p.key);
+    return hipGetLastError();
+}
+
+// ---- one record per queue position: its scenario and that scenario's start basis
+__global__ void __launch_bounds__(256) queue_records_kernel(int N, const int *__restrict__ order, const int *__restrict__ pick,
+                                                           int2 *__restrict__ qrec) {
+    const int q = blockIdx.x * blockDim.x + threadIdx.x;
+    if (q >= N) return;
+    const int s = order ? order[q] : q;
+    qrec[q] = make_int2(s, pick ? pick[s] : 0);
+}
+hipError_t launch_queue_records(const int *order, const int *pick, int2 *qrec, int N, hipStream_t s) {
+    if (N <= 0) return hipSuccess;
+    hipLaunchKernelGGL(queue_records_kernel, dim3((N + 255) / 256), dim3(256), 0, s, N, order, pick, qrec);
     return hipGetLastError();
 }
 

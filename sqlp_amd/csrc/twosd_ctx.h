@@ -95,6 +95,8 @@ struct twosd_ctx {
     int *d_order = nullptr;       // LP visiting order grouped by pool basis
     char *d_sort_tmp = nullptr;
     size_t order_cap = 0, sort_tmp_bytes = 0;
+    int2 *d_qrec = nullptr;       // LP launch: (scenario, start basis) per queue position
+    size_t qrec_cap = 0;
     bool want_head = false;
     bool prep_valid = false;
     bool k_valid = false;         // K rows / ELL of the pool (depend on the pool and the positions)

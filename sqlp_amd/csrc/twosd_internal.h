@@ -45,10 +45,18 @@ struct HyperParams {
     int *eidx; double *evals;                           // nslots x ecap sparse eta arena
     int *queue;                                         // qgroups heads, kQueueStride ints apart
     int qgroups;                                        // XCD-group work queues (>= 1)
-    double *obj, *pi, *y;
+    // per-scenario outputs, side by side (the kernel's epilogue fetches them with one scalar load)
+    double *obj;
     int *status, *iters;
-    long long *ops;                                     // executed FMAs
+    long long *ops;                                     // executed FMAs (nullable)
     int *etan;                                          // N: eta-file entries of the final solve (nullable)
+    int *pool_pick;                                     // N: the start basis each solve ended from (npool > 1, else
+                                                        //   nullptr; 0 if the pool start was retried)
+    // dual key mode (solve_push): per scenario a 64-bit key of its optimal dual (from the
+    // maintained slack reduced costs, 24 significant bits); with pi == y == nullptr the vertex
+    // recovery is skipped
+    unsigned long long *vkey;                           // N (nullable)
+    double *pi, *y;
     unsigned long long *retries;                        // pool starts retried from the primary basis (nullable)
     unsigned long long *stamps;                         // [10] phase cycles (TWOSD_STAMPS builds only)
     // basis pool: xbase, hb0 (npool x MP), brptr / bcp (npool x (MP+1), absolute offsets),
@@ -56,12 +64,8 @@ struct HyperParams {
     int npool;
     const int *bnnz;                                    // npool: nnz of B^{-1} (ops accounting)
     int *head_out;                                      // N x m final basis (nullable)
-    int *pool_pick;                                     // N pool basis per scenario (in; npool > 1)
-    const int *order;                                   // N visiting order of the scenarios (nullable)
-    // dual key mode (solve_push): per scenario a 64-bit key of its optimal dual (from the
-    // maintained slack reduced costs, 24 significant bits); with pi == y == nullptr the vertex
-    // recovery is skipped
-    unsigned long long *vkey;                           // N (nullable)
+    const int2 *qrec;                                   // N: (scenario, start pool basis) of queue position q
+                                                        //   (launch_queue_records; nullptr: (q, 0))
     double key_zero;                                    // key components <= key_zero (1 + max) snap to 0
     int pi_by_pos;                                      // pi / head row = queue position instead of scenario
     // basis key (pool refresh): sum of mix64(j) over the basic columns of the optimal basis
@@ -169,6 +173,8 @@ size_t hyper_lds_bytes(int R, int C, int kmax, int k);   // C = column slots (hy
 int hyper_rows_per_lane(int m);
 int hyper_cols_per_lane(int ncols);
 hipError_t launch_hyper(int R, int C, const HyperParams &p, int nblocks, size_t lds, hipStream_t s);
+// qrec[q] = (order ? order[q] : q, pick ? pick[that scenario] : 0) for q in [0, N)
+hipError_t launch_queue_records(const int *order, const int *pick, int2 *qrec, int N, hipStream_t s);
 int hyper_max_blocks_per_cu(int R, int C, int kmax, int k);
 
 
