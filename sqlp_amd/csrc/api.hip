@@ -2020,8 +2020,8 @@ __device__ __forceinline__ double dev_infeas(double x, int bt) {
 
 // Selection stream of one pool basis per block (prepare_x, per x; hb0 = head * 4 + bound type): the rows of basis p that can
 // turn infeasible on the training box of the deltas, ordered by their worst box infeasibility
-// (largest first, row index on ties), each written as a row-start record (-1 - bound type,
-// x_B,i) followed by its element entries (e, B_p^{-1}[i][row_e]) at the basis's static capacity
+// (largest first, row index on ties), each written as a row-start record (sign-folded
+// x_B,i, the sentinel offset k * 65 * 8) followed by its element entries (e, B_p^{-1}[i][row_e]) at the basis's static capacity
 // offset; rows without entries add their constant infeasibility to cinf[p] (fixed-order sum).
 constexpr int kSelStreamThreads = 256;
 // count weight of the selection key in units of the mean |coef_e| E|V_e - E V_e| (storm: 13.5;
@@ -2140,8 +2140,9 @@ __global__ void __launch_bounds__(kSelStreamThreads) pool_selstream_kernel(
         for (int cpy = 0; cpy < ncopy; ++cpy) {
             const float sg = (t == BT_Y || t == BT_L || cpy == 1) ? -1.0f : 1.0f;
             int2 *o = out + cpy * (1 + q1 - q0);
-            // record (value bits, byte offset of the element's staged pair row e * 65 * 8; -1: row start)
-            if (lane == 0) o[0] = make_int2(__float_as_int(sg * (float)xbase[(size_t)p * MP + i]), -1);
+            // record (value bits, byte offset of the element's staged pair row e * 65 * 8; row start: the
+            // offset of row k, which the selection kernels keep zeroed)
+            if (lane == 0) o[0] = make_int2(__float_as_int(sg * (float)xbase[(size_t)p * MP + i]), k * 65 * 8);
             for (int q = q0 + lane; q < q1; q += 64) o[1 + q - q0] = make_int2(__float_as_int(sg * (float)kraw[q]), ke[q] * 65 * 8);
         }
     }

@@ -1215,25 +1215,29 @@ __device__ __forceinline__ void h_stage_pairs(float *dvt, const double *__restri
         dvt[2 * (e * 65 + (sl & 63)) + (sl >> 6)] = sl < nv ? (float)(kcoef[e] * dv[(size_t)srow(sl) * k + e]) : 0.0f;
     }
 }
-// byte address of the staged pair of element `off` (the record's byte offset e * 65 * 8; row starts
-// carry -1 and read element 0) for this lane, computed on the VALU: the record streams are
-// wave-uniform, so on the scalar unit every record's address would add two SALU instructions to
-// a loop that is SALU-bound already
-__device__ __forceinline__ const sel_f2 *h_pair_addr(const sel_f2 *dvt2, int off, int lane8) {
-    int o;
-    asm("v_max_i32 %0, %1, 0" : "=v"(o) : "s"(off));
-    return reinterpret_cast<const sel_f2 *>(reinterpret_cast<const char *>(dvt2) + o + lane8);
+// Row-start records carry the byte offset of one more pair row behind the staged tile (row k, zeroed
+// here): the offset is non-negative like every other, so a record's LDS address is one add of the
+// wave-uniform offset to the lane's base, and the row-start test a compare with an SGPR
+__device__ __forceinline__ int h_sel_sentinel(int k) { return k * 65 * 8; }
+__device__ __forceinline__ void h_stage_sentinel(float *dvt, int k) {
+    for (int idx = threadIdx.x; idx < 2 * 65; idx += 64 * kSelWaves) dvt[2 * 65 * k + idx] = 0.0f;
+}
+// address of the staged pair of the record's byte offset `off` (e * 65 * 8; row starts: the zeroed
+// sentinel row) for the lane whose pair of row 0 is at `lbase`: one VALU add of an SGPR (the record
+// streams are wave-uniform; on the scalar unit the address would cost a copy to a VGPR besides)
+__device__ __forceinline__ const sel_f2 *h_pair_addr(const char *lbase, int off) {
+    return reinterpret_cast<const sel_f2 *>(lbase + off);
 }
 // one basis' record stream for both scenarios of the lane (records (value bits, byte offset); offset
-// < 0: row start), pruned once no scenario of the wave can still win (alive2); returns the pair's
+// == sent: row start), pruned once no scenario of the wave can still win (alive2); returns the pair's
 // keys (inf when pruned)
 template <typename Alive>
 __device__ __forceinline__ sel_f2 h_stream2(const int2 *__restrict__ rec, int j0, int j1, float cinf, float cw,
-                                            const sel_f2 *dvt2, int lane, Alive alive2) {
+                                            const sel_f2 *dvt2, int sent, int lane, Alive alive2) {
     sel_f2 inf = {cinf, cinf}, x = {0.0f, 0.0f};
-    const int lane8 = 8 * lane;
+    const char *lbase = reinterpret_cast<const char *>(dvt2) + 8 * lane;
     auto step = [&](int code, float v, sel_f2 dl) {
-        if (code < 0) {   // next row: close the previous one
+        if (code == sent) {   // next row: close the previous one
             inf += h_viol_f2(x, cw);
             x = (sel_f2){v, v};
         } else {
@@ -1247,7 +1251,7 @@ __device__ __forceinline__ sel_f2 h_stream2(const int2 *__restrict__ rec, int j0
 #pragma unroll
         for (int u = 0; u < kSelB; ++u) rc[u] = rec[j + u];
 #pragma unroll
-        for (int u = 0; u < kSelB; ++u) dl[u] = *h_pair_addr(dvt2, rc[u].y, lane8);
+        for (int u = 0; u < kSelB; ++u) dl[u] = *h_pair_addr(lbase, rc[u].y);
 #pragma unroll
         for (int u = 0; u < kSelB; ++u) step(rc[u].y, __int_as_float(rc[u].x), dl[u]);
         // exact pruning: inf only grows, so once no scenario of the wave can still beat its best,
@@ -1256,14 +1260,14 @@ __device__ __forceinline__ sel_f2 h_stream2(const int2 *__restrict__ rec, int j0
     }
     for (; j < j1; ++j) {
         const int2 r = rec[j];
-        step(r.y, __int_as_float(r.x), *h_pair_addr(dvt2, r.y, lane8));
+        step(r.y, __int_as_float(r.x), *h_pair_addr(lbase, r.y));
     }
     inf += h_viol_f2(x, cw);
     return inf;
 }
 
 __global__ void __launch_bounds__(64 * kSelWaves) pool_select_kernel(PoolSelParams S) {
-    extern __shared__ float dvt[];   // k x 65 pairs
+    extern __shared__ float dvt[];   // (k + 1) x 65 pairs
     const sel_f2 *dvt2 = reinterpret_cast<const sel_f2 *>(dvt);
     __shared__ float bsum[kSelWaves][kSelTile];
     __shared__ int bidx[kSelWaves][kSelTile];
@@ -1275,6 +1279,8 @@ __global__ void __launch_bounds__(64 * kSelWaves) pool_select_kernel(PoolSelPara
     const int wid = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);   // wave-uniform: scalar stream loads
     const int s0 = blockIdx.x * kSelTile;
     const int ns = min(kSelTile, S.N - s0);
+    const int sent = h_sel_sentinel(S.k);
+    h_stage_sentinel(dvt, S.k);
     h_stage_pairs(dvt, S.dv, S.kcoef, S.k, ns, [&](int sl) { return s0 + sl; });
     if (threadIdx.x < kSelTile) sbest[threadIdx.x] = 0x7f800000u;   // +inf
     __syncthreads();
@@ -1292,7 +1298,7 @@ __global__ void __launch_bounds__(64 * kSelWaves) pool_select_kernel(PoolSelPara
     const int p_lo = (int)((long long)S.npool * blockIdx.y / gridDim.y), p_hi = (int)((long long)S.npool * (blockIdx.y + 1) / gridDim.y);
     bpx = bpy = p_lo;
     for (int p = p_lo + wid; p < p_hi; p += kSelWaves) {
-        const sel_f2 inf = h_stream2(S.rec, S.sptr[p], S.send[p], S.cinf[p], S.cw, dvt2, lane, alive2);
+        const sel_f2 inf = h_stream2(S.rec, S.sptr[p], S.send[p], S.cinf[p], S.cw, dvt2, sent, lane, alive2);
         if (inf.x < best.x) {
             best.x = inf.x;
             bpx = p;
@@ -1334,21 +1340,26 @@ __global__ void __launch_bounds__(64 * kSelWaves) pool_select_kernel(PoolSelPara
 // its records wave-uniformly, as in level 1.  Result per scenario: least (key, ci) with the
 // level-1 pick as ci = -1, i.e. a candidate replaces the pick only with a strictly smaller key,
 // and among equal keys the earlier candidate wins (deterministic).
-__global__ void __launch_bounds__(64 * kSelWaves) pool_refine_kernel(PoolRefineParams S) {
-    extern __shared__ float dvt[];   // k x 65 pairs
+// Two blocks per CU need 8 waves per SIMD: at most 64 VGPRs and 96 SGPRs.  Left to itself the compiler
+// takes 106 SGPRs here (7 waves per SIMD, so one 16-wave block per CU: half the block slots stood
+// empty, per-block stamps in profiles/r09); the second launch bound makes it spill a few SGPRs to
+// VGPR lanes outside the record loop instead.
+__global__ void __launch_bounds__(64 * kSelWaves, 8) pool_refine_kernel(PoolRefineParams S) {
+    extern __shared__ float dvt[];   // (k + 1) x 65 pairs
     const sel_f2 *dvt2 = reinterpret_cast<const sel_f2 *>(dvt);
     __shared__ float rkey[kSelWaves][kSelTile];
     __shared__ int rci[kSelWaves][kSelTile];
     __shared__ unsigned sbest[kSelTile];   // best key so far over all waves, per scenario (as in level 1)
     const int lane = threadIdx.x & 63;
     const int wid = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    // XCD-aware tile remap: consecutive tiles (the same level-1 pick group, the same candidate
-    // record streams) go to blocks b, b + 8, ... which share one XCD's L2 under round-robin
-    // placement (speed only; any bijection is correct)
-    const int nb = gridDim.x, b = blockIdx.x, xq = nb >> 3, xr = nb & 7, xc = b & 7;
-    const int tile = xc * xq + min(xc, xr) + (b >> 3);
+    // tile = block: the blocks in flight at any time cover a short stretch of the sorted order on all
+    // XCDs.  (A remap that gave each XCD one contiguous eighth of the order, for its L2, bought no
+    // shorter blocks and left the XCDs with the cheaper eighths idle for the last sixth of the launch.)
+    const int tile = blockIdx.x;
     const int t0 = tile * kSelTile;
     const int nv = min(kSelTile, S.N - t0);
+    const int sent = h_sel_sentinel(S.k);
+    h_stage_sentinel(dvt, S.k);
     h_stage_pairs(dvt, S.dv, S.kcoef, S.k, nv, [&](int sl) { return S.order[t0 + sl]; });
     const bool vx = lane < nv, vy = 64 + lane < nv;
     const int sx = vx ? S.order[t0 + lane] : 0, sy = vy ? S.order[t0 + 64 + lane] : 0;
@@ -1382,7 +1393,7 @@ __global__ void __launch_bounds__(64 * kSelWaves) pool_refine_kernel(PoolRefineP
         for (int ci = c_lo + wid; ci < c_hi; ci += kSelWaves) {
             const int cb = S.cand[(size_t)g * S.ncand + ci];
             if (cb < 0) break;
-            const sel_f2 inf = h_stream2(S.rec, S.sptr[cb], S.send[cb], S.cinf[cb], S.cw, dvt2, lane, alive2);
+            const sel_f2 inf = h_stream2(S.rec, S.sptr[cb], S.send[cb], S.cinf[cb], S.cw, dvt2, sent, lane, alive2);
             if (mx && inf.x < best.x) {
                 best.x = inf.x;
                 bcx = ci;
@@ -1471,7 +1482,7 @@ hipError_t launch_pool_refine(const PoolRefineParams &p, hipStream_t s) {
     return hipGetLastError();
 }
 
-size_t pool_select_lds_bytes(int k) { return (size_t)4 * 65 * (kSelTile / 64) * (size_t)std::max(k, 1); }
+size_t pool_select_lds_bytes(int k) { return (size_t)4 * 65 * (kSelTile / 64) * (size_t)(std::max(k, 0) + 1); }   // + the sentinel row
 
 hipError_t launch_pool_select(const PoolSelParams &p, hipStream_t s) {
     if (p.N <= 0) return hipSuccess;

@@ -141,7 +141,7 @@ struct PoolSelParams {
     const float *cinf;                                  // npool: infeasibility of the constant rows
     const int *sptr, *send;                             // npool: [sptr[p], send[p]) = records of basis p
     const int2 *rec;                                    // (float bits, code): row start (sign-folded xbase_i,
-                                                        //   -1); entry (sign * B^{-1}[i][row_e], e * 65 * 8)
+                                                        //   k * 65 * 8); entry (sign * B^{-1}[i][row_e], e * 65 * 8)
     int *pick;                                          // N out
     float cw;                                           // key = sum |infeas| + cw * #infeasible rows
     float *key;                                         // N out (nullable): key of the pick
