@@ -21,6 +21,22 @@
  *     pi = d obj / d rhs), so obj = pi . (r_w - T_w x).
  *   - Variables of the simplex basis ("head"): j < n2 is structural y_j; j = n2 + i is the
  *     slack of row i.
+ *   - General bounds lo <= y <= hi (twosd_set_template): the library solves the canonical LP of
+ *     twosd_canonical_form (y' >= 0, m_lp = m2 + nb rows, n_lp columns; nb = boxed variables),
+ *     see twosd_lp_shape.  Callers see:
+ *       y            in their own space (n2 entries, every one within its bounds);
+ *       objectives   of their own LP (obj[], twosd_last_objective, twosd_evaluate_sampled,
+ *                    max_val[], alpha all include the shift's constant c0 = q.s);
+ *       dual vectors of length mv = m_lp = m2 + nb: the m2 row duals (JuMP's convention), then
+ *                    one multiplier <= 0 per boxed variable (ascending j), with
+ *                        obj = v . [ r_w - T_w x - W s ; hi - lo ] + c0
+ *                    (s = the shift point of each column: lo, hi of a (-inf, hi] column, or 0).
+ *                    pi of twosd_solve_batch / twosd_solve_values and the vectors of
+ *                    twosd_dvs_push / twosd_dvs_get have that length;
+ *       basis heads  (set_basis, get_basis, pool_*) in the LP's numbering: m_lp entries, j < n_lp
+ *                    an LP column, j = n_lp + i the slack of LP row i;
+ *       scenario values in their own space (the caller's r, never the shifted one).
+ *     With every bound [0, +inf) all of this equals m2 / n2 and the template is the caller's own.
  */
 #ifndef TWOSD_HIP_H
 #define TWOSD_HIP_H
@@ -59,8 +75,14 @@ int twosd_destroy(twosd_ctx *ctx);
  * Stage-2 template (replaces extract_coefficients, subprob.jl:15-69, and the JuMP model
  * held by spStageProblem, prob.jl:10-15).
  *   T: m2 x n1 CSC (colptr[n1+1], rowval[nnzT], nzval[nnzT]); W: m2 x n2 CSC.
- *   q[n2], r[m2], sense[m2] in {'G','L','E'}, ylb/yub[n2] (only [0, +inf) is supported:
- *   the reference warns on other bounds, subprob.jl:19-26).
+ *   q[n2], r[m2], sense[m2] in {'G','L','E'}, ylb/yub[n2] (NULL: 0 / +inf; -inf / +inf for an
+ *   absent bound).  Bounds other than [0, +inf) are removed by twosd_canonical_form and every
+ *   kernel runs on the canonical LP (the reference only warns on them and drops the bound
+ *   multipliers from its cuts, subprob.jl:19-26; here a dual vertex carries them, see the
+ *   conventions above).  A template whose bounds are all [0, +inf) is used as given.  The
+ *   kernel envelope (1024 rows, the column slots, the LDS slice) applies to the LP's sizes:
+ *   each boxed variable costs one row.  TWOSD_E_ARG for bounds that are no interval (lo > hi,
+ *   NaN, lo = +inf, hi = -inf).
  * Re-setting the template clears basis, scenarios, dual vertex set and cuts.
  */
 int twosd_set_template(twosd_ctx *ctx, int m2, int n1, int n2,
@@ -69,10 +91,39 @@ int twosd_set_template(twosd_ctx *ctx, int m2, int n1, int n2,
                        const double *q, const double *r, const char *sense,
                        const double *ylb, const double *yub, int index_base);
 
+/* Sizes of the LP the kernels solve for the current template: rows m_lp = m2 + n_bound_rows,
+ * columns n_lp, bound rows (= boxed variables).  (m2, n2, 0) when every bound is [0, +inf).
+ * Dual vectors and basis heads have m_lp entries.  Outputs nullable. */
+int twosd_lp_shape(twosd_ctx *ctx, int *m_lp, int *n_lp, int *n_bound_rows);
+
+/*
+ * Canonical form of a stage-2 LP with general bounds (host code only: no context, no GPU call;
+ * twosd_set_template applies it).  Per column j with lo = ylb[j], hi = yub[j]:
+ *   [0, +inf)   unchanged                   [lo, +inf)   y = lo + y'
+ *   (-inf, hi]  y = hi - y' (column and cost negated)
+ *   free        y = y+ - y-, the y- columns appended after the kept columns, ascending j
+ *   lo = hi     the column leaves the LP, y_j = lo
+ *   [lo, hi]    y = lo + y' and one 'L' row y' <= hi - lo, appended after the m2 rows, ascending j
+ * With s the shift point (lo; hi of the negated kind; else 0): out_r = [r - W s ; hi - lo] (the
+ * columns with s != 0 in ascending j, entries in CSC order), *c0 = q.s, and T gains zero rows.
+ * Outputs (caller-allocated for the worst case; each nullable): out_colptr[2 n2 + 1],
+ * out_rowval / out_nzval[2 nnz(W) + n2], out_q[2 n2], out_r / out_sense[m2 + n2] -- *n_lp + 1,
+ * nnz, *n_lp and *m_lp entries are written, indices in index_base.  The column table maps a
+ * solution back: y_j = col_off[j] + col_sign[j] * y'[col_src[j]] - y'[col_src2[j]], an index of -1
+ * (either base) meaning the term is absent; box_col[b] is the column of bound row m2 + b.  With
+ * every bound [0, +inf) the outputs equal the inputs bit for bit and *n_bound_rows = 0.
+ */
+int twosd_canonical_form(int m2, int n2, const int64_t *W_colptr, const int64_t *W_rowval, const double *W_nzval,
+                         const double *q, const double *r, const char *sense, const double *ylb, const double *yub,
+                         int index_base, int *m_lp, int *n_lp, int *n_bound_rows, int64_t *out_colptr,
+                         int64_t *out_rowval, double *out_nzval, double *out_q, double *out_r, char *out_sense,
+                         double *c0, int *col_src, double *col_sign, double *col_off, int *col_src2, int *box_col);
+
 /*
  * Random element positions of a scenario (spSmpsScenario entries, smps_sto.jl:135):
- * element e sits at stage-2 row row[e]; col[e] = -1 for an RHS entry, else the
- * first-stage column of a T entry (delta_coefficients, subprob.jl:104-121).
+ * element e sits at stage-2 row row[e] (a row of the caller's template: < m2, never a bound
+ * row); col[e] = -1 for an RHS entry, else the first-stage column of a T entry
+ * (delta_coefficients, subprob.jl:104-121).
  */
 int twosd_set_random_positions(twosd_ctx *ctx, int k, const int *row, const int *col, int index_base);
 

@@ -34,6 +34,7 @@ check(rc) = rc == 0 || error(unsafe_string(ccall((:twosd_last_error, LIB), Cstri
 mutable struct HipContext                     # one per cell per GPU; finalizer frees device memory
     h::Ptr{Cvoid}
     nrow::Int; n1::Int; n2::Int
+    mv::Int                                   # dual vector length: nrow + boxed stage-2 variables (twosd_lp_shape)
     positions::Vector{TwoSD.spSmpsPosition}
     has_basis::Bool
 end
@@ -50,17 +51,25 @@ function HipContext(sp2::TwoSD.spStageProblem, sto::TwoSD.spStoType; device::Int
     q = Float64[coefficient(objective_function(sp2.model), v) for v in sp2.current_stage_vars]
     sense = UInt8[row_sense(c) for c in sp2.stage_constraints]
     r = Vector{Float64}(coef.rhs)
+    # the JuMP bounds of the stage-2 variables (LO / UP / FX / FR / MI / boxed): the library removes
+    # them by its canonical form and its duals carry the boxed variables' multipliers, where
+    # extract_coefficients only warns (subprob.jl:19-26).  This path, like the rest of the file, is
+    # not executed in this repository.
+    ylb = Float64[is_fixed(v) ? fix_value(v) : has_lower_bound(v) ? lower_bound(v) : -Inf for v in sp2.current_stage_vars]
+    yub = Float64[is_fixed(v) ? fix_value(v) : has_upper_bound(v) ? upper_bound(v) : Inf for v in sp2.current_stage_vars]
     check(ccall((:twosd_set_template, LIB), Cint,
         (Ptr{Cvoid}, Cint, Cint, Cint, Ptr{Int64}, Ptr{Int64}, Ptr{Float64}, Ptr{Int64}, Ptr{Int64}, Ptr{Float64},
          Ptr{Float64}, Ptr{Float64}, Ptr{UInt8}, Ptr{Float64}, Ptr{Float64}, Cint),
         ref[], size(T, 1), size(T, 2), size(W, 2), T.colptr, T.rowval, T.nzval, W.colptr, W.rowval, W.nzval,
-        q, r, sense, C_NULL, C_NULL, 1))                        # index_base = 1: Julia arrays as-is
+        q, r, sense, ylb, yub, 1))                              # index_base = 1: Julia arrays as-is
+    mlp = Ref{Cint}(0)
+    check(ccall((:twosd_lp_shape, LIB), Cint, (Ptr{Cvoid}, Ref{Cint}, Ptr{Cint}, Ptr{Cint}), ref[], mlp, C_NULL, C_NULL))
     pos = collect(keys(sto.indep))
     rows = Cint[coef.row_lookup[p.row_name] for p in pos]       # KeyError as subprob.jl:112,116
     cols = Cint[p.col_name in ("RHS", "rhs") ? -1 : coef.col_lookup[p.col_name] for p in pos]
     check(ccall((:twosd_set_random_positions, LIB), Cint, (Ptr{Cvoid}, Cint, Ptr{Cint}, Ptr{Cint}, Cint),
                 ref[], length(pos), rows, cols, 1))
-    ctx = HipContext(ref[], size(T, 1), size(T, 2), size(W, 2), pos, false)
+    ctx = HipContext(ref[], size(T, 1), size(T, 2), size(W, 2), Int(mlp[]), pos, false)
     finalizer(c -> ccall((:twosd_destroy, LIB), Cint, (Ptr{Cvoid},), c.h), ctx)
     return ctx
 end
@@ -76,9 +85,10 @@ function compute_basis!(ctx::HipContext, x::Vector{Float64}, ω::TwoSD.spSmpsSce
     ctx.has_basis = true
 end
 
-# solve_problem!(sp, x, ω) -> (obj, y, π) of smps_routines.jl:50-62 on the device
+# solve_problem!(sp, x, ω) -> (obj, y, π) of smps_routines.jl:50-62 on the device; π has ctx.mv
+# entries (the row duals, then one multiplier <= 0 per boxed variable), y is within its bounds
 function solve_problem(ctx::HipContext, x::Vector{Float64}, ω::TwoSD.spSmpsScenario)
-    obj = Ref(0.0); st = Ref{Cint}(0); y = zeros(ctx.n2); π = zeros(ctx.nrow)
+    obj = Ref(0.0); st = Ref{Cint}(0); y = zeros(ctx.n2); π = zeros(ctx.mv)
     v = element_values(ctx, ω)
     GC.@preserve v y π check(ccall((:twosd_solve_values, LIB), Cint,
         (Ptr{Cvoid}, Ptr{Float64}, Cint, Ptr{Float64}, Ref{Float64}, Ptr{Float64}, Ptr{Float64}, Ref{Cint}),
@@ -135,6 +145,7 @@ end
 # The cell's dual vertex set lives on the device (dual_set.jl:69-127); push!/length as the reference
 struct HipDualVertexSet; ctx::HipContext; end
 function Base.push!(V::HipDualVertexSet, π::Vector{Float64})
+    length(π) == V.ctx.mv || error("push!: dual vector of length $(length(π)), expected $(V.ctx.mv)")
     n = Ref{Cint}(0)
     check(ccall((:twosd_dvs_push, LIB), Cint, (Ptr{Cvoid}, Cint, Ptr{Float64}, Ptr{Cint}, Ref{Cint}),
                 V.ctx.h, 1, π, C_NULL, n))

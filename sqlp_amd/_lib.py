@@ -30,6 +30,8 @@ SIGNATURES = [
     ("twosd_create", I, [I, P]),
     ("twosd_destroy", I, [P]),
     ("twosd_set_template", I, [P, I, I, I, P, P, P, P, P, P, P, P, P, P, P, I]),
+    ("twosd_lp_shape", I, [P, P, P, P]),
+    ("twosd_canonical_form", I, [I, I, P, P, P, P, P, P, P, P, I, P, P, P, P, P, P, P, P, P, P, P, P, P, P, P]),
     ("twosd_set_random_positions", I, [P, I, P, P, I]),
     ("twosd_compute_basis", I, [P, P, P]),
     ("twosd_set_basis", I, [P, P]),

@@ -283,6 +283,8 @@ static int upload(T **d, const std::vector<T> &h) {
 static void free_template(twosd_ctx *c) {
     dfree(c->d_colptr); dfree(c->d_rowidx); dfree(c->d_val); dfree(c->d_q); dfree(c->d_btype);
     dfree(c->d_fixedmask); dfree(c->d_ubmask);
+    dfree(c->d_bm_src); dfree(c->d_bm_src2); dfree(c->d_bm_sign); dfree(c->d_bm_off); dfree(c->d_yu);
+    c->yu_cap = 0; c->has_bounds = false; c->nb = 0; c->c0 = 0.0;
     dfree(c->d_hb0); dfree(c->d_basic0);
     dfree(c->d_xbase); dfree(c->d_queue); dfree(c->d_lpstats);
     dfree(c->d_obj); dfree(c->d_pi); dfree(c->d_pi_rep); dfree(c->d_y); dfree(c->d_status); dfree(c->d_iters); dfree(c->d_ops); dfree(c->d_etan);
@@ -331,6 +333,161 @@ extern "C" int twosd_destroy(twosd_ctx *c) {
     return TWOSD_OK;
 }
 
+// ---- general stage-2 bounds: canonical form ------------------------------------------------
+// min q'y, W y (senses) b, lo <= y <= hi  ->  min q'y' + c0, W' y' (senses') b', y' >= 0, per column
+// (lo, hi):  [0, inf) kept;  [lo, inf) y = lo + y';  (-inf, hi] y = hi - y' (column and cost
+// negated);  free y = y+ - y- (the y- columns appended after the kept ones, ascending j);
+// lo = hi: the column leaves the LP;  [lo, hi] y = lo + y' plus one L row y' <= hi - lo (appended
+// after the m2 rows, ascending j).  s is the shift point (lo, hi of the negated kind, or 0):
+// r' = r - W s over the columns with s != 0 in ascending j, entries in CSC order; c0 = q.s likewise.
+// A dual of the canonical LP is the m2 row duals followed by one multiplier <= 0 per boxed
+// variable; the unbounded kinds need none (their dual constraint is the LP's own column).
+namespace {
+struct Canon {
+    bool any = false;             // false: every bound is [0, +inf), the arrays below are the input's
+    int m_lp = 0, n_lp = 0, nb = 0;
+    std::vector<int> colptr, rowidx;
+    std::vector<double> val, q, r;
+    std::vector<char> sense;
+    double c0 = 0.0;
+    // back-map of caller column j: y_j = off[j] + sign[j] * y'[src[j]] - y'[src2[j]] (src / src2 = -1: term absent)
+    std::vector<int> src, src2, box_col;
+    std::vector<double> sign, off;
+};
+}  // namespace
+
+// W: m2 x n2 CSC, 0-based; ylb / yub nullable (0 / +inf)
+static int canonical_form_impl(int m2, int n2, const int *cp, const int *ri, const double *v, const double *q,
+                               const double *r, const char *sense, const double *ylb, const double *yub, Canon &K) {
+    enum { KEEP, SHIFT, NEG, FREE, FIXED, BOX };
+    std::vector<int> kind(n2, KEEP);
+    std::vector<double> s(n2, 0.0);
+    K = Canon();
+    int nfree = 0, nfixed = 0;
+    for (int j = 0; j < n2; ++j) {
+        const double lo = ylb ? ylb[j] : 0.0, hi = yub ? yub[j] : INFINITY;
+        if (std::isnan(lo) || std::isnan(hi) || lo > hi || lo == INFINITY || hi == -INFINITY)
+            return fail(TWOSD_E_ARG, "y[%d] bounds [%g, %g] are not an interval", j, lo, hi);
+        const bool flo = std::isfinite(lo), fhi = std::isfinite(hi);
+        if (flo && !fhi) kind[j] = lo == 0.0 ? KEEP : SHIFT;
+        else if (!flo && fhi) kind[j] = NEG;
+        else if (!flo && !fhi) kind[j] = FREE;
+        else kind[j] = lo == hi ? FIXED : BOX;
+        s[j] = kind[j] == NEG ? hi : (flo ? lo : 0.0);
+        if (kind[j] == KEEP) s[j] = 0.0;
+        K.any |= kind[j] != KEEP;
+        K.nb += kind[j] == BOX;
+        nfree += kind[j] == FREE;
+        nfixed += kind[j] == FIXED;
+    }
+    K.src.assign(n2, -1); K.src2.assign(n2, -1);
+    K.sign.assign(n2, 1.0); K.off.assign(n2, 0.0);
+    K.m_lp = m2 + K.nb;
+    K.n_lp = n2 - nfixed + nfree;
+    K.r.assign(r, r + m2);
+    K.sense.assign(sense, sense + m2);
+    if (!K.any) {
+        K.colptr.assign(cp, cp + n2 + 1);
+        K.rowidx.assign(ri, ri + cp[n2]);
+        K.val.assign(v, v + cp[n2]);
+        K.q.assign(q, q + n2);
+        for (int j = 0; j < n2; ++j) K.src[j] = j;
+        return TWOSD_OK;
+    }
+    // r' = r - W s and c0 = q.s, columns ascending
+    for (int j = 0; j < n2; ++j) {
+        if (s[j] == 0.0) continue;
+        for (int p = cp[j]; p < cp[j + 1]; ++p) K.r[ri[p]] -= v[p] * s[j];
+        K.c0 += q[j] * s[j];
+    }
+    K.colptr.assign(1, 0);
+    int col = 0, box = 0;
+    for (int j = 0; j < n2; ++j) {
+        K.off[j] = s[j];
+        if (kind[j] == FIXED) continue;
+        const double sg = kind[j] == NEG ? -1.0 : 1.0;
+        K.src[j] = col++;
+        K.sign[j] = sg;
+        for (int p = cp[j]; p < cp[j + 1]; ++p) { K.rowidx.push_back(ri[p]); K.val.push_back(sg * v[p]); }
+        if (kind[j] == BOX) {
+            K.rowidx.push_back(m2 + box); K.val.push_back(1.0);
+            K.r.push_back((yub ? yub[j] : INFINITY) - (ylb ? ylb[j] : 0.0));
+            K.sense.push_back('L');
+            K.box_col.push_back(j);
+            ++box;
+        }
+        K.q.push_back(sg * q[j]);
+        K.colptr.push_back((int)K.rowidx.size());
+    }
+    for (int j = 0; j < n2; ++j) {   // y- of the free columns
+        if (kind[j] != FREE) continue;
+        K.src2[j] = col++;
+        for (int p = cp[j]; p < cp[j + 1]; ++p) { K.rowidx.push_back(ri[p]); K.val.push_back(-v[p]); }
+        K.q.push_back(-q[j]);
+        K.colptr.push_back((int)K.rowidx.size());
+    }
+    return TWOSD_OK;
+}
+
+// W CSC of the caller (index base `base`) as 0-based ints, validated
+static int read_csc(int m2, int n2, const int64_t *Wcp, const int64_t *Wrv, const double *Wnz, int base, std::vector<int> &cp,
+                    std::vector<int> &ri, std::vector<double> &v) {
+    cp.resize(n2 + 1);
+    for (int j = 0; j <= n2; ++j) {
+        cp[j] = (int)(Wcp[j] - base);
+        if (j && cp[j] < cp[j - 1]) return fail(TWOSD_E_ARG, "W colptr malformed");
+    }
+    const int nnzW = cp[n2];
+    if (cp[0] != 0 || nnzW < 0) return fail(TWOSD_E_ARG, "W colptr malformed");
+    ri.resize(nnzW); v.resize(nnzW);
+    for (int p = 0; p < nnzW; ++p) {
+        ri[p] = (int)(Wrv[p] - base);
+        v[p] = Wnz[p];
+        if (ri[p] < 0 || ri[p] >= m2) return fail(TWOSD_E_ARG, "W row index %d out of range", ri[p] + base);
+    }
+    return TWOSD_OK;
+}
+
+extern "C" int twosd_canonical_form(int m2, int n2, const int64_t *Wcp, const int64_t *Wrv, const double *Wnz, const double *q,
+                                    const double *r, const char *sense, const double *ylb, const double *yub, int base,
+                                    int *m_lp, int *n_lp, int *n_bound_rows, int64_t *out_colptr, int64_t *out_rowval,
+                                    double *out_nzval, double *out_q, double *out_r, char *out_sense, double *c0,
+                                    int *col_src, double *col_sign, double *col_off, int *col_src2, int *box_col) {
+    if (m2 <= 0 || n2 <= 0 || !Wcp || !Wrv || !Wnz || !q || !r || !sense || !m_lp || !n_lp || !n_bound_rows)
+        return fail(TWOSD_E_ARG, "twosd_canonical_form: bad sizes or NULL arrays");
+    if (base != 0 && base != 1) return fail(TWOSD_E_ARG, "index_base must be 0 or 1");
+    std::vector<int> cp, ri;
+    std::vector<double> v;
+    int rc;
+    if ((rc = read_csc(m2, n2, Wcp, Wrv, Wnz, base, cp, ri, v))) return rc;
+    Canon K;
+    if ((rc = canonical_form_impl(m2, n2, cp.data(), ri.data(), v.data(), q, r, sense, ylb, yub, K))) return rc;
+    *m_lp = K.m_lp; *n_lp = K.n_lp; *n_bound_rows = K.nb;
+    if (out_colptr) for (int j = 0; j <= K.n_lp; ++j) out_colptr[j] = K.colptr[j] + base;
+    if (out_rowval) for (size_t p = 0; p < K.rowidx.size(); ++p) out_rowval[p] = K.rowidx[p] + base;
+    if (out_nzval) std::copy(K.val.begin(), K.val.end(), out_nzval);
+    if (out_q) std::copy(K.q.begin(), K.q.end(), out_q);
+    if (out_r) std::copy(K.r.begin(), K.r.end(), out_r);
+    if (out_sense) std::copy(K.sense.begin(), K.sense.end(), out_sense);
+    if (c0) *c0 = K.c0;
+    for (int j = 0; j < n2; ++j) {
+        if (col_src) col_src[j] = K.src[j] < 0 ? -1 : K.src[j] + base;
+        if (col_src2) col_src2[j] = K.src2[j] < 0 ? -1 : K.src2[j] + base;
+        if (col_sign) col_sign[j] = K.sign[j];
+        if (col_off) col_off[j] = K.off[j];
+    }
+    if (box_col) for (int b = 0; b < K.nb; ++b) box_col[b] = K.box_col[b] + base;
+    return TWOSD_OK;
+}
+
+extern "C" int twosd_lp_shape(twosd_ctx *c, int *m_lp, int *n_lp, int *n_bound_rows) {
+    if (!c || !c->has_template) return fail(TWOSD_E_STATE, "lp_shape: no template");
+    if (m_lp) *m_lp = c->L.m;
+    if (n_lp) *n_lp = c->L.n;
+    if (n_bound_rows) *n_bound_rows = c->nb;
+    return TWOSD_OK;
+}
+
 extern "C" int twosd_set_template(twosd_ctx *c, int m2, int n1, int n2, const int64_t *Tcp, const int64_t *Trv,
                                   const double *Tnz, const int64_t *Wcp, const int64_t *Wrv, const double *Wnz,
                                   const double *q, const double *r, const char *sense, const double *ylb,
@@ -343,45 +500,53 @@ extern "C" int twosd_set_template(twosd_ctx *c, int m2, int n1, int n2, const in
     free_template(c);
     HostLP &L = c->L;
     L = HostLP();
-    L.m = m2; L.n = n2;
-    L.colptr.resize(n2 + 1);
-    for (int j = 0; j <= n2; ++j) L.colptr[j] = (int)(Wcp[j] - base);
-    const int nnzW = L.colptr[n2];
-    if (L.colptr[0] != 0 || nnzW < 0) return fail(TWOSD_E_ARG, "W colptr malformed");
-    L.rowidx.resize(nnzW); L.val.resize(nnzW);
-    for (int p = 0; p < nnzW; ++p) {
-        L.rowidx[p] = (int)(Wrv[p] - base);
-        L.val[p] = Wnz[p];
-        if (L.rowidx[p] < 0 || L.rowidx[p] >= m2) return fail(TWOSD_E_ARG, "W row index %d out of range", L.rowidx[p] + base);
-    }
-    L.q.assign(q, q + n2);
-    L.sense.assign(sense, sense + m2);
+    int rc;
+    if ((rc = read_csc(m2, n2, Wcp, Wrv, Wnz, base, L.colptr, L.rowidx, L.val))) return rc;
     for (int i = 0; i < m2; ++i)
-        if (L.sense[i] != 'G' && L.sense[i] != 'L' && L.sense[i] != 'E')
-            return fail(TWOSD_E_ARG, "sense[%d] = '%c' (expected G/L/E)", i, L.sense[i]);
-    for (int j = 0; j < n2; ++j) {
-        const double lo = ylb ? ylb[j] : 0.0, hi = yub ? yub[j] : INFINITY;
-        if (lo != 0.0 || !std::isinf(hi) || hi < 0)
-            return fail(TWOSD_E_UNSUPPORTED, "y[%d] bounds [%g, %g]: only [0, +inf) is supported (subprob.jl:19-26 warns on these)", j, lo, hi);
+        if (sense[i] != 'G' && sense[i] != 'L' && sense[i] != 'E')
+            return fail(TWOSD_E_ARG, "sense[%d] = '%c' (expected G/L/E)", i, sense[i]);
+    // general bounds leave here: from this point m2 / n2 are the LP's sizes (the caller's when
+    // every bound is [0, +inf), and then L holds the caller's arrays untouched)
+    const int m2u = m2, n2u = n2;
+    Canon K;
+    if ((rc = canonical_form_impl(m2u, n2u, L.colptr.data(), L.rowidx.data(), L.val.data(), q, r, sense, ylb, yub, K))) return rc;
+    c->has_bounds = K.any;
+    c->m2_user = m2u; c->n2_user = n2u; c->nb = K.nb; c->c0 = K.c0;
+    c->r_user.assign(r, r + m2u);
+    if (K.any) {
+        L.colptr.swap(K.colptr); L.rowidx.swap(K.rowidx); L.val.swap(K.val);
+        m2 = K.m_lp; n2 = K.n_lp;
+        if (n2 <= 0) return fail(TWOSD_E_UNSUPPORTED, "every stage-2 variable is fixed: no LP is left");
     }
+    L.m = m2; L.n = n2;
+    L.q.swap(K.q);
+    L.sense.swap(K.sense);
+    const int nnzW = L.colptr[n2];
     c->n1 = n1;
-    c->r.assign(r, r + m2);
-    c->T.assign((size_t)m2 * n1, 0.0);   // dense T (m2 x n1) on the host for per-x setup
+    c->r.swap(K.r);
+    c->T.assign((size_t)m2 * n1, 0.0);   // dense T (LP rows x n1; the bound rows are zero) on the host for per-x setup
     for (int j = 0; j < n1; ++j)
         for (int64_t p = Tcp[j] - base; p < Tcp[j + 1] - base; ++p) {
             const int i = (int)(Trv[p] - base);
-            if (i < 0 || i >= m2) return fail(TWOSD_E_ARG, "T row index out of range");
+            if (i < 0 || i >= m2u) return fail(TWOSD_E_ARG, "T row index out of range");
             c->T[(size_t)i * n1 + j] = Tnz[p];
         }
+    // the envelope applies to the LP's sizes; the messages name the caller's too
+    char sizes[160];
+    snprintf(sizes, sizeof sizes, "m2 = %d, n2 = %d (LP: %d rows with %d bound rows of boxed variables, %d columns)", m2u, n2u, m2,
+             c->nb, n2);
     const int R = hyper_rows_per_lane(m2);
-    if (R < 0) return fail(TWOSD_E_UNSUPPORTED, "m2 = %d exceeds the LP kernel envelope (%d rows)", m2, 64 * 16);
+    if (R < 0) return fail(TWOSD_E_UNSUPPORTED, "%s: %d LP rows exceed the LP kernel envelope (%d rows)", sizes, m2, 64 * 16);
     const int C = (n2 + m2 + 63) / 64;
-    if (C > kMaxColsPerLane) return fail(TWOSD_E_UNSUPPORTED, "n2 + m2 = %d exceeds %d columns", n2 + m2, 64 * kMaxColsPerLane);
+    if (C > kMaxColsPerLane)
+        return fail(TWOSD_E_UNSUPPORTED, "%s: %d LP columns and rows exceed %d columns", sizes, n2 + m2, 64 * kMaxColsPerLane);
     c->R = R; c->MP = 64 * R; c->C = C;
     c->CH = hyper_cols_per_lane(n2 + m2);
-    if (c->CH <= 0) return fail(TWOSD_E_UNSUPPORTED, "n2 + m2 = %d exceeds the LP kernel's column slots", n2 + m2);
+    if (c->CH <= 0) return fail(TWOSD_E_UNSUPPORTED, "%s: %d LP columns and rows exceed the LP kernel's column slots", sizes, n2 + m2);
     // device template
-    int rc;
+    if (K.any && ((rc = upload(&c->d_bm_src, K.src)) || (rc = upload(&c->d_bm_src2, K.src2)) || (rc = upload(&c->d_bm_sign, K.sign)) ||
+                  (rc = upload(&c->d_bm_off, K.off))))
+        return rc;
     if ((rc = dalloc(&c->d_colptr, n2 + 1)) || (rc = dalloc(&c->d_rowidx, nnzW)) || (rc = dalloc(&c->d_val, nnzW)) ||
         (rc = dalloc(&c->d_q, n2)) || (rc = dalloc(&c->d_btype, n2 + m2)) || (rc = dalloc(&c->d_fixedmask, 64)) ||
         (rc = dalloc(&c->d_ubmask, 64)))
@@ -433,7 +598,7 @@ extern "C" int twosd_set_random_positions(twosd_ctx *c, int k, const int *row, c
     for (int e = 0; e < k; ++e) {
         const int rr = row[e] - base;
         const int cc = col[e] < 0 ? -1 : col[e] - base;
-        if (rr < 0 || rr >= c->L.m) return fail(TWOSD_E_ARG, "position %d: row %d out of range", e, row[e]);
+        if (rr < 0 || rr >= c->m2_user) return fail(TWOSD_E_ARG, "position %d: row %d out of range", e, row[e]);   // not a bound row
         if (cc >= c->n1) return fail(TWOSD_E_ARG, "position %d: column %d is not a first-stage column (KeyError in delta_coefficients, subprob.jl:116)", e, col[e]);
         c->pos_row[e] = rr; c->pos_col[e] = cc;
     }
@@ -445,10 +610,11 @@ extern "C" int twosd_set_random_positions(twosd_ctx *c, int k, const int *row, c
     return TWOSD_OK;
 }
 
-// template value at position e (RHS or T entry)
+// template value at position e (RHS or T entry), in the caller's space: the caller's r, not the
+// shifted r' of a template with general bounds (a delta is the same in both)
 static double template_value(const twosd_ctx *c, int e) {
     const int rr = c->pos_row[e], cc = c->pos_col[e];
-    return cc < 0 ? c->r[rr] : c->T[(size_t)rr * c->n1 + cc];
+    return cc < 0 ? c->r_user[rr] : c->T[(size_t)rr * c->n1 + cc];
 }
 
 // b = r - T x + effect of the element deltas dv (k)
@@ -2357,7 +2523,9 @@ int twosd::run_lp_ex(twosd_ctx *c, const double *x, const double *d_dv, int N, c
         const int ecap = (int)std::min<long long>(INT32_MAX / 2, (long long)std::max(4096, 32 * MP) * std::max(256, kmax) / 256);
         int bpc = hyper_max_blocks_per_cu(R, CH, kmax, c->k);
         if (const char *e = getenv("TWOSD_BPC")) bpc = std::min(bpc, std::max(1, atoi(e)));   // diagnostics: occupancy sweep
-        if (bpc < 1) return fail(TWOSD_E_UNSUPPORTED, "LP kernel: LDS slice too large (m = %d, k = %d)", m, c->k);
+        if (bpc < 1)
+            return fail(TWOSD_E_UNSUPPORTED, "LP kernel: LDS slice too large (m2 = %d, n2 = %d; LP: %d rows, %d columns; k = %d)",
+                        c->m2_user, c->n2_user, m, n, c->k);
         const int nblocks = std::max(1, std::min((NL + kWavesPerBlock - 1) / kWavesPerBlock, bpc * c->num_cus));
         const size_t slots = (size_t)nblocks * kWavesPerBlock;
         if (slots > c->earena_slots || ecap != c->earena_cap) {
@@ -2565,6 +2733,31 @@ __global__ void __launch_bounds__(256) lp_obj_kernel(int N, const double *__rest
     }
 }
 
+// Template with general bounds: the LP's outputs back into the caller's space.  yu[s][j] =
+// off[j] + sign[j] * y[s][src[j]] - y[s][src2[j]] (a term with index -1 is absent: fixed columns
+// have no LP column, only free ones a second), one thread per output entry, j fastest, so a wave
+// writes consecutive entries of a row and reads a (nearly) consecutive run of the LP's row; and
+// obj[s] += c0, the constant q.s the shift took out of the LP.  y / yu nullable (objectives only).
+__global__ void __launch_bounds__(256) bounds_backmap_kernel(int N, int n2, int n_lp, const int *__restrict__ src,
+                                                             const int *__restrict__ src2, const double *__restrict__ sign,
+                                                             const double *__restrict__ off, const double *__restrict__ y,
+                                                             double *__restrict__ yu, double c0, double *__restrict__ obj) {
+    const size_t t0 = (size_t)blockIdx.x * blockDim.x + threadIdx.x, step = (size_t)gridDim.x * blockDim.x;
+    for (size_t s = t0; s < (size_t)N; s += step) obj[s] += c0;
+    if (!y) return;
+    const size_t tot = (size_t)N * n2;
+    for (size_t i = t0; i < tot; i += step) {
+        const size_t s = i / n2;
+        const int j = (int)(i - s * n2);
+        const double *row = y + s * n_lp;
+        const int a = src[j], b = src2[j];
+        double v = off[j];
+        if (a >= 0) v = fma(sign[j], row[a], v);
+        if (b >= 0) v -= row[b];
+        yu[i] = v;
+    }
+}
+
 // d_w: the batch's scenario weights (nullable: 1.0), for the objective sum
 static int copy_lp_outputs(twosd_ctx *c, int N, double *obj, double *pi, double *y, int *status, const double *d_w) {
     if (!c->d_lpstats) {
@@ -2574,6 +2767,20 @@ static int copy_lp_outputs(twosd_ctx *c, int N, double *obj, double *pi, double 
     if (!c->d_objpart) {
         int rc = dalloc(&c->d_objpart, (size_t)2 * kObjBlocks);
         if (rc) return rc;
+    }
+    const double *d_yout = c->d_y;
+    if (c->has_bounds) {   // before the objective sum and the copies: they see the caller's values
+        if (y && (size_t)N > c->yu_cap) {
+            int rc = dalloc(&c->d_yu, (size_t)std::max(N, c->out_cap) * c->n2_user);
+            if (rc) { c->yu_cap = 0; return rc; }
+            c->yu_cap = (size_t)std::max(N, c->out_cap);
+        }
+        const size_t work = y ? (size_t)N * c->n2_user : (size_t)N;
+        hipLaunchKernelGGL(bounds_backmap_kernel, dim3((unsigned)std::min<size_t>(4096, (work + 255) / 256)), dim3(256), 0, c->stream, N,
+                           c->n2_user, c->L.n, c->d_bm_src, c->d_bm_src2, c->d_bm_sign, c->d_bm_off, y ? c->d_y : nullptr,
+                           y ? c->d_yu : nullptr, c->c0, c->d_obj);
+        HIPCHK(hipGetLastError());
+        d_yout = c->d_yu;
     }
     HIPCHK(hipMemsetAsync(c->d_lpstats, 0, 5 * sizeof(unsigned long long), c->stream));
     hipLaunchKernelGGL(lp_stats_kernel, dim3((unsigned)std::min(256, (N + 255) / 256)), dim3(256), 0, c->stream, N,
@@ -2588,7 +2795,7 @@ static int copy_lp_outputs(twosd_ctx *c, int N, double *obj, double *pi, double 
     HIPCHK(hipStreamSynchronize(c->stream));
     if (obj) HIPCHK(hipMemcpy(obj, c->d_obj, sizeof(double) * N, hipMemcpyDeviceToHost));
     if (pi) HIPCHK(hipMemcpy(pi, c->d_pi, sizeof(double) * N * c->L.m, hipMemcpyDeviceToHost));
-    if (y) HIPCHK(hipMemcpy(y, c->d_y, sizeof(double) * N * c->L.n, hipMemcpyDeviceToHost));
+    if (y) HIPCHK(hipMemcpy(y, d_yout, sizeof(double) * N * c->n2_user, hipMemcpyDeviceToHost));
     if (status) HIPCHK(hipMemcpy(status, c->d_status, sizeof(int) * N, hipMemcpyDeviceToHost));
     c->last_pivots_sum = (int64_t)stv[0]; c->last_ops_sum = (int64_t)stv[1]; c->last_pivots_max = (int)stv[2];
     c->last_eta_entries = (int64_t)stv[4];

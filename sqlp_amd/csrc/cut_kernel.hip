@@ -2050,7 +2050,9 @@ static int cut_finalize_impl(twosd_ctx *c, const double *x, const unsigned long 
         if (c->pos_col[e] < 0) a += sums[1 + e];
         else beta[c->pos_col[e]] -= sums[1 + e];
     }
-    *alpha = a;
+    // general bounds: the picks' weights sum to 1, so the shift's objective constant enters once
+    // (here, after any all-reduce of the partials)
+    *alpha = c->has_bounds ? a + c->c0 : a;
     return TWOSD_OK;
 }
 
@@ -2104,6 +2106,8 @@ extern "C" int twosd_build_cut(twosd_ctx *c, int epi, const double *x, double ti
     c->t_us[3] = 1e3 * ms2;
     if (weight_mark) *weight_mark = E.total_weight;
     if (max_val) HIPCHK(hipMemcpy(max_val, w->val, sizeof(double) * E.count, hipMemcpyDeviceToHost));
+    if (max_val && c->has_bounds)   // scores of the canonical LP: the caller's objective adds the shift's constant
+        for (int s = 0; s < E.count; ++s) max_val[s] += c->c0;
     if (max_arg) HIPCHK(hipMemcpy(max_arg, w->arg, sizeof(int) * E.count, hipMemcpyDeviceToHost));
     return TWOSD_OK;
 }
@@ -2172,6 +2176,8 @@ extern "C" int twosd_cut_partial(twosd_ctx *c, int epi, const double *x, double 
     c->t_us[2] = 1e3 * ms;
     CutWs *w = cws(c);
     if (max_val) HIPCHK(hipMemcpy(max_val, w->val, sizeof(double) * E.count, hipMemcpyDeviceToHost));
+    if (max_val && c->has_bounds)   // scores of the canonical LP: the caller's objective adds the shift's constant
+        for (int s = 0; s < E.count; ++s) max_val[s] += c->c0;
     if (max_arg) HIPCHK(hipMemcpy(max_arg, w->arg, sizeof(int) * E.count, hipMemcpyDeviceToHost));
     return TWOSD_OK;
 }

@@ -46,8 +46,19 @@ struct twosd_ctx {
     bool has_template = false, has_basis = false;
     twosd::HostLP L;              // W CSC, q, sense (host)
     int n1 = 0, R = 0, MP = 0, C = 0, k = 0;
-    std::vector<double> r, T;     // r (m2), dense T (m2 x n1, row-major)
+    std::vector<double> r, T;     // the LP's r (L.m), dense T (L.m x n1, row-major)
     std::vector<int> pos_row, pos_col;
+    // general stage-2 bounds (twosd_canonical_form): L / r / T above describe the canonical LP
+    // (y >= 0, L.m = m2 + nb rows, L.n columns); the caller's sizes, rhs and the back-map of y live
+    // here.  has_bounds == false: the template is the caller's own and none of this is read.
+    bool has_bounds = false;
+    int m2_user = 0, n2_user = 0, nb = 0;
+    double c0 = 0.0;              // objective constant q.s of the shift
+    std::vector<double> r_user;   // the caller's r (m2_user): scenario values are in its space
+    int *d_bm_src = nullptr, *d_bm_src2 = nullptr;   // n2_user: LP column(s) of each caller column
+    double *d_bm_sign = nullptr, *d_bm_off = nullptr;
+    double *d_yu = nullptr;       // y of the last batch in the caller's space (N x n2_user)
+    size_t yu_cap = 0;
     int *d_colptr = nullptr, *d_rowidx = nullptr;
     double *d_val = nullptr, *d_q = nullptr;
     int8_t *d_btype = nullptr;

@@ -198,7 +198,7 @@ def push_sharded(V, pis_local: np.ndarray) -> int:
     pis_local = np.ascontiguousarray(np.atleast_2d(pis_local), dtype=np.float64)
     if pis_local.shape[0]:
         V.push_batch(pis_local)
-    new_rows = V.matrix(n0) if len(V) > n0 else np.zeros((0, V.ctx.m))
+    new_rows = V.matrix(n0) if len(V) > n0 else np.zeros((0, V.ctx.mv))
     rank, G = world()
     if G == 1:
         return len(V)

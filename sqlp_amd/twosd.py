@@ -35,6 +35,64 @@ def _f64(a):
 
 
 @dataclass
+class CanonicalForm:
+    """twosd_canonical_form's output: the LP  min q'y' + c0, W y' (sense) r, y' >= 0  that the
+    kernels solve for a template with general bounds, and the map back to the caller's y."""
+    m_lp: int
+    n_lp: int
+    n_bound_rows: int
+    W: tuple             # CSC (colptr, rowval, nzval), m_lp x n_lp, 0-based int64
+    q: np.ndarray
+    r: np.ndarray        # [r - W s ; hi - lo]
+    sense: list
+    c0: float
+    col_src: np.ndarray  # y_j = col_off[j] + col_sign[j] * y'[col_src[j]] - y'[col_src2[j]]  (-1: no term)
+    col_sign: np.ndarray
+    col_off: np.ndarray
+    col_src2: np.ndarray
+    box_col: np.ndarray  # column of bound row m2 + b
+
+    def map_back(self, y_lp) -> np.ndarray:
+        """LP solution(s) (.. x n_lp) -> the caller's y (.. x n2)."""
+        y_lp = np.asarray(y_lp, dtype=np.float64)
+        ext = np.concatenate([y_lp, np.zeros(y_lp.shape[:-1] + (1,))], axis=-1)   # index -1 reads the zero
+        return self.col_off + self.col_sign * ext[..., self.col_src] - ext[..., self.col_src2]
+
+
+def canonical_form(W, q, r, sense, ylb=None, yub=None) -> CanonicalForm:
+    """twosd_canonical_form (host code of the library, no GPU): W is a CSC triple (colptr, rowval,
+    nzval), 0-based; ylb / yub default to 0 / +inf.  Raises TwoSDError(TWOSD_E_ARG) for bounds that
+    are no interval."""
+    lib = _lib.load()
+    cp, rv, nz = (np.ascontiguousarray(W[0], dtype=np.int64), np.ascontiguousarray(W[1], dtype=np.int64), _f64(W[2]))
+    q, r = _f64(q), _f64(r)
+    m2, n2, nnz = len(r), len(q), len(nz)
+    sb = np.frombuffer("".join(sense).encode(), dtype=np.int8).copy()
+    lo = None if ylb is None else _f64(ylb)
+    hi = None if yub is None else _f64(yub)
+    m_lp, n_lp, nb = C.c_int(), C.c_int(), C.c_int()
+    ocp = np.zeros(2 * n2 + 1, dtype=np.int64)
+    orv = np.zeros(2 * nnz + n2, dtype=np.int64)
+    onz = np.zeros(2 * nnz + n2)
+    oq = np.zeros(2 * n2)
+    orr = np.zeros(m2 + n2)
+    osn = np.zeros(m2 + n2, dtype=np.int8)
+    c0 = C.c_double()
+    src = np.zeros(n2, dtype=np.int32)
+    src2 = np.zeros(n2, dtype=np.int32)
+    sign = np.zeros(n2)
+    off = np.zeros(n2)
+    box = np.zeros(n2, dtype=np.int32)
+    check(lib.twosd_canonical_form(m2, n2, ptr(cp), ptr(rv), ptr(nz), ptr(q), ptr(r), ptr(sb), ptr(lo), ptr(hi), 0,
+                                   C.byref(m_lp), C.byref(n_lp), C.byref(nb), ptr(ocp), ptr(orv), ptr(onz), ptr(oq),
+                                   ptr(orr), ptr(osn), C.byref(c0), ptr(src), ptr(sign), ptr(off), ptr(src2), ptr(box)))
+    ml, nl = m_lp.value, n_lp.value
+    nnz_lp = int(ocp[nl])
+    return CanonicalForm(ml, nl, nb.value, (ocp[:nl + 1].copy(), orv[:nnz_lp].copy(), onz[:nnz_lp].copy()), oq[:nl].copy(),
+                         orr[:ml].copy(), [chr(v) for v in osn[:ml]], c0.value, src, sign, off, src2, box[:nb.value].copy())
+
+
+@dataclass
 class sdCut:
     """eta >= alpha + beta'x (epigraph.jl:5-12); never scaled."""
     alpha: float
@@ -69,6 +127,13 @@ class SDContext:
             ptr(self._keep[0]), ptr(self._keep[1]), ptr(self._keep[2]),
             ptr(self._keep[3]), ptr(self._keep[4]), ptr(self._keep[5]),
             ptr(_f64(sp2.q)), ptr(_f64(sp2.r)), ptr(sense), ptr(_f64(sp2.ylb)), ptr(_f64(sp2.yub)), ib))
+        # the LP the kernels solve (twosd_lp_shape): general bounds cost one row per boxed variable.
+        # mv = m_lp = m + n_bound_rows is the length of a dual vector (row duals, then the boxed
+        # variables' multipliers) and of a basis head; all equal m / n2 with default bounds.
+        ml, nl, nb = C.c_int(), C.c_int(), C.c_int()
+        check(self.lib.twosd_lp_shape(self.h, C.byref(ml), C.byref(nl), C.byref(nb)))
+        self.m_lp, self.n_lp, self.n_bound_rows = ml.value, nl.value, nb.value
+        self.mv = self.m_lp
         self.row_lookup = {n: i for i, n in enumerate(sp2.stage_constraints)}
         self.col_lookup = {n: j for j, n in enumerate(sp2.last_stage_vars)}
         if sto is not None and positions is None:
@@ -121,7 +186,7 @@ class SDContext:
         self.has_basis = True
 
     def get_basis(self):
-        head = np.zeros(self.m, dtype=np.int32)
+        head = np.zeros(self.m_lp, dtype=np.int32)
         check(self.lib.twosd_get_basis(self.h, ptr(head)))
         return head
 
@@ -289,7 +354,7 @@ class SDContext:
         return n.value
 
     def pool_get(self, p):
-        head = np.zeros(self.m, dtype=np.int32)
+        head = np.zeros(self.m_lp, dtype=np.int32)
         check(self.lib.twosd_pool_get(self.h, int(p), ptr(head)))
         return head
 
@@ -393,7 +458,7 @@ class SDContext:
         N = values.shape[0]
         obj = np.zeros(N)
         st = np.zeros(N, dtype=np.int32)
-        pi = np.zeros((N, self.m)) if want_pi else None
+        pi = np.zeros((N, self.mv)) if want_pi else None
         y = np.zeros((N, self.n2)) if want_y else None
         rc = self.lib.twosd_solve_values(self.h, ptr(_f64(x)), N, ptr(values), ptr(obj), ptr(pi), ptr(y), ptr(st))
         if rc != 0 and not (rc == -4 and not raise_on_status):
@@ -418,8 +483,8 @@ class sdDualVertexSet:
     def push_batch(self, pis) -> np.ndarray:
         """Sequential push! of every row; returns the vertex index of each row."""
         pis = _f64(np.atleast_2d(pis))
-        if pis.shape[1] != self.ctx.m:
-            raise ValueError(f"dual vector length {pis.shape[1]} != {self.ctx.m}")
+        if pis.shape[1] != self.ctx.mv:
+            raise ValueError(f"dual vector length {pis.shape[1]} != {self.ctx.mv}")
         out = np.zeros(pis.shape[0], dtype=np.int32)
         ns = C.c_int()
         check(self.ctx.lib.twosd_dvs_push(self.ctx.h, pis.shape[0], ptr(pis), ptr(out), C.byref(ns)))
@@ -433,7 +498,7 @@ class sdDualVertexSet:
     def matrix(self, first=0, count=None) -> np.ndarray:
         n = len(self)
         count = n - first if count is None else count
-        out = np.zeros((count, self.ctx.m))
+        out = np.zeros((count, self.ctx.mv))
         check(self.ctx.lib.twosd_dvs_get(self.ctx.h, first, count, ptr(out)))
         return out
 
@@ -522,7 +587,7 @@ def solve_batch(epi: sdEpigraph, x, first=0, count=None, want_pi=True, want_y=Fa
     count = epi.num_scenarios - first if count is None else count
     obj = np.zeros(count)
     st = np.zeros(count, dtype=np.int32)
-    pi = np.zeros((count, ctx.m)) if want_pi else None
+    pi = np.zeros((count, ctx.mv)) if want_pi else None
     y = np.zeros((count, ctx.n2)) if want_y else None
     check(ctx.lib.twosd_solve_batch(ctx.h, epi.index, ptr(_f64(x)), first, count, ptr(obj), ptr(pi), ptr(y), ptr(st)))
     return obj, y, pi, st
