@@ -266,6 +266,56 @@ int twosd_evaluate_sampled(twosd_ctx *ctx, const double *x, int64_t N_total, int
                            uint64_t seed, double *s2);
 
 /*
+ * Out-of-sample recourse cost with its error bar (no reference counterpart: evaluate,
+ * smps_routines.jl:67-82, returns the mean alone; ssn_test.jl:50-57 sets it against the cuts'
+ * lower bound).  Sample moments of the stage-2 objective over scenarios of a stream, reduced on
+ * the device in a fixed order (the same bits on every run) and mergeable: chunks, batches and
+ * ranks combine through twosd_moments_merge, so a shard layout fixes the bits.
+ * variance = m2 / (n - 1); standard error of the mean = sqrt(variance / n).
+ */
+typedef struct twosd_moments {
+    int64_t n;      /* scenarios counted: LP optimal                                    */
+    int64_t n_bad;  /* scenarios left out: LP not optimal                               */
+    double mean;    /* of obj over the n            (0 when n == 0)                     */
+    double m2;      /* sum (obj - mean)^2 over them (0 when n <= 1)                     */
+    double min, max;/* +inf / -inf when n == 0                                          */
+} twosd_moments;
+
+/* out = a merged with b (host code only: no context, no GPU call; out may alias a or b).  With
+ * n = na + nb and d = mean_b - mean_a: mean = mean_a + d (nb / n), m2 = m2_a + m2_b + d d (na nb / n);
+ * n_bad adds.  An operand with n == 0 gives the other operand's fields bit for bit (n_bad added). */
+int twosd_moments_merge(const twosd_moments *a, const twosd_moments *b, twosd_moments *out);
+
+/* Moments of the caller's own objectives obj[n]; status[n] nullable (every entry counts), else
+ * only entries with TWOSD_LP_OPTIMAL count and the others' values are never read into a sum
+ * (they may be NaN).  Uploads the arrays and runs the moments kernel; needs no template. */
+int twosd_moments_of_values(twosd_ctx *ctx, int64_t n, const double *obj, const int *status, twosd_moments *out);
+
+/* Moments of the stage-2 objective at x over scenarios [first, first+count) of stream `seed`
+ * (the scenarios of twosd_evaluate_sampled): per chunk of 2^20 scenarios sample, solve, reduce on
+ * the device -- no objective is copied to the host; chunks merge in ascending order.  A
+ * non-optimal LP does not abort: the scenario counts in n_bad, *out is filled and the return
+ * value is TWOSD_E_LP.  The caller adds c'x to the mean. */
+int twosd_evaluate_moments(twosd_ctx *ctx, const double *x, int64_t first, int64_t count, uint64_t seed,
+                           twosd_moments *out);
+
+/* Two first-stage points on common random numbers: the same scenarios solved at xa and at xb.  A
+ * scenario counts when its LP is optimal at both (a->n == b->n == diff->n); *diff holds the
+ * moments of obj(xa) - obj(xb) formed per scenario.  Outputs and return value as above. */
+int twosd_evaluate_paired(twosd_ctx *ctx, const double *xa, const double *xb, int64_t first, int64_t count,
+                          uint64_t seed, twosd_moments *a, twosd_moments *b, twosd_moments *diff);
+
+/* Sample until the confidence interval is tight: batch j is scenarios [first + j batch, ...) of
+ * the stream, merged in order.  After each batch with n >= 2: hw = z sqrt(m2 / (n - 1) / n);
+ * stops with *converged = 1 when hw <= max(abs_tol, rel_tol |offset + mean|), or with
+ * *converged = 0 once n + n_bad >= n_max (the last batch is clipped to n_max).  offset is the
+ * caller's c'x; z a normal quantile (1.96 for 95 %).  *half_width = +inf while n < 2.
+ * TWOSD_E_ARG for batch < 2, n_max < batch, z <= 0 or a negative tolerance. */
+int twosd_evaluate_ci(twosd_ctx *ctx, const double *x, uint64_t seed, int64_t first, int64_t batch, int64_t n_max,
+                      double z, double rel_tol, double abs_tol, double offset, twosd_moments *out,
+                      double *half_width, int *converged);
+
+/*
  * solve_problem! (smps_routines.jl:50-62) for scenarios [first, first+count) of epigraph
  * `epi` at first-stage x[n1].  obj[count], status[count] required; pi[count*m2] and
  * y[count*n2] nullable.  Returns TWOSD_E_LP if any status != OPTIMAL (outputs still set).

@@ -299,6 +299,41 @@ function evaluate(ctx::HipContext, s1_cost::Float64, x::Vector{Float64}, N::Int,
     return s1_cost + s2[]
 end
 
+# struct twosd_moments: sample moments of the stage-2 objective over the n scenarios whose LP was
+# optimal (n_bad: the others).  variance = m2 / (n - 1)
+struct Moments
+    n::Int64; n_bad::Int64
+    mean::Float64; m2::Float64; min::Float64; max::Float64
+end
+Moments() = Moments(0, 0, 0.0, 0.0, Inf, -Inf)
+lp_ok(rc; strict::Bool=true) = (rc == -4 && !strict) || check(rc)      # TWOSD_E_LP: see n_bad
+
+# Sample the stream `seed` in batches until z * standard error <= max(abs_tol, rel_tol |c'x + mean|)
+# or n_max scenarios (twosd_evaluate_ci; z: a normal quantile, e.g. quantile(Normal(), 0.975)).
+# Returns (mean incl. c'x, half width, moments of the stage-2 part, converged).  No reference
+# counterpart: evaluate (smps_routines.jl:67-82) returns the mean alone.
+function evaluate_ci(ctx::HipContext, s1_cost::Float64, x::Vector{Float64}, seed::UInt64; batch::Int=4096,
+                     n_max::Int=1 << 20, z::Float64=1.959963984540054, rel_tol::Float64=1e-3, abs_tol::Float64=0.0,
+                     first::Int=0, strict::Bool=true)
+    m = Ref(Moments()); hw = Ref(0.0); conv = Ref{Cint}(0)
+    lp_ok(ccall((:twosd_evaluate_ci, LIB), Cint,
+                (Ptr{Cvoid}, Ptr{Float64}, UInt64, Int64, Int64, Int64, Float64, Float64, Float64, Float64,
+                 Ref{Moments}, Ref{Float64}, Ref{Cint}),
+                ctx.h, x, seed, first, batch, n_max, z, rel_tol, abs_tol, s1_cost, m, hw, conv); strict=strict)
+    return (mean = s1_cost + m[].mean, half_width = hw[], moments = m[], converged = conv[] != 0)
+end
+
+# Two first-stage points on common random numbers (twosd_evaluate_paired): moments of the stage-2
+# objective at xa, at xb and of their per-scenario difference over scenarios [first, first+count)
+function evaluate_paired(ctx::HipContext, xa::Vector{Float64}, xb::Vector{Float64}, seed::UInt64, first::Int, count::Int;
+                         strict::Bool=true)
+    a = Ref(Moments()); b = Ref(Moments()); d = Ref(Moments())
+    lp_ok(ccall((:twosd_evaluate_paired, LIB), Cint,
+                (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Int64, Int64, UInt64, Ref{Moments}, Ref{Moments}, Ref{Moments}),
+                ctx.h, xa, xb, first, count, seed, a, b, d); strict=strict)
+    return a[], b[], d[]
+end
+
 # warm-start basis pool (fewer pivots, same optima): built once, refreshed at a new x
 pool_build!(ctx::HipContext, epi::HipEpigraph, x::Vector{Float64}, count::Integer, max_pool::Integer) =
     (n = Ref{Cint}(0); check(ccall((:twosd_pool_build, LIB), Cint,

@@ -52,6 +52,11 @@ SIGNATURES = [
     ("twosd_add_sampled_scenarios", I, [P, I, I, C.c_uint64, C.c_uint64, P]),
     ("twosd_get_scenarios", I, [P, I, I, I, P]),
     ("twosd_evaluate_sampled", I, [P, P, C.c_int64, C.c_int64, C.c_int64, C.c_uint64, P]),
+    ("twosd_moments_merge", I, [P, P, P]),
+    ("twosd_moments_of_values", I, [P, C.c_int64, P, P, P]),
+    ("twosd_evaluate_moments", I, [P, P, C.c_int64, C.c_int64, C.c_uint64, P]),
+    ("twosd_evaluate_paired", I, [P, P, P, C.c_int64, C.c_int64, C.c_uint64, P, P, P]),
+    ("twosd_evaluate_ci", I, [P, P, C.c_uint64, C.c_int64, C.c_int64, C.c_int64, D, D, D, D, P, P, P]),
     ("twosd_solve_batch", I, [P, I, P, I, I, P, P, P, P]),
     ("twosd_solve_values", I, [P, P, I, P, P, P, P, P]),
     ("twosd_dvs_push", I, [P, I, P, P, P]),
@@ -89,6 +94,13 @@ SIGNATURES = [
     ("twosd_pool_candidate_picks", I, [P, I, P, I, I, I, P, P]),
     ("twosd_pool_set_candidates", I, [P, I, I, I, P, P]),
 ]
+
+
+
+class Moments(C.Structure):
+    """struct twosd_moments (include/twosd_hip.h)."""
+    _fields_ = [("n", C.c_int64), ("n_bad", C.c_int64), ("mean", D), ("m2", D), ("min", D), ("max", D)]
+
 
 _lib = None
 

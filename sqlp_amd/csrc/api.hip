@@ -289,6 +289,8 @@ static void free_template(twosd_ctx *c) {
     dfree(c->d_xbase); dfree(c->d_queue); dfree(c->d_lpstats);
     dfree(c->d_obj); dfree(c->d_pi); dfree(c->d_pi_rep); dfree(c->d_y); dfree(c->d_status); dfree(c->d_iters); dfree(c->d_ops); dfree(c->d_etan);
     dfree(c->d_dvtmp);
+    if (c->d_mompart) { hipFree(c->d_mompart); c->d_mompart = nullptr; }
+    dfree(c->d_ev_obj); dfree(c->d_ev_st); c->ev_obj_cap = c->ev_st_cap = 0;
     dfree(c->d_bnnz); dfree(c->d_sel_cinf); dfree(c->d_sel_ptr); dfree(c->d_sel_code); c->sel_code_cap = 0; dfree(c->d_head_out); dfree(c->d_pool_pick); dfree(c->d_cpick); dfree(c->d_order); dfree(c->d_sort_tmp); dfree(c->d_qrec); c->qrec_cap = 0;
     dfree(c->d_cand); dfree(c->d_sel_key); dfree(c->d_sel_pkey); dfree(c->d_sel_ppick); c->sel_pcap = 0; c->key_cap = 0; c->pool_l1 = c->pool_ncand = 0; c->order_cap = 0; c->sort_tmp_bytes = 0; c->head_cap = 0; c->pick_cap = 0; c->pool.clear();
     dfree(c->d_dist_kind); dfree(c->d_dist_off); dfree(c->d_dist_val); dfree(c->d_dist_prob); dfree(c->d_dist_p0);
@@ -2733,6 +2735,98 @@ __global__ void __launch_bounds__(256) lp_obj_kernel(int N, const double *__rest
     }
 }
 
+// Sample moments of a batch's objectives (twosd_moments per block): block b owns the contiguous
+// range [b L, min(N, (b + 1) L)), L = ceil(N / kMomBlocks), so a block's record is the moments of
+// a slice of the stream and the host merges the records in block order (twosd_moments_merge).
+// An entry counts when its status is optimal (PAIRED: in both arrays); the value of any other
+// entry is never loaded.  Per block, over its counted entries:
+//   0. the first counted index (each thread stops at its first; tree min) gives the pivot K = v[first]
+//   1. n and S = sum (v - K): mean = K + S / n.  The pivot keeps the sum at the size of the
+//      spread, not of the values, and makes a constant slice exact (S = 0, mean = K, m2 = 0)
+//   2. sum (v - mean)^2, min, max -- the second read of the slice comes from L2
+// never the one-pass sum v^2 - n mean^2, which loses 2 log10(mean / sd) digits.  PAIRED adds the
+// records of b and of the per-scenario difference d = a - b (formed per entry, then reduced like
+// a value): part[3 blk + 0 / 1 / 2] = a, b, d.  Every reduction is the fixed LDS tree of
+// lp_obj_kernel over per-thread partials of a fixed stride: no atomics, the same bits on every run.
+constexpr int kMomBlocks = 256;
+template <typename T, typename Op>
+__device__ __forceinline__ T mom_block_reduce(T v, T *sh, Op op) {
+    __syncthreads();   // sh may still be read as the previous reduction's result
+    sh[threadIdx.x] = v;
+    __syncthreads();
+    for (int o = 128; o > 0; o >>= 1) {
+        if ((int)threadIdx.x < o) sh[threadIdx.x] = op(sh[threadIdx.x], sh[threadIdx.x + o]);
+        __syncthreads();
+    }
+    return sh[0];
+}
+template <bool PAIRED>
+__global__ void __launch_bounds__(256) eval_moments_kernel(long long N, const double *__restrict__ va,
+                                                           const int *__restrict__ sa, const double *__restrict__ vb,
+                                                           const int *__restrict__ sb, twosd_moments *__restrict__ part) {
+    constexpr int R = PAIRED ? 3 : 1;
+    __shared__ double shd[256];
+    __shared__ long long shi[256];
+    const long long L = (N + kMomBlocks - 1) / kMomBlocks;
+    const long long lo0 = (long long)blockIdx.x * L, lo = lo0 < N ? lo0 : N, hi = lo + L < N ? lo + L : N;
+    const auto counted = [&](long long i) {
+        return (!sa || sa[i] == TWOSD_LP_OPTIMAL) && (!PAIRED || !sb || sb[i] == TWOSD_LP_OPTIMAL);
+    };
+    const auto add = [](auto x, auto y) { return x + y; };
+    const long long none = 0x7fffffffffffffffLL;
+    long long first = none;
+    for (long long i = lo + threadIdx.x; i < hi; i += 256)
+        if (counted(i)) { first = i; break; }
+    first = mom_block_reduce(first, shi, [](long long x, long long y) { return x < y ? x : y; });
+    twosd_moments *out = part + (size_t)R * blockIdx.x;
+    if (first == none) {   // an empty slice, or nothing counted: the merge's identity
+        if (threadIdx.x == 0)
+            for (int r = 0; r < R; ++r) out[r] = twosd_moments{0, hi - lo, 0.0, 0.0, HUGE_VAL, -HUGE_VAL};
+        return;
+    }
+    double K[R], S[R], mean[R], q[R], mn[R], mx[R];
+    K[0] = va[first];
+    if (PAIRED) { K[1] = vb[first]; K[2] = K[0] - K[1]; }
+    long long n = 0;
+    for (int r = 0; r < R; ++r) S[r] = 0.0;
+    for (long long i = lo + threadIdx.x; i < hi; i += 256) {
+        if (!counted(i)) continue;
+        ++n;
+        const double a = va[i];
+        S[0] += a - K[0];
+        if (PAIRED) {
+            const double b = vb[i];
+            S[1] += b - K[1];
+            S[2] += (a - b) - K[2];
+        }
+    }
+    n = mom_block_reduce(n, shi, add);
+    for (int r = 0; r < R; ++r) {
+        S[r] = mom_block_reduce(S[r], shd, add);
+        mean[r] = K[r] + S[r] / (double)n;
+        q[r] = 0.0; mn[r] = HUGE_VAL; mx[r] = -HUGE_VAL;
+    }
+    for (long long i = lo + threadIdx.x; i < hi; i += 256) {
+        if (!counted(i)) continue;
+        double v[R];
+        v[0] = va[i];
+        if (PAIRED) { v[1] = vb[i]; v[2] = v[0] - v[1]; }
+        for (int r = 0; r < R; ++r) {
+            const double e = v[r] - mean[r];
+            q[r] = fma(e, e, q[r]);
+            mn[r] = v[r] < mn[r] ? v[r] : mn[r];
+            mx[r] = v[r] > mx[r] ? v[r] : mx[r];
+        }
+    }
+    for (int r = 0; r < R; ++r) {
+        q[r] = mom_block_reduce(q[r], shd, add);
+        mn[r] = mom_block_reduce(mn[r], shd, [](double x, double y) { return x < y ? x : y; });
+        mx[r] = mom_block_reduce(mx[r], shd, [](double x, double y) { return x > y ? x : y; });
+    }
+    if (threadIdx.x == 0)
+        for (int r = 0; r < R; ++r) out[r] = twosd_moments{n, (hi - lo) - n, mean[r], n > 1 ? q[r] : 0.0, mn[r], mx[r]};
+}
+
 // Template with general bounds: the LP's outputs back into the caller's space.  yu[s][j] =
 // off[j] + sign[j] * y[s][src[j]] - y[s][src2[j]] (a term with index -1 is absent: fixed columns
 // have no LP column, only free ones a second), one thread per output entry, j fastest, so a wave
@@ -2822,6 +2916,192 @@ extern "C" int twosd_last_objective(twosd_ctx *c, double *weighted_sum, double *
     if (weighted_sum) *weighted_sum = c->last_obj_wsum;
     if (weight_sum) *weight_sum = c->last_obj_w;
     return TWOSD_OK;
+}
+
+// ---- out-of-sample moments (twosd_moments_*, twosd_evaluate_moments / _paired / _ci) --------------
+static const twosd_moments kMomentsEmpty = {0, 0, 0.0, 0.0, HUGE_VAL, -HUGE_VAL};
+
+// The pairwise update of Chan, Golub and LeVeque: the one merge of the blocks' records, of the
+// chunks, of the batches and of the ranks.
+extern "C" int twosd_moments_merge(const twosd_moments *a, const twosd_moments *b, twosd_moments *out) {
+    if (!a || !b || !out) return fail(TWOSD_E_ARG, "moments_merge: NULL");
+    const twosd_moments A = *a, B = *b;   // out may alias either
+    if (A.n < 0 || B.n < 0) return fail(TWOSD_E_ARG, "moments_merge: negative count");
+    twosd_moments r;
+    if (B.n == 0) r = A;
+    else if (A.n == 0) r = B;
+    else {
+        const double na = (double)A.n, nb = (double)B.n, n = (double)(A.n + B.n);
+        const double d = B.mean - A.mean;
+        r.n = A.n + B.n;
+        r.mean = A.mean + d * (nb / n);
+        r.m2 = A.m2 + B.m2 + d * d * (na * nb / n);
+        r.min = B.min < A.min ? B.min : A.min;
+        r.max = B.max > A.max ? B.max : A.max;
+    }
+    r.n_bad = A.n_bad + B.n_bad;
+    *out = r;
+    return TWOSD_OK;
+}
+
+// moments of N device-resident values (PAIRED: also of vb and of va - vb) into out[0 .. R): the
+// kernel's kMomBlocks records, one small copy, one stream sync, merged in block order
+static int device_moments(twosd_ctx *c, long long N, const double *d_va, const int *d_sa, const double *d_vb,
+                          const int *d_sb, twosd_moments *out) {
+    const int R = d_vb ? 3 : 1;
+    for (int r = 0; r < R; ++r) out[r] = kMomentsEmpty;
+    if (N <= 0) return TWOSD_OK;
+    if (!c->d_mompart) HIPCHK(hipMalloc(&c->d_mompart, sizeof(twosd_moments) * 3 * kMomBlocks));
+    twosd_moments *d_part = (twosd_moments *)c->d_mompart;
+    if (d_vb)
+        hipLaunchKernelGGL(eval_moments_kernel<true>, dim3(kMomBlocks), dim3(256), 0, c->stream, N, d_va, d_sa, d_vb, d_sb, d_part);
+    else
+        hipLaunchKernelGGL(eval_moments_kernel<false>, dim3(kMomBlocks), dim3(256), 0, c->stream, N, d_va, d_sa, d_vb, d_sb, d_part);
+    HIPCHK(hipGetLastError());
+    std::vector<twosd_moments> part((size_t)R * kMomBlocks);
+    HIPCHK(hipMemcpyAsync(part.data(), d_part, sizeof(twosd_moments) * part.size(), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    for (int b = 0; b < kMomBlocks; ++b)
+        for (int r = 0; r < R; ++r) twosd_moments_merge(&out[r], &part[(size_t)R * b + r], &out[r]);
+    return TWOSD_OK;
+}
+
+extern "C" int twosd_moments_of_values(twosd_ctx *c, int64_t n, const double *obj, const int *status, twosd_moments *out) {
+    if (!c) return fail(TWOSD_E_STATE, "moments_of_values: no context");
+    if (!out || n < 0 || (n > 0 && !obj)) return fail(TWOSD_E_ARG, "moments_of_values: bad arguments");
+    HIPCHK(hipSetDevice(c->device));
+    int rc;
+    if (n > 0) {
+        if ((rc = dgrow(&c->d_ev_obj, &c->ev_obj_cap, (size_t)n, 0, c->stream))) return rc;
+        HIPCHK(hipMemcpy(c->d_ev_obj, obj, sizeof(double) * n, hipMemcpyHostToDevice));
+        if (status) {
+            if ((rc = dgrow(&c->d_ev_st, &c->ev_st_cap, (size_t)n, 0, c->stream))) return rc;
+            HIPCHK(hipMemcpy(c->d_ev_st, status, sizeof(int) * n, hipMemcpyHostToDevice));
+        }
+    }
+    return device_moments(c, n, c->d_ev_obj, status ? c->d_ev_st : nullptr, nullptr, nullptr, out);
+}
+
+static int64_t eval_chunk_size() {
+    int64_t chunk = 1 << 20;
+    if (const char *e = getenv("TWOSD_EVAL_CHUNK")) chunk = std::min<int64_t>(std::max<int64_t>(atoll(e), 1), 1 << 24);   // test hook
+    return chunk;
+}
+
+// scenarios [at, at + n) of stream `seed` drawn into d_dvtmp and solved at x; copy_lp_outputs adds
+// the bounds' constant to d_obj and keeps the last-LP statistics current (nothing is copied out).
+// TWOSD_OK, or TWOSD_E_LP with d_obj / d_status still set, or a failure.
+static int eval_solve_chunk(twosd_ctx *c, const double *x, int64_t at, int n, uint64_t seed) {
+    const int k = c->k;
+    int rc;
+    if ((rc = dgrow(&c->d_dvtmp, &c->dvtmp_cap, (size_t)n * std::max(k, 1), 0, c->stream))) return rc;
+    SampleParams S{};
+    S.N = n; S.k = k; S.seed = seed; S.first_index = (unsigned long long)at;
+    S.kind = c->d_dist_kind; S.off = c->d_dist_off; S.val = c->d_dist_val; S.prob = c->d_dist_prob;
+    S.p0 = c->d_dist_p0; S.p1 = c->d_dist_p1; S.tmpl = c->d_dist_tmpl; S.out = c->d_dvtmp;
+    HIPCHK(launch_sample(S, c->stream));
+    if ((rc = run_lp(c, x, c->d_dvtmp, n, false, false))) return rc;
+    return copy_lp_outputs(c, n, nullptr, nullptr, nullptr, nullptr, nullptr);
+}
+
+static int eval_check_state(twosd_ctx *c, const char *who) {
+    if (!c || !c->has_template) return fail(TWOSD_E_STATE, "%s: no template", who);
+    if (!c->has_basis) return fail(TWOSD_E_STATE, "%s: no warm-start basis", who);
+    if (!c->has_dist) return fail(TWOSD_E_STATE, "%s: no distributions (twosd_set_distributions)", who);
+    return TWOSD_OK;
+}
+
+// moments over [first, first + count) at xa (xb: the paired form, out[0 .. 3) = a, b, a - b);
+// *lp_bad: some LP was not optimal (counted in n_bad; not a failure here)
+static int eval_moments_range(twosd_ctx *c, const double *xa, const double *xb, int64_t first, int64_t count, uint64_t seed,
+                              twosd_moments *out, bool *lp_bad) {
+    const int R = xb ? 3 : 1;
+    const int64_t chunk = eval_chunk_size();
+    for (int r = 0; r < R; ++r) out[r] = kMomentsEmpty;
+    for (int64_t at = 0; at < count; at += chunk) {
+        const int n = (int)std::min(chunk, count - at);
+        int rc = eval_solve_chunk(c, xa, first + at, n, seed);
+        if (rc == TWOSD_E_LP) *lp_bad = true;
+        else if (rc) return rc;
+        twosd_moments m[3];
+        if (xb) {
+            if ((rc = dgrow(&c->d_ev_obj, &c->ev_obj_cap, (size_t)n, 0, c->stream)) ||
+                (rc = dgrow(&c->d_ev_st, &c->ev_st_cap, (size_t)n, 0, c->stream)))
+                return rc;
+            HIPCHK(hipMemcpyAsync(c->d_ev_obj, c->d_obj, sizeof(double) * n, hipMemcpyDeviceToDevice, c->stream));
+            HIPCHK(hipMemcpyAsync(c->d_ev_st, c->d_status, sizeof(int) * n, hipMemcpyDeviceToDevice, c->stream));
+            HIPCHK(hipStreamSynchronize(c->stream));   // the next solve may reallocate d_obj / d_status
+            rc = eval_solve_chunk(c, xb, first + at, n, seed);
+            if (rc == TWOSD_E_LP) *lp_bad = true;
+            else if (rc) return rc;
+            if ((rc = device_moments(c, n, c->d_ev_obj, c->d_ev_st, c->d_obj, c->d_status, m))) return rc;
+        } else if ((rc = device_moments(c, n, c->d_obj, c->d_status, nullptr, nullptr, m)))
+            return rc;
+        for (int r = 0; r < R; ++r) twosd_moments_merge(&out[r], &m[r], &out[r]);
+    }
+    return TWOSD_OK;
+}
+
+static int eval_lp_result(bool lp_bad, const twosd_moments &m, const char *who) {
+    if (!lp_bad) return TWOSD_OK;
+    return fail(TWOSD_E_LP, "%s: %lld of %lld scenario LPs not optimal (left out of the moments, see n_bad)", who,
+                (long long)m.n_bad, (long long)(m.n + m.n_bad));
+}
+
+extern "C" int twosd_evaluate_moments(twosd_ctx *c, const double *x, int64_t first, int64_t count, uint64_t seed,
+                                      twosd_moments *out) {
+    int rc = eval_check_state(c, "evaluate_moments");
+    if (rc) return rc;
+    if (!out || first < 0 || count < 0 || (c->n1 > 0 && !x)) return fail(TWOSD_E_ARG, "evaluate_moments: bad arguments");
+    HIPCHK(hipSetDevice(c->device));
+    bool lp_bad = false;
+    if ((rc = eval_moments_range(c, x, nullptr, first, count, seed, out, &lp_bad))) return rc;
+    return eval_lp_result(lp_bad, *out, "evaluate_moments");
+}
+
+extern "C" int twosd_evaluate_paired(twosd_ctx *c, const double *xa, const double *xb, int64_t first, int64_t count,
+                                     uint64_t seed, twosd_moments *a, twosd_moments *b, twosd_moments *diff) {
+    int rc = eval_check_state(c, "evaluate_paired");
+    if (rc) return rc;
+    if (!a || !b || !diff || first < 0 || count < 0 || !xa || !xb) return fail(TWOSD_E_ARG, "evaluate_paired: bad arguments");
+    HIPCHK(hipSetDevice(c->device));
+    bool lp_bad = false;
+    twosd_moments m[3];
+    if ((rc = eval_moments_range(c, xa, xb, first, count, seed, m, &lp_bad))) return rc;
+    *a = m[0]; *b = m[1]; *diff = m[2];
+    return eval_lp_result(lp_bad, m[0], "evaluate_paired");
+}
+
+extern "C" int twosd_evaluate_ci(twosd_ctx *c, const double *x, uint64_t seed, int64_t first, int64_t batch, int64_t n_max,
+                                 double z, double rel_tol, double abs_tol, double offset, twosd_moments *out,
+                                 double *half_width, int *converged) {
+    if (!out || !half_width || !converged || first < 0) return fail(TWOSD_E_ARG, "evaluate_ci: bad arguments");
+    if (batch < 2 || n_max < batch) return fail(TWOSD_E_ARG, "evaluate_ci: need 2 <= batch <= n_max (batch %lld, n_max %lld)", (long long)batch, (long long)n_max);
+    if (!(z > 0.0) || !(rel_tol >= 0.0) || !(abs_tol >= 0.0) || !std::isfinite(offset))
+        return fail(TWOSD_E_ARG, "evaluate_ci: need z > 0, tolerances >= 0 and a finite offset");
+    int rc = eval_check_state(c, "evaluate_ci");
+    if (rc) return rc;
+    if (c->n1 > 0 && !x) return fail(TWOSD_E_ARG, "evaluate_ci: x required");
+    HIPCHK(hipSetDevice(c->device));
+    twosd_moments acc = kMomentsEmpty;
+    bool lp_bad = false;
+    double hw = HUGE_VAL;
+    int conv = 0;
+    for (int64_t done = 0; done < n_max && !conv; ) {
+        const int64_t cnt = std::min(batch, n_max - done);
+        twosd_moments m;
+        if ((rc = eval_moments_range(c, x, nullptr, first + done, cnt, seed, &m, &lp_bad))) return rc;
+        twosd_moments_merge(&acc, &m, &acc);
+        done += cnt;
+        if (acc.n >= 2) {
+            hw = z * std::sqrt(acc.m2 / (double)(acc.n - 1) / (double)acc.n);
+            conv = hw <= std::max(abs_tol, rel_tol * std::fabs(offset + acc.mean));
+        }
+    }
+    *out = acc;
+    *half_width = hw;
+    *converged = conv;
+    return eval_lp_result(lp_bad, acc, "evaluate_ci");
 }
 
 extern "C" int twosd_training_cap(twosd_ctx *c, int64_t pivots_sum, int64_t scenarios, int *cap) {

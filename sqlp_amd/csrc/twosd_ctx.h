@@ -153,6 +153,12 @@ struct twosd_ctx {
     // weighted objective sum of the last batch (sum_s w_s obj_s, fixed-order reduction) and its weight
     double last_obj_wsum = 0.0, last_obj_w = 0.0;
     double *d_objpart = nullptr;
+    // out-of-sample moments (eval_moments_kernel): the blocks' partial records, and a grow-only
+    // copy of objectives / statuses (the solve at xa of a paired chunk; moments_of_values' upload)
+    void *d_mompart = nullptr;
+    double *d_ev_obj = nullptr;
+    int *d_ev_st = nullptr;
+    size_t ev_obj_cap = 0, ev_st_cap = 0;
     // scenario distributions (on-device sampler)
     bool has_dist = false;
     int *d_dist_kind = nullptr, *d_dist_off = nullptr;

@@ -87,6 +87,57 @@ def evaluate_sharded(ctx, first_stage_cost, x, N, seed):
     return float(np.dot(first_stage_cost, x)) + sum_in_rank_order(s2)
 
 
+def merge_moments_in_rank_order(m):
+    """All-gather every rank's Moments (six fp64: the counts are exact below 2^53) and merge them
+    in rank order through twosd_moments_merge: identical on every rank, independent of the
+    reduction tree.  Single rank: m itself."""
+    from .twosd import Moments
+    if not (dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1):
+        return m
+    t = torch.tensor([float(m.n), float(m.n_bad), m.mean, m.m2, m.min, m.max], dtype=torch.float64)
+    if dist.get_backend() == "nccl":
+        t = t.cuda()
+    parts = [torch.zeros_like(t) for _ in range(dist.get_world_size())]
+    dist.all_gather(parts, t)
+    acc = None
+    for p in parts:
+        v = p.cpu().tolist()
+        q = Moments(int(v[0]), int(v[1]), v[2], v[3], v[4], v[5])
+        acc = q if acc is None else acc.merge(q)
+    return acc
+
+
+def evaluate_ci_sharded(ctx, first_stage_cost, x, seed, batch=4096, n_max=1 << 20, confidence=0.95, rel_tol=1e-3,
+                        abs_tol=0.0, first=0, z=None):
+    """twosd.evaluate_ci with every batch split over the ranks (shard_range): each rank evaluates
+    its slice of the batch, the slices merge in rank order and the batches in stream order, so
+    every rank holds the same moments and takes the same stop decision (the rule of
+    twosd_evaluate_ci).  A non-optimal LP counts in n_bad."""
+    from . import twosd
+    rank, G = world()
+    if batch < 2 or n_max < batch:
+        raise ValueError("evaluate_ci_sharded: need 2 <= batch <= n_max")
+    if rel_tol < 0 or abs_tol < 0:
+        raise ValueError("evaluate_ci_sharded: negative tolerance")
+    z = twosd.normal_quantile(confidence) if z is None else float(z)
+    if not z > 0:
+        raise ValueError("evaluate_ci_sharded: z <= 0")
+    offset = float(np.dot(first_stage_cost, x))
+    zero = np.zeros(len(x))
+    acc = twosd.Moments()
+    done, hw, conv = 0, float("inf"), False
+    while done < n_max and not conv:
+        cnt = min(batch, n_max - done)
+        lo, hi = shard_range(cnt, rank, G)
+        mine = twosd.evaluate_moments(ctx, zero, x, seed, first + done + lo, hi - lo, raise_on_status=False)
+        acc = acc.merge(merge_moments_in_rank_order(mine))
+        done += cnt
+        if acc.n >= 2:
+            hw = z * acc.std_error
+            conv = hw <= max(abs_tol, rel_tol * abs(offset + acc.mean))
+    return twosd.EvaluateCI(offset + acc.mean, hw, acc.n, acc.n_bad, bool(conv), acc)
+
+
 class CutExchange:
     """Device buffers of the per-cut exchange of one context, allocated once and regrown only
     when the vertex set grows (no per-cut allocation)."""

@@ -6,6 +6,7 @@ Reference (module TwoSD, yhz0/SQLP) -> here:
   add_scenario!(epi, w, weight)   epigraph.jl:81-96       -> add_scenario / add_scenarios
   solve_problem!(sp, x, w)        smps_routines.jl:50-62  -> solve_problem / solve_batch
   evaluate(sp1, sp2, sto, x; N)   smps_routines.jl:67-82  -> evaluate
+  (none: evaluate returns the mean alone)                  -> evaluate_moments / evaluate_paired / evaluate_ci
   argmax_procedure(...)           subprob.jl:141-169      -> argmax_procedure
   build_sasa_cut(epi, x, V)       epigraph.jl:125-146     -> build_sasa_cut -> sdCut
   sd_iteration! (hot segment)     algorithm.jl:45-55,79-85 -> sd_iteration_hot_path
@@ -621,6 +622,129 @@ def evaluate_sampled(ctx: SDContext, first_stage_cost, x, N, seed, first=0, coun
     check(ctx.lib.twosd_evaluate_sampled(ctx.h, ptr(_f64(x)), C.c_int64(N), C.c_int64(first), C.c_int64(count),
                                          C.c_uint64(seed), C.byref(s2)))
     return float(np.dot(first_stage_cost, x)) + s2.value
+
+
+@dataclass(frozen=True)
+class Moments:
+    """struct twosd_moments: sample moments of the stage-2 objective over the n scenarios whose LP
+    was optimal (n_bad: the others), reduced on the device in a fixed order and mergeable."""
+    n: int = 0
+    n_bad: int = 0
+    mean: float = 0.0
+    m2: float = 0.0
+    min: float = float("inf")
+    max: float = float("-inf")
+
+    @property
+    def variance(self) -> float:
+        """Sample variance (ddof = 1); nan for n < 2."""
+        return self.m2 / (self.n - 1) if self.n >= 2 else float("nan")
+
+    @property
+    def std_error(self) -> float:
+        """Standard error of the mean."""
+        return float(np.sqrt(self.m2 / (self.n - 1) / self.n)) if self.n >= 2 else float("nan")
+
+    def half_width(self, z: float = 1.959963984540054) -> float:
+        """Half-width of the normal confidence interval of the mean (z: a normal quantile)."""
+        return z * self.std_error
+
+    def merge(self, other: "Moments") -> "Moments":
+        """twosd_moments_merge(self, other): the moments of both samples together."""
+        a, b, out = self._c(), other._c(), _lib.Moments()
+        check(_lib.load().twosd_moments_merge(C.byref(a), C.byref(b), C.byref(out)))
+        return Moments._of(out)
+
+    def _c(self):
+        return _lib.Moments(int(self.n), int(self.n_bad), float(self.mean), float(self.m2), float(self.min), float(self.max))
+
+    @classmethod
+    def _of(cls, m) -> "Moments":
+        return cls(int(m.n), int(m.n_bad), float(m.mean), float(m.m2), float(m.min), float(m.max))
+
+
+def _lp_status_ok(rc, raise_on_status):
+    """check(rc), except that TWOSD_E_LP passes when the caller asked to see n_bad instead."""
+    if rc != 0 and not (rc == -4 and not raise_on_status):
+        check(rc)
+
+
+def moments_of_values(ctx: SDContext, obj, status=None) -> Moments:
+    """Moments of the caller's own objectives on the device (twosd_moments_of_values): entries
+    whose status is not optimal are left out (n_bad) and never read into a sum."""
+    obj = _f64(np.ravel(obj))
+    st = None if status is None else np.ascontiguousarray(np.ravel(status), dtype=np.int32)
+    if st is not None and st.shape != obj.shape:
+        raise ValueError("status and obj differ in length")
+    out = _lib.Moments()
+    check(ctx.lib.twosd_moments_of_values(ctx.h, C.c_int64(obj.size), ptr(obj), ptr(st), C.byref(out)))
+    return Moments._of(out)
+
+
+def evaluate_moments(ctx: SDContext, first_stage_cost, x, seed, first, count, raise_on_status=True) -> Moments:
+    """Moments of c'x + obj_w over scenarios [first, first+count) of the device-drawn stream `seed`
+    (twosd_evaluate_moments: no objective leaves the device).  mean, min and max include c'x.
+    raise_on_status=False returns the moments of the optimal scenarios when some LP is not
+    optimal (their number is n_bad) instead of raising."""
+    out = _lib.Moments()
+    rc = ctx.lib.twosd_evaluate_moments(ctx.h, ptr(_f64(x)), C.c_int64(first), C.c_int64(count), C.c_uint64(seed),
+                                        C.byref(out))
+    _lp_status_ok(rc, raise_on_status)
+    return _shift(Moments._of(out), float(np.dot(first_stage_cost, x)))
+
+
+def _shift(m: Moments, c: float) -> Moments:
+    if m.n == 0 or c == 0.0:
+        return m
+    return Moments(m.n, m.n_bad, m.mean + c, m.m2, m.min + c, m.max + c)
+
+
+def evaluate_paired(ctx: SDContext, first_stage_cost, xa, xb, seed, first, count, raise_on_status=True):
+    """Two first-stage points on common random numbers (twosd_evaluate_paired): the same
+    scenarios solved at xa and at xb -> (a, b, diff), diff the moments of the per-scenario
+    difference of c'x + obj.  diff.half_width() is the error bar of "xa is better than xb"."""
+    a, b, d = _lib.Moments(), _lib.Moments(), _lib.Moments()
+    rc = ctx.lib.twosd_evaluate_paired(ctx.h, ptr(_f64(xa)), ptr(_f64(xb)), C.c_int64(first), C.c_int64(count),
+                                       C.c_uint64(seed), C.byref(a), C.byref(b), C.byref(d))
+    _lp_status_ok(rc, raise_on_status)
+    ca, cb = float(np.dot(first_stage_cost, xa)), float(np.dot(first_stage_cost, xb))
+    return _shift(Moments._of(a), ca), _shift(Moments._of(b), cb), _shift(Moments._of(d), ca - cb)
+
+
+@dataclass(frozen=True)
+class EvaluateCI:
+    """Result of evaluate_ci: mean (c'x included) +- half_width over n scenarios."""
+    mean: float
+    half_width: float
+    n: int
+    n_bad: int
+    converged: bool
+    moments: Moments    # stage-2 part alone (without c'x)
+
+
+def normal_quantile(confidence: float) -> float:
+    """z of a two-sided normal interval (the library holds no inverse CDF)."""
+    if not 0.0 < confidence < 1.0:
+        raise ValueError("confidence must lie in (0, 1)")
+    from statistics import NormalDist
+    return NormalDist().inv_cdf(0.5 + 0.5 * confidence)
+
+
+def evaluate_ci(ctx: SDContext, first_stage_cost, x, seed, batch=4096, n_max=1 << 20, confidence=0.95, rel_tol=1e-3,
+                abs_tol=0.0, first=0, raise_on_status=True, z=None) -> EvaluateCI:
+    """Sample the stream `seed` in batches until the confidence interval of c'x + E[obj] is tight
+    (twosd_evaluate_ci): half-width <= max(abs_tol, rel_tol |mean|), or n_max scenarios.  z (a
+    quantile of the caller's own, e.g. Student's t) overrides `confidence`."""
+    out = _lib.Moments()
+    hw = C.c_double()
+    conv = C.c_int()
+    offset = float(np.dot(first_stage_cost, x))
+    rc = ctx.lib.twosd_evaluate_ci(ctx.h, ptr(_f64(x)), C.c_uint64(seed), C.c_int64(first), C.c_int64(batch),
+                                   C.c_int64(n_max), normal_quantile(confidence) if z is None else float(z), float(rel_tol), float(abs_tol), offset,
+                                   C.byref(out), C.byref(hw), C.byref(conv))
+    _lp_status_ok(rc, raise_on_status)
+    m = Moments._of(out)
+    return EvaluateCI(offset + m.mean, hw.value, m.n, m.n_bad, bool(conv.value), m)
 
 
 def evaluate_epigraph(cuts, incumbent_cut, x, total_scenario_weight, lower_bound, sense=MIN_SENSE):
