@@ -312,7 +312,7 @@ static void free_template(twosd_ctx *c) {
     dfree(c->d_bkey); c->bkey_cap = 0;
     dfree(c->d_refresh_sel); c->refresh_sel_cap = 0; c->box_epi = -1;
     dfree(c->d_eo_pb); dfree(c->d_eo_K); dfree(c->d_eo_off); dfree(c->d_eo_etap); dfree(c->d_eo_etaoff);
-    dfree(c->d_eo_eidx); dfree(c->d_eo_evals); dfree(c->d_eo_used); c->eo_rows = c->eo_cap = 0; c->eo_kmax = 0;
+    dfree(c->d_eo_eidx); dfree(c->d_eo_evals); dfree(c->d_eo_used); c->eo_rows = c->eo_cap = 0; c->eo_kmax = 0; c->eo_min_cap = 0;
     dfree(c->d_pg_scrow); dfree(c->d_pg_scoff); dfree(c->d_pg_scval); dfree(c->d_pg_ival); dfree(c->d_pg_irow); dfree(c->d_pg_ioff); dfree(c->d_pg_amax); dfree(c->d_pg_d0p); dfree(c->d_pg_cnt); dfree(c->d_pg_tot);
     dfree(c->d_pg_valid); dfree(c->d_pg_head0); dfree(c->d_pg_map); dfree(c->d_pg_off); dfree(c->d_pg_pos);
     dfree(c->d_rt_pack); dfree(c->d_gs_heads); dfree(c->d_gs_cnt); dfree(c->d_gs_tot); dfree(c->d_gs_valid);
@@ -1248,6 +1248,20 @@ static int refresh_training(twosd_ctx *c, const double *x, const double *d_dv, i
             o.kcap = 0;
             if ((rc = run_lp_ex(c, x, d_dv, count, o))) return rc;
         }
+    }
+    // The eta files share one arena, claimed through an atomic counter that keeps counting past
+    // its end.  Files that did not fit are lost (K = -1), and which ones those are depends on the
+    // order the waves finish in: solve again with an arena of the size this run asked for, so that
+    // the refreshed pool does not depend on that order.  Past 2^31 entries (32-bit offsets) the
+    // losses stay.
+    HIPCHK(hipStreamSynchronize(c->stream));
+    unsigned long long used64 = 0;
+    HIPCHK(hipMemcpy(&used64, c->d_eo_used, sizeof(used64), hipMemcpyDeviceToHost));
+    if (used64 > c->eo_cap && used64 <= (unsigned long long)INT32_MAX) {
+        if (getenv("TWOSD_DEBUG"))
+            fprintf(stderr, "refresh training: eta files of %llu entries past the arena of %zu, solved again\n", used64, c->eo_cap);
+        c->eo_min_cap = (size_t)std::min<unsigned long long>(used64 + used64 / 8, INT32_MAX);
+        if ((rc = run_lp_ex(c, x, d_dv, count, o))) return rc;
     }
     c->last_train_opt = opt;
     if (n_opt) *n_opt = opt;
@@ -2562,15 +2576,18 @@ int twosd::run_lp_ex(twosd_ctx *c, const double *x, const double *d_dv, int N, c
             if (need * 4096 > (size_t)INT32_MAX)
                 return fail(TWOSD_E_UNSUPPORTED, "eta files of %zu solves exceed the 2^31-entry arena (at most %d)", need,
                             INT32_MAX / 4096);
-            if (need > c->eo_rows || c->eo_kmax != kmax) {
+            // the arena: 4096 entries per row, or what an earlier training run asked for
+            // (refresh_training solves again when the eta files did not fit)
+            const size_t cap_need = std::max(std::max<size_t>(need, 256) * 4096, c->eo_min_cap);
+            if (need > c->eo_rows || c->eo_kmax != kmax || c->eo_cap < cap_need) {
                 const size_t rows = std::max<size_t>(need, 256);
                 if ((rc = dalloc(&c->d_eo_pb, rows)) || (rc = dalloc(&c->d_eo_K, rows)) || (rc = dalloc(&c->d_eo_off, rows)) ||
                     (rc = dalloc(&c->d_eo_etap, rows * kmax)) || (rc = dalloc(&c->d_eo_etaoff, rows * (kmax + 1))) ||
-                    (rc = dalloc(&c->d_eo_eidx, rows * 4096)) || (rc = dalloc(&c->d_eo_evals, rows * 4096)))
+                    (rc = dalloc(&c->d_eo_eidx, cap_need)) || (rc = dalloc(&c->d_eo_evals, cap_need)))
                     return rc;
                 if (!c->d_eo_used && (rc = dalloc(&c->d_eo_used, 1))) return rc;
                 c->eo_rows = rows;
-                c->eo_cap = rows * 4096;
+                c->eo_cap = cap_need;
                 c->eo_kmax = kmax;
             }
             HIPCHK(hipMemsetAsync(c->d_eo_used, 0, sizeof(unsigned long long), c->stream));

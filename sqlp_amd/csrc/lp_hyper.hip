@@ -1572,6 +1572,9 @@ hipError_t launch_hyper(int R, int C, const HyperParams &p, int nblocks, size_t 
 
 int hyper_max_blocks_per_cu(int R, int C, int kmax, int k) {
     const size_t lds = hyper_lds_bytes(R, C, kmax, k);
+    // a block whose slices exceed the CU's 160 KB cannot launch: 0, not ho's floor of 1 (R = 16,
+    // C = 64, k = 127 at kmax = 1024 is 64 bytes past it, and the eta-capacity search took it)
+    if (lds > 160 * 1024) return 0;
     switch (R) {
         case 1: HYPER_C_SWITCH(1, ho, lds); break;
         case 2: HYPER_C_SWITCH(2, ho, lds); break;

@@ -180,6 +180,7 @@ struct twosd_ctx {
     unsigned long long *d_eo_used = nullptr;
     double *d_eo_evals = nullptr;
     size_t eo_rows = 0, eo_cap = 0;
+    size_t eo_min_cap = 0;   // arena floor: what a training run whose eta files did not fit asked for
     int eo_kmax = 0;
     double last_refresh_ms[5] = {0, 0, 0, 0, 0};   // train solves, re-solves, compose, upload, total
     int *d_refresh_sel = nullptr;                  // refresh: scenarios to re-solve

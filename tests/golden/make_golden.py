@@ -9,6 +9,9 @@ cannot be matched).  Files:
   lp_<name>.npz      x, scenario values, HiGHS obj / duals for a handful of scenarios
   cut_<name>.npz     V (HiGHS duals), x, values, weights, reference-order build_sasa_cut
                      alpha / beta / max_val / max_arg (strict '>' rule, tie_rel = 0)
+  synth_heads.npz    optimal basis heads of the generated templates whose host setup solve is too
+                     slow for a test (``python tests/golden/make_golden.py synth_heads`` writes
+                     this file alone)
 """
 import json
 import os
@@ -80,5 +83,20 @@ def main():
         json.dump(ev, f, indent=1)
 
 
+def synth_heads():
+    """Optimal basis head of scenario 0 at X[0] of the templates tests/synth_cases.GOLDEN_HEADS
+    names, read off the HiGHS solution (synth_cases.start_head; the scenario is nondegenerate)."""
+    from tests import synth_cases as SC
+    heads = {}
+    for tid in SC.GOLDEN_HEADS:
+        S = SC.template(tid)
+        heads[tid] = SC.start_head(S, SC.X[0], SC.values(S)[0])
+        print(tid, "head of", len(heads[tid]), "columns,", int((heads[tid] >= S.n2).sum()), "slacks")
+    np.savez_compressed(os.path.join(HERE, "synth_heads.npz"), **heads)
+
+
 if __name__ == "__main__":
-    main()
+    if sys.argv[1:] == ["synth_heads"]:
+        synth_heads()
+    else:
+        main()

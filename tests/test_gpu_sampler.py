@@ -72,3 +72,54 @@ def test_evaluate_sampled(name):
     s_a = twosd.evaluate_sampled(ctx, np.zeros(len(x)), x, N, seed, 0, h)
     s_b = twosd.evaluate_sampled(ctx, np.zeros(len(x)), x, N, seed, h, N - h)
     assert abs(float(np.dot(c1, x)) + s_a + s_b - val) <= 1e-10 * (1 + abs(val))
+
+
+def _mixed_sto(S):
+    """The three kinds mixed over the k random rhs rows of a generated template (the construction
+    of tests/test_oracle_kat.py::test_sampler_oracle_distributions), with the DISCRETE edges: a
+    one-point support, and probabilities that sum to 0.9, so that a tenth of the draws run the
+    cumulative scan to its `i < n - 1` stop."""
+    from sqlp_amd.smps import spSmpsPosition, spStoType
+    dists = [("DISCRETE", [1.0, 4.0, 2.0], [0.3, 0.3, 0.3]), ("NORMAL", 10.0, 4.0), ("UNIFORM", -1.0, 3.0),
+             ("DISCRETE", [2.5], [1.0]), ("DISCRETE", [7.0, 3.0, 5.0], [0.3, 0.3, 0.4]), ("UNIFORM", 100.0, 100.5),
+             ("NORMAL", -3.0, 0.25), ("DISCRETE", [-1.0, 1.0], [0.5, 0.5])]
+    sto = spStoType("synthetic", {})
+    for e, (col, row) in enumerate(S.positions):
+        sto.indep[spSmpsPosition(col, row)] = dists[e % len(dists)]
+    return sto
+
+
+@pytest.mark.parametrize("tid", ["c", "e"])
+def test_sampler_mixed_kinds_and_counter_carry(tid):
+    """UNIFORM elements (no shipped .sto has one), the DISCRETE edges, a seed with a nonzero high
+    word, and scenario indices that carry into the high counter word inside the batch: N k is no
+    multiple of the 256-thread block, so the last block is ragged.  Two shards that split at the
+    carry reproduce the single draw."""
+    from oracle import cpu
+    from sqlp_amd import twosd
+    from tests import synth_cases as SC
+    S = SC.template(tid)
+    sto = _mixed_sto(S)
+    ctx = twosd.SDContext(S.sp2, sto)
+    ctx.set_distributions(sto)
+    N, seed, first = 1000, 0x9E3779B97F4A7C15, 2 ** 32 - 300
+    assert (N * S.k) % 256 and seed >> 32
+    epi = twosd.sdEpigraph(ctx, 1.0, 0.0)
+    twosd.add_sampled_scenarios(epi, N, seed, first_index=first)
+    got = twosd.get_scenarios(epi)
+    ref = cpu.sample_deltas(sto, ctx.positions, ctx.template_values, N, seed, first) + ctx.template_values
+    kinds = np.array([sto.indep[p][0] for p in ctx.positions])
+    assert set(kinds) == {"DISCRETE", "NORMAL", "UNIFORM"}
+    exact = kinds != "NORMAL"
+    np.testing.assert_array_equal(got[:, exact], ref[:, exact])
+    np.testing.assert_allclose(got[:, ~exact], ref[:, ~exact], rtol=1e-12, atol=1e-12)
+    # the reference itself has what the case is about: the high counter word matters, the short
+    # DISCRETE element reaches its last value past its probability mass, UNIFORM stays in range
+    low = cpu.sample_deltas(sto, ctx.positions, ctx.template_values, N, seed, first - 2 ** 32) + ctx.template_values
+    assert (low[:300] != ref[:300]).any() and (low[300:] != ref[300:]).any()
+    assert np.allclose(ref[:, 3], 2.5) and 0.3 < np.isclose(ref[:, 0], 4.0).mean() < 0.5
+    assert ref[:, 2].min() >= -1.0 - 1e-12 and ref[:, 2].max() < 3.0 and len(np.unique(ref[:, 2])) > N - 5
+    two = twosd.sdEpigraph(ctx, 1.0, 0.0)
+    twosd.add_sampled_scenarios(two, 300, seed, first_index=first)
+    twosd.add_sampled_scenarios(two, N - 300, seed, first_index=2 ** 32)
+    np.testing.assert_array_equal(twosd.get_scenarios(two), got)
