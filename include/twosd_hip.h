@@ -83,7 +83,11 @@ int twosd_destroy(twosd_ctx *ctx);
  *   kernel envelope (1024 rows, the column slots, the LDS slice) applies to the LP's sizes:
  *   each boxed variable costs one row.  TWOSD_E_ARG for bounds that are no interval (lo > hi,
  *   NaN, lo = +inf, hi = -inf).
- * Re-setting the template clears basis, scenarios, dual vertex set and cuts.
+ * Re-setting the template clears basis, scenarios, dual vertex set and cuts, and releases every
+ * device array sized for the old template.  Statistics and heuristics start as on a fresh
+ * context: the twosd_last_* getters, timings and refresh times read zero or their defaults, and
+ * the push-mode choice and the automatic training pivot cap keep nothing of the old template.
+ * Caller settings (twosd_set_refresh_kcap, TWOSD_KMAX) stay.
  */
 int twosd_set_template(twosd_ctx *ctx, int m2, int n1, int n2,
                        const int64_t *T_colptr, const int64_t *T_rowval, const double *T_nzval,

@@ -40,55 +40,6 @@ int twosd::fail(int code, const char *fmt, ...) {
         if (_e != hipSuccess) return fail(TWOSD_E_DEVICE, "%s: %s", #expr, hipGetErrorString(_e)); \
     } while (0)
 
-// TWOSD_POISON=<byte> (test hook): every new device allocation is filled with that byte, so a
-// result that depends on memory no kernel wrote changes with it (the fill completes before the
-// allocation returns: the context's streams do not order against the null-stream memset)
-int twosd::poison_byte(int family) {
-    static const int b = getenv("TWOSD_POISON") ? atoi(getenv("TWOSD_POISON")) : -1;
-    static const int fam = getenv("TWOSD_POISON_FAMILY") ? atoi(getenv("TWOSD_POISON_FAMILY")) : -1;
-    static const bool said = b >= 0 && fprintf(stderr, "TWOSD_POISON: new device allocations filled with 0x%02x (families %d)\n",
-                                               b & 0xff, fam) > 0;
-    (void)said;
-    return (fam & family) ? b : -1;
-}
-template <typename T>
-static int dalloc(T **p, size_t count) {
-    if (*p) { hipFree(*p); *p = nullptr; }
-    if (count == 0) count = 1;
-    hipError_t e = hipMalloc((void **)p, sizeof(T) * count);
-    if (e != hipSuccess) return fail(TWOSD_E_DEVICE, "hipMalloc(%zu bytes): %s", sizeof(T) * count, hipGetErrorString(e));
-    if (poison_byte(1) >= 0) { hipMemset(*p, poison_byte(1), sizeof(T) * count); hipDeviceSynchronize(); }
-    return TWOSD_OK;
-}
-template <typename T>
-static void dfree(T *&p) {
-    if (p) hipFree(p);
-    p = nullptr;
-}
-
-// grow a device array to at least `count` elements, keeping `keep` elements
-template <typename T>
-int twosd::dgrow(T **p, size_t *cap, size_t count, size_t keep, hipStream_t s) {
-    if (count <= *cap && *p) return TWOSD_OK;
-    size_t ncap = std::max<size_t>(count, *cap * 2 + 1024);
-    T *np = nullptr;
-    hipError_t e = hipMalloc((void **)&np, sizeof(T) * ncap);
-    if (e != hipSuccess) return fail(TWOSD_E_DEVICE, "hipMalloc(%zu bytes): %s", sizeof(T) * ncap, hipGetErrorString(e));
-    if (poison_byte(2) >= 0) { hipMemset(np, poison_byte(2), sizeof(T) * ncap); hipDeviceSynchronize(); }
-    if (*p && keep) {
-        e = hipMemcpyAsync(np, *p, sizeof(T) * keep, hipMemcpyDeviceToDevice, s);
-        if (e != hipSuccess) return fail(TWOSD_E_DEVICE, "grow copy: %s", hipGetErrorString(e));
-        hipStreamSynchronize(s);
-    }
-    if (*p) hipFree(*p);
-    *p = np;
-    *cap = ncap;
-    return TWOSD_OK;
-}
-template int twosd::dgrow<double>(double **, size_t *, size_t, size_t, hipStream_t);
-template int twosd::dgrow<int>(int **, size_t *, size_t, size_t, hipStream_t);
-template int twosd::dgrow<uint64_t>(uint64_t **, size_t *, size_t, size_t, hipStream_t);
-
 extern "C" const char *twosd_last_error(void) { return g_err.c_str(); }
 extern "C" const char *twosd_version(void) { return "twosd-mi355x 0.1 (gfx950)"; }
 
@@ -98,7 +49,7 @@ extern "C" int twosd_create(int device, twosd_ctx **out) {
     HIPCHK(hipGetDeviceCount(&ndev));
     if (device < 0 || device >= ndev) return fail(TWOSD_E_ARG, "twosd_create: device %d of %d", device, ndev);
     HIPCHK(hipSetDevice(device));
-    twosd_ctx *c = new twosd_ctx();
+    std::unique_ptr<twosd_ctx> c(new twosd_ctx());   // a failure below destroys what was created
     c->device = device;
     HIPCHK(hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking));
     for (int i = 0; i < 8; ++i) HIPCHK(hipEventCreate(&c->ev[i]));
@@ -107,7 +58,7 @@ extern "C" int twosd_create(int device, twosd_ctx **out) {
     c->num_cus = prop.multiProcessorCount;
     const char *km = getenv("TWOSD_KMAX");
     if (km) c->kmax_override = atoi(km);
-    *out = c;
+    *out = c.release();
     return TWOSD_OK;
 }
 
@@ -134,20 +85,6 @@ static void build_ell(int S, F colf, std::vector<int> &slot, std::vector<int> &i
             }
         slot[s + 1] = slot[s] + width;
     }
-}
-
-// pinned host staging buffer `slot` of at least n elements of T (grown, never shrunk)
-template <typename T>
-static T *stage_buf(twosd_ctx *c, int slot, size_t n) {
-    const size_t bytes = std::max<size_t>(n, 1) * sizeof(T);
-    if (bytes > c->stage_bytes[slot]) {
-        if (c->stage[slot]) hipHostFree(c->stage[slot]);
-        c->stage[slot] = nullptr;
-        c->stage_bytes[slot] = 0;
-        if (hipHostMalloc(&c->stage[slot], bytes + bytes / 4) != hipSuccess) return nullptr;
-        c->stage_bytes[slot] = bytes + bytes / 4;
-    }
-    return static_cast<T *>(c->stage[slot]);
 }
 
 // the two-level candidate lists (device, or staged for the next selection) refer to pool
@@ -180,22 +117,16 @@ static int head_of(twosd_ctx *c, int p, const std::vector<int> **h) {
         // the heads of a device-built pool are fetched on the first host use, not by the refresh
         // (at N = 8 every rank would copy 9 MB per step that only tests and the CPU baseline read)
         const size_t need = c->pool.size() * (size_t)c->MP;
-        if (need > c->pool_hb_cap) {
-            if (c->pool_hb) hipHostFree(c->pool_hb);
-            c->pool_hb = nullptr;
-            c->pool_hb_cap = 0;
-            if (hipHostMalloc((void **)&c->pool_hb, sizeof(int) * need * 5 / 4) != hipSuccess)
-                return drop_pool(c, fail(TWOSD_E_DEVICE, "pool heads: pinned allocation of %zu ints failed", need));
-            c->pool_hb_cap = need * 5 / 4;
-        }
-        hipError_t e = hipMemcpyAsync(c->pool_hb, c->d_hb0, sizeof(int) * need, hipMemcpyDeviceToHost, c->stream);
+        if (!c->pool_hb.reserve<int>(need))
+            return drop_pool(c, fail(TWOSD_E_DEVICE, "pool heads: pinned allocation of %zu ints failed", need));
+        hipError_t e = hipMemcpyAsync(c->pool_hb.p, c->d_hb0, sizeof(int) * need, hipMemcpyDeviceToHost, c->stream);
         if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
         if (e != hipSuccess) return drop_pool(c, fail(TWOSD_E_DEVICE, "pool heads: read-back failed: %s", hipGetErrorString(e)));
         c->pool_hb_valid = true;
     }
     if (B.hb_row >= 0) {
         const int m = c->L.m;
-        const int *r = c->pool_hb + (size_t)B.hb_row * c->MP;
+        const int *r = c->pool_hb.as<int>() + (size_t)B.hb_row * c->MP;
         B.head.resize(m);
         for (int i = 0; i < m; ++i) B.head[i] = r[i] >> 2;
         B.hb_row = -1;
@@ -225,112 +156,22 @@ static void parallel_for(int n, F f) {
     for (auto &t : th) t.join();
 }
 
-template <typename T>
-static int upload_raw(T **d, const T *h, size_t n) {
-    int rc = dalloc(d, std::max<size_t>(n, 1));
-    if (rc) return rc;
-    if (n) HIPCHK(hipMemcpy(*d, h, sizeof(T) * n, hipMemcpyHostToDevice));
-    return TWOSD_OK;
-}
-
-// grow-only device array of at least n elements (no hipFree / hipMalloc when they fit;
-// contents not kept on growth)
-template <typename T>
-static int dev_reserve(twosd_ctx *c, T **d, size_t n) {
-    size_t &cap = c->dcap[(const void *)d];
-    if (!*d || cap < std::max<size_t>(n, 1)) {
-        const size_t want = std::max<size_t>(n, 1) + std::max<size_t>(n, 1) / 4;
-        int rc = dalloc(d, want);
-        if (rc) { cap = 0; return rc; }
-        cap = want;
-    }
-    return TWOSD_OK;
-}
-template <typename T>
-static int upload_big(twosd_ctx *c, T **d, const T *h, size_t n) {
-    int rc = dev_reserve(c, d, n);
-    if (rc) return rc;
-    if (n) HIPCHK(hipMemcpy(*d, h, sizeof(T) * n, hipMemcpyHostToDevice));
-    return TWOSD_OK;
-}
-template <typename T>
-static int upload_big(twosd_ctx *c, T **d, const std::vector<T> &h) {
-    return upload_big(c, d, h.data(), h.size());
-}
-
 // device selection-stream outputs of a pool of P bases with `records` records (prepare_x
 // writes them per x)
 static int reserve_selection(twosd_ctx *c, int P, int records) {
     int rc;
-    if ((size_t)std::max(records, 1) > c->sel_code_cap) {
-        dfree(c->d_sel_code);
-        if ((rc = dalloc(&c->d_sel_code, 2 * (size_t)std::max(records, 1)))) return rc;
-        c->sel_code_cap = std::max(records, 1);
-    }
-    if ((rc = dev_reserve(c, &c->d_sel_end, (size_t)P)) || (rc = dev_reserve(c, &c->d_sel_cinf, (size_t)P))) return rc;
+    if ((rc = c->d_sel_code.fit(2 * (size_t)std::max(records, 1)))) return rc;   // (code, float bits) pairs
+    if ((rc = c->d_sel_end.reserve((size_t)P)) || (rc = c->d_sel_cinf.reserve((size_t)P))) return rc;
     c->sel_cap_total = records;
     return TWOSD_OK;
 }
 
-template <typename T>
-static int upload(T **d, const std::vector<T> &h) {
-    int rc = dalloc(d, std::max<size_t>(h.size(), 1));
-    if (rc) return rc;
-    if (!h.empty()) HIPCHK(hipMemcpy(*d, h.data(), sizeof(T) * h.size(), hipMemcpyHostToDevice));
-    return TWOSD_OK;
-}
-
-static void free_template(twosd_ctx *c) {
-    dfree(c->d_colptr); dfree(c->d_rowidx); dfree(c->d_val); dfree(c->d_q); dfree(c->d_btype);
-    dfree(c->d_fixedmask); dfree(c->d_ubmask);
-    dfree(c->d_bm_src); dfree(c->d_bm_src2); dfree(c->d_bm_sign); dfree(c->d_bm_off); dfree(c->d_yu);
-    c->yu_cap = 0; c->has_bounds = false; c->nb = 0; c->c0 = 0.0;
-    dfree(c->d_hb0); dfree(c->d_basic0);
-    dfree(c->d_xbase); dfree(c->d_queue); dfree(c->d_lpstats);
-    dfree(c->d_obj); dfree(c->d_pi); dfree(c->d_pi_rep); dfree(c->d_y); dfree(c->d_status); dfree(c->d_iters); dfree(c->d_ops); dfree(c->d_etan);
-    dfree(c->d_dvtmp);
-    if (c->d_mompart) { hipFree(c->d_mompart); c->d_mompart = nullptr; }
-    dfree(c->d_ev_obj); dfree(c->d_ev_st); c->ev_obj_cap = c->ev_st_cap = 0;
-    dfree(c->d_bnnz); dfree(c->d_sel_cinf); dfree(c->d_sel_ptr); dfree(c->d_sel_code); c->sel_code_cap = 0; dfree(c->d_head_out); dfree(c->d_pool_pick); dfree(c->d_cpick); dfree(c->d_order); dfree(c->d_sort_tmp); dfree(c->d_qrec); c->qrec_cap = 0;
-    dfree(c->d_cand); dfree(c->d_sel_key); dfree(c->d_sel_pkey); dfree(c->d_sel_ppick); c->sel_pcap = 0; c->key_cap = 0; c->pool_l1 = c->pool_ncand = 0; c->order_cap = 0; c->sort_tmp_bytes = 0; c->head_cap = 0; c->pick_cap = 0; c->pool.clear();
-    dfree(c->d_dist_kind); dfree(c->d_dist_off); dfree(c->d_dist_val); dfree(c->d_dist_prob); dfree(c->d_dist_p0);
-    dfree(c->d_dist_p1); dfree(c->d_dist_tmpl); c->has_dist = false;
-    dfree(c->d_kslot); dfree(c->d_kix); dfree(c->d_kv); dfree(c->d_kcoef); c->k_valid = false;
-    dfree(c->d_sel_end); dfree(c->d_kp); dfree(c->d_ke); dfree(c->d_kraw); dfree(c->d_xaux); c->xaux_cap = 0; c->sel_cap_total = 0;
-    dfree(c->d_d0); dfree(c->d_eidx); dfree(c->d_evals); dfree(c->d_stamps);
-    dfree(c->d_wcp); dfree(c->d_wcc); dfree(c->d_wcv); dfree(c->d_bcp); dfree(c->d_bci); dfree(c->d_bcv);
-    dfree(c->d_brptr); dfree(c->d_brcol); dfree(c->d_brval);
-    c->earena_slots = 0; c->earena_cap = 0;
-    for (auto &e : c->epis) { dfree(e.d_dv); dfree(e.d_w); }
-    c->epis.clear();
-    c->out_cap = 0; c->dvtmp_cap = 0;
-    dvs_free(c);
-    cut_free(c);
-    vkey_free(c);
-    c->dcap.clear();
-    dfree(c->d_vkey); c->vkey_cap = 0;
-    dfree(c->d_bkey); c->bkey_cap = 0;
-    dfree(c->d_refresh_sel); c->refresh_sel_cap = 0; c->box_epi = -1;
-    dfree(c->d_eo_pb); dfree(c->d_eo_K); dfree(c->d_eo_off); dfree(c->d_eo_etap); dfree(c->d_eo_etaoff);
-    dfree(c->d_eo_eidx); dfree(c->d_eo_evals); dfree(c->d_eo_used); c->eo_rows = c->eo_cap = 0; c->eo_kmax = 0; c->eo_min_cap = 0;
-    dfree(c->d_pg_scrow); dfree(c->d_pg_scoff); dfree(c->d_pg_scval); dfree(c->d_pg_ival); dfree(c->d_pg_irow); dfree(c->d_pg_ioff); dfree(c->d_pg_amax); dfree(c->d_pg_d0p); dfree(c->d_pg_cnt); dfree(c->d_pg_tot);
-    dfree(c->d_pg_valid); dfree(c->d_pg_head0); dfree(c->d_pg_map); dfree(c->d_pg_off); dfree(c->d_pg_pos);
-    dfree(c->d_rt_pack); dfree(c->d_gs_heads); dfree(c->d_gs_cnt); dfree(c->d_gs_tot); dfree(c->d_gs_valid);
-    dfree(c->d_gs_irow); dfree(c->d_gs_ioff); dfree(c->d_gs_ival);
-    if (c->d_gs_seg) { hipFree(c->d_gs_seg); c->d_gs_seg = nullptr; c->gs_seg_cap = 0; }
-    c->rt_epi = -1; c->rt_nown = -1; c->rt_trained = false;
-    if (c->pool_hb) { hipHostFree(c->pool_hb); c->pool_hb = nullptr; c->pool_hb_cap = 0; }
-    c->has_template = c->has_basis = false;
-}
+// a template re-set starts from the state of a fresh context: buffers, flags and statistics
+static void free_template(twosd_ctx *c) { static_cast<TemplateState &>(*c) = TemplateState(); }
 
 extern "C" int twosd_destroy(twosd_ctx *c) {
     if (!c) return TWOSD_OK;
     hipSetDevice(c->device);
-    free_template(c);
-    for (int i = 0; i < 8; ++i) hipEventDestroy(c->ev[i]);
-    for (int i = 0; i < 16; ++i)
-        if (c->stage[i]) hipHostFree(c->stage[i]);
-    hipStreamDestroy(c->stream);
     delete c;
     return TWOSD_OK;
 }
@@ -501,7 +342,6 @@ extern "C" int twosd_set_template(twosd_ctx *c, int m2, int n1, int n2, const in
     HIPCHK(hipSetDevice(c->device));
     free_template(c);
     HostLP &L = c->L;
-    L = HostLP();
     int rc;
     if ((rc = read_csc(m2, n2, Wcp, Wrv, Wnz, base, L.colptr, L.rowidx, L.val))) return rc;
     for (int i = 0; i < m2; ++i)
@@ -546,12 +386,12 @@ extern "C" int twosd_set_template(twosd_ctx *c, int m2, int n1, int n2, const in
     c->CH = hyper_cols_per_lane(n2 + m2);
     if (c->CH <= 0) return fail(TWOSD_E_UNSUPPORTED, "%s: %d LP columns and rows exceed the LP kernel's column slots", sizes, n2 + m2);
     // device template
-    if (K.any && ((rc = upload(&c->d_bm_src, K.src)) || (rc = upload(&c->d_bm_src2, K.src2)) || (rc = upload(&c->d_bm_sign, K.sign)) ||
-                  (rc = upload(&c->d_bm_off, K.off))))
+    if (K.any && ((rc = c->d_bm_src.upload(K.src)) || (rc = c->d_bm_src2.upload(K.src2)) || (rc = c->d_bm_sign.upload(K.sign)) ||
+                  (rc = c->d_bm_off.upload(K.off))))
         return rc;
-    if ((rc = dalloc(&c->d_colptr, n2 + 1)) || (rc = dalloc(&c->d_rowidx, nnzW)) || (rc = dalloc(&c->d_val, nnzW)) ||
-        (rc = dalloc(&c->d_q, n2)) || (rc = dalloc(&c->d_btype, n2 + m2)) || (rc = dalloc(&c->d_fixedmask, 64)) ||
-        (rc = dalloc(&c->d_ubmask, 64)))
+    if ((rc = c->d_colptr.alloc(n2 + 1)) || (rc = c->d_rowidx.alloc(nnzW)) || (rc = c->d_val.alloc(nnzW)) ||
+        (rc = c->d_q.alloc(n2)) || (rc = c->d_btype.alloc(n2 + m2)) || (rc = c->d_fixedmask.alloc(64)) ||
+        (rc = c->d_ubmask.alloc(64)))
         return rc;
     std::vector<int8_t> bt(n2 + m2);
     std::vector<uint64_t> fixedm(64, 0), ubm(64, 0);
@@ -582,7 +422,7 @@ extern "C" int twosd_set_template(twosd_ctx *c, int m2, int n1, int n2, const in
             for (auto &e : rows[i]) { cc.push_back(e.first); cv.push_back(e.second); }
             cp[i + 1] = (int)cc.size();
         }
-        if ((rc = upload(&c->d_wcp, cp)) || (rc = upload(&c->d_wcc, cc)) || (rc = upload(&c->d_wcv, cv))) return rc;
+        if ((rc = c->d_wcp.upload(cp)) || (rc = c->d_wcc.upload(cc)) || (rc = c->d_wcv.upload(cv))) return rc;
     }
     c->has_template = true;
     c->k = 0;
@@ -740,9 +580,9 @@ static int upload_pool(twosd_ctx *c) {
     if (ro[P] > INT32_MAX) return fail(TWOSD_E_UNSUPPORTED, "basis pool too large (> 2^31 entries)");
     const size_t nz = std::max<size_t>(ro[P], 1);
     std::vector<int> rp_all((size_t)P * (MP + 1)), cp_all((size_t)P * (MP + 1));
-    int *rc_all = stage_buf<int>(c, 0, nz), *ci_all = stage_buf<int>(c, 1, nz);
-    double *rv_all = stage_buf<double>(c, 2, nz), *cv_all = stage_buf<double>(c, 3, nz);
-    double *d0_all = stage_buf<double>(c, 4, (size_t)P * 64 * std::max(c->CH, 1));
+    int *rc_all = c->stage[0].reserve<int>(nz), *ci_all = c->stage[1].reserve<int>(nz);
+    double *rv_all = c->stage[2].reserve<double>(nz), *cv_all = c->stage[3].reserve<double>(nz);
+    double *d0_all = c->stage[4].reserve<double>((size_t)P * 64 * std::max(c->CH, 1));
     if (!rc_all || !ci_all || !rv_all || !cv_all || !d0_all) return fail(TWOSD_E_DEVICE, "pool upload: pinned staging allocation failed");
     parallel_for(P, [&](int p) {
         const PoolBasis &B = c->pool[p];
@@ -781,12 +621,12 @@ static int upload_pool(twosd_ctx *c) {
     });
     const auto tc = std::chrono::steady_clock::now();
     int rc;
-    if ((rc = upload_big(c, &c->d_hb0, hb)) || (rc = upload_big(c, &c->d_basic0, basic)) || (rc = upload_big(c, &c->d_bnnz, bnnz))) return rc;
+    if ((rc = c->d_hb0.upload_reserve(hb)) || (rc = c->d_basic0.upload_reserve(basic)) || (rc = c->d_bnnz.upload_reserve(bnnz))) return rc;
     if (c->CH > 0) {
-        if ((rc = upload_big(c, &c->d_bcp, cp_all)) || (rc = upload_big(c, &c->d_bci, ci_all, ro[P])) ||
-            (rc = upload_big(c, &c->d_bcv, cv_all, ro[P])) || (rc = upload_big(c, &c->d_brptr, rp_all)) ||
-            (rc = upload_big(c, &c->d_brcol, rc_all, ro[P])) || (rc = upload_big(c, &c->d_brval, rv_all, ro[P])) ||
-            (rc = upload_big(c, &c->d_d0, d0_all, (size_t)P * 64 * c->CH)))
+        if ((rc = c->d_bcp.upload_reserve(cp_all)) || (rc = c->d_bci.upload_reserve(ci_all, ro[P])) ||
+            (rc = c->d_bcv.upload_reserve(cv_all, ro[P])) || (rc = c->d_brptr.upload_reserve(rp_all)) ||
+            (rc = c->d_brcol.upload_reserve(rc_all, ro[P])) || (rc = c->d_brval.upload_reserve(rv_all, ro[P])) ||
+            (rc = c->d_d0.upload_reserve(d0_all, (size_t)P * 64 * c->CH)))
             return rc;
         c->b0_nnz = bnnz[0];
     }
@@ -1031,10 +871,10 @@ static int pg_args(twosd_ctx *c, int nsrc, PgArgs &A) {
     const HostLP &L = c->L;
     const int m = L.m;
     int rc;
-    if ((rc = dev_reserve(c, &c->d_pg_pos, (size_t)std::max(c->k, 1))) || (rc = dev_reserve(c, &c->d_pg_amax, (size_t)nsrc)) ||
-        (rc = dev_reserve(c, &c->d_pg_cnt, (size_t)4 * nsrc * m)) || (rc = dev_reserve(c, &c->d_pg_tot, (size_t)5 * nsrc)) ||
-        (rc = dev_reserve(c, &c->d_pg_valid, (size_t)nsrc)) || (rc = dev_reserve(c, &c->d_pg_head0, (size_t)m)) ||
-        (rc = dev_reserve(c, &c->d_pg_d0p, (size_t)64 * c->CH)) || (rc = dev_reserve(c, &c->d_pg_ioff, (size_t)nsrc)))
+    if ((rc = c->d_pg_pos.reserve((size_t)std::max(c->k, 1))) || (rc = c->d_pg_amax.reserve((size_t)nsrc)) ||
+        (rc = c->d_pg_cnt.reserve((size_t)4 * nsrc * m)) || (rc = c->d_pg_tot.reserve((size_t)5 * nsrc)) ||
+        (rc = c->d_pg_valid.reserve((size_t)nsrc)) || (rc = c->d_pg_head0.reserve((size_t)m)) ||
+        (rc = c->d_pg_d0p.reserve((size_t)64 * c->CH)) || (rc = c->d_pg_ioff.reserve((size_t)nsrc)))
         return rc;
     HIPCHK(hipMemcpyAsync(c->d_pg_head0, c->head0.data(), sizeof(int) * m, hipMemcpyHostToDevice, c->stream));
     HIPCHK(hipMemcpyAsync(c->d_pg_d0p, c->d_d0, sizeof(double) * 64 * c->CH, hipMemcpyDeviceToDevice, c->stream));
@@ -1070,13 +910,13 @@ static int pg_compute(twosd_ctx *c, int nsrc, PgArgs &A, int **h_tot, int **h_va
     if (getenv("TWOSD_PG_NOSCRATCH")) cap = 0;   // A/B knob: two FTRAN passes
     if (const char *e = getenv("TWOSD_PG_SCCAP")) cap = atoll(e);   // test hook: sources past it take pass 1
     cap = std::min(cap, ((3LL << 29) / 12) / std::max(nsrc, 1));
-    if (cap > 0 && ((rc = dev_reserve(c, &c->d_pg_scrow, (size_t)nsrc * cap)) || (rc = dev_reserve(c, &c->d_pg_scval, (size_t)nsrc * cap)) ||
-                    (rc = dev_reserve(c, &c->d_pg_scoff, (size_t)nsrc * m))))
+    if (cap > 0 && ((rc = c->d_pg_scrow.reserve((size_t)nsrc * cap)) || (rc = c->d_pg_scval.reserve((size_t)nsrc * cap)) ||
+                    (rc = c->d_pg_scoff.reserve((size_t)nsrc * m))))
         return rc;
     A.sc_cap = cap; A.sc_row = c->d_pg_scrow; A.sc_val = c->d_pg_scval; A.sc_off = c->d_pg_scoff;
     HIPCHK(pg_launch_ftran(A, 0, nsrc, c->stream));
-    int *h_nz = stage_buf<int>(c, 11, (size_t)nsrc);
-    long long *h_ioff = stage_buf<long long>(c, 12, (size_t)nsrc);
+    int *h_nz = c->stage[11].reserve<int>((size_t)nsrc);
+    long long *h_ioff = c->stage[12].reserve<long long>((size_t)nsrc);
     if (!h_nz || !h_ioff) return fail(TWOSD_E_DEVICE, "pool refresh: pinned staging allocation failed");
     HIPCHK(hipMemcpyAsync(h_nz, A.nztot, sizeof(int) * nsrc, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
@@ -1088,14 +928,14 @@ static int pg_compute(twosd_ctx *c, int nsrc, PgArgs &A, int **h_tot, int **h_va
         nzmax = std::max<long long>(nzmax, h_nz[a]);
         over += h_nz[a] > cap;
     }
-    if ((rc = dev_reserve(c, &c->d_pg_irow, (size_t)inz)) || (rc = dev_reserve(c, &c->d_pg_ival, (size_t)inz))) return rc;
+    if ((rc = c->d_pg_irow.reserve((size_t)inz)) || (rc = c->d_pg_ival.reserve((size_t)inz))) return rc;
     HIPCHK(hipMemcpyAsync(c->d_pg_ioff, h_ioff, sizeof(long long) * nsrc, hipMemcpyHostToDevice, c->stream));
     A.inter_off = c->d_pg_ioff; A.inter_row = c->d_pg_irow; A.inter_val = c->d_pg_ival;
     if (cap > 0) HIPCHK(pg_launch_gather(A, nsrc, c->stream));
     if (over || cap == 0) HIPCHK(pg_launch_ftran(A, 1, nsrc, c->stream));
     c->pg_sc_cap = std::max<long long>(1024, nzmax + nzmax / 2);   // the next build's scratch
     HIPCHK(pg_launch_count(A, nsrc, c->stream));
-    int *ht = stage_buf<int>(c, 9, (size_t)5 * nsrc);
+    int *ht = c->stage[9].reserve<int>((size_t)5 * nsrc);
     if (!ht) return fail(TWOSD_E_DEVICE, "pool refresh: pinned staging allocation failed");
     HIPCHK(hipMemcpyAsync(ht, c->d_pg_tot, sizeof(int) * 4 * nsrc, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipMemcpyAsync(ht + (size_t)4 * nsrc, c->d_pg_valid, sizeof(int) * nsrc, hipMemcpyDeviceToHost, c->stream));
@@ -1130,7 +970,7 @@ static int pg_assemble(twosd_ctx *c, PgArgs &A, const int *h_tot, const int *h_v
     const int P = (int)map.size();
     const bool dbg = getenv("TWOSD_DEBUG") != nullptr;
     const auto t0 = std::chrono::steady_clock::now();
-    if ((rc = dev_reserve(c, &c->d_pg_map, (size_t)P)) || (rc = dev_reserve(c, &c->d_pg_off, (size_t)4 * P))) return rc;
+    if ((rc = c->d_pg_map.reserve((size_t)P)) || (rc = c->d_pg_off.reserve((size_t)4 * P))) return rc;
     // From here the live pool arrays are grown in place (a grown array does not keep its
     // contents) and then overwritten: a failure past this point leaves c->pool describing
     // arrays that no longer hold it.  The context then drops its basis, so every later solve
@@ -1143,15 +983,15 @@ static int pg_assemble(twosd_ctx *c, PgArgs &A, const int *h_tot, const int *h_v
     HIPCHK(hipMemcpyAsync(c->d_pg_map, map.data(), sizeof(int) * P, hipMemcpyHostToDevice, c->stream));
     HIPCHK(hipMemcpyAsync(c->d_pg_off, off.data(), sizeof(int) * 4 * P, hipMemcpyHostToDevice, c->stream));
     const size_t nz = (size_t)acc[0], kz = (size_t)acc[1], ez = (size_t)acc[2] * 64;
-    if ((rc = dev_reserve(c, &c->d_brptr, (size_t)P * (MP + 1))) || (rc = dev_reserve(c, &c->d_brcol, nz)) ||
-        (rc = dev_reserve(c, &c->d_brval, nz)) || (rc = dev_reserve(c, &c->d_bcp, (size_t)P * (MP + 1))) ||
-        (rc = dev_reserve(c, &c->d_bci, nz)) || (rc = dev_reserve(c, &c->d_bcv, nz)) ||
-        (rc = dev_reserve(c, &c->d_kp, (size_t)P * (m + 1))) || (rc = dev_reserve(c, &c->d_ke, kz)) ||
-        (rc = dev_reserve(c, &c->d_kraw, kz)) || (rc = dev_reserve(c, &c->d_kslot, (size_t)P * (c->R + 1))) ||
-        (rc = dev_reserve(c, &c->d_kix, ez)) || (rc = dev_reserve(c, &c->d_kv, ez)) ||
-        (rc = dev_reserve(c, &c->d_hb0, (size_t)P * MP)) || (rc = dev_reserve(c, &c->d_basic0, (size_t)P * 64)) ||
-        (rc = dev_reserve(c, &c->d_bnnz, (size_t)P)) || (rc = dev_reserve(c, &c->d_d0, (size_t)P * 64 * c->CH)) ||
-        (rc = dev_reserve(c, &c->d_sel_ptr, (size_t)P + 1)) || (rc = reserve_selection(c, P, (int)acc[3])))
+    if ((rc = c->d_brptr.reserve((size_t)P * (MP + 1))) || (rc = c->d_brcol.reserve(nz)) ||
+        (rc = c->d_brval.reserve(nz)) || (rc = c->d_bcp.reserve((size_t)P * (MP + 1))) ||
+        (rc = c->d_bci.reserve(nz)) || (rc = c->d_bcv.reserve(nz)) ||
+        (rc = c->d_kp.reserve((size_t)P * (m + 1))) || (rc = c->d_ke.reserve(kz)) ||
+        (rc = c->d_kraw.reserve(kz)) || (rc = c->d_kslot.reserve((size_t)P * (c->R + 1))) ||
+        (rc = c->d_kix.reserve(ez)) || (rc = c->d_kv.reserve(ez)) ||
+        (rc = c->d_hb0.reserve((size_t)P * MP)) || (rc = c->d_basic0.reserve((size_t)P * 64)) ||
+        (rc = c->d_bnnz.reserve((size_t)P)) || (rc = c->d_d0.reserve((size_t)P * 64 * c->CH)) ||
+        (rc = c->d_sel_ptr.reserve((size_t)P + 1)) || (rc = reserve_selection(c, P, (int)acc[3])))
         return broken(rc);
     // (a grown array is reallocated: the start pool's CSC was read only by the FTRAN passes)
     PgFill F{};
@@ -1316,10 +1156,7 @@ extern "C" int twosd_pool_refresh(twosd_ctx *c, int epi, const double *x, int fi
     c->last_refresh_ms[2] = c->last_refresh_ms[3] = 0.0;
     if (R > 0 && !getenv("TWOSD_REFRESH_HOST")) {
         // 3. B^{-1} of the representatives from their eta files, and the pool arrays, on the device
-        if ((size_t)R > c->refresh_sel_cap) {
-            if ((rc = dalloc(&c->d_refresh_sel, (size_t)R))) return rc;
-            c->refresh_sel_cap = R;
-        }
+        if ((rc = c->d_refresh_sel.fit((size_t)R))) return rc;
         HIPCHK(hipMemcpyAsync(c->d_refresh_sel, sel.data(), sizeof(int) * R, hipMemcpyHostToDevice, c->stream));
         const int dev = refresh_build_device(c, sel);
         if (dev < 0) return dev;
@@ -1457,18 +1294,12 @@ __global__ void rt_copy_kernel(const CopySeg *__restrict__ seg) {
 }
 static int rt_copy(twosd_ctx *c, const std::vector<CopySeg> &segs) {
     if (segs.empty()) return TWOSD_OK;
-    CopySeg *h = stage_buf<CopySeg>(c, 13, segs.size());
+    CopySeg *h = c->stage[13].reserve<CopySeg>(segs.size());
     if (!h) return fail(TWOSD_E_DEVICE, "refresh: pinned staging allocation failed");
     std::copy(segs.begin(), segs.end(), h);
-    if (!c->d_gs_seg || c->gs_seg_cap < segs.size()) {
-        if (c->d_gs_seg) hipFree(c->d_gs_seg);
-        c->d_gs_seg = nullptr;
-        c->gs_seg_cap = 0;
-        HIPCHK(hipMalloc(&c->d_gs_seg, sizeof(CopySeg) * std::max<size_t>(segs.size(), 64)));
-        c->gs_seg_cap = std::max<size_t>(segs.size(), 64);
-    }
+    if (int rc = c->d_gs_seg.fit(sizeof(CopySeg) * std::max<size_t>(segs.size(), 64))) return rc;
     HIPCHK(hipMemcpyAsync(c->d_gs_seg, h, sizeof(CopySeg) * segs.size(), hipMemcpyHostToDevice, c->stream));
-    hipLaunchKernelGGL(rt_copy_kernel, dim3(64, (unsigned)segs.size()), dim3(256), 0, c->stream, (const CopySeg *)c->d_gs_seg);
+    hipLaunchKernelGGL(rt_copy_kernel, dim3(64, (unsigned)segs.size()), dim3(256), 0, c->stream, (const CopySeg *)c->d_gs_seg.p);
     HIPCHK(hipGetLastError());
     HIPCHK(hipStreamSynchronize(c->stream));   // the staging buffer is reused by the next call
     return TWOSD_OK;
@@ -1558,21 +1389,18 @@ extern "C" int twosd_refresh_build_local(twosd_ctx *c, int n_own, const int *rep
     const auto t0 = std::chrono::steady_clock::now();
     const int m = c->L.m;
     int rc;
-    if ((size_t)std::max(n_own, 1) > c->refresh_sel_cap) {
-        if ((rc = dalloc(&c->d_refresh_sel, (size_t)std::max(n_own, 1)))) return rc;
-        c->refresh_sel_cap = std::max(n_own, 1);
-    }
+    if ((rc = c->d_refresh_sel.fit((size_t)std::max(n_own, 1)))) return rc;
     if (n_own) HIPCHK(hipMemcpyAsync(c->d_refresh_sel, reps, sizeof(int) * n_own, hipMemcpyHostToDevice, c->stream));
     PgArgs A;
     int *h_tot = nullptr, *h_valid = nullptr;
     long long inz = 0;
     const int nsrc = n_own + 1;
     if ((rc = pg_compute(c, nsrc, A, &h_tot, &h_valid, &inz, getenv("TWOSD_DEBUG") != nullptr))) return rc;
-    const long long *h_ioff = static_cast<const long long *>(c->stage[12]);
+    const long long *h_ioff = c->stage[12].as<long long>();
     const long long nz0 = n_own ? h_ioff[1] : inz;
     const RtPack L = rt_layout(n_own, inz - nz0, m);
-    if ((rc = dev_reserve(c, &c->d_rt_pack, L.bytes))) return rc;
-    long long *hdr = stage_buf<long long>(c, 14, 4);
+    if ((rc = c->d_rt_pack.reserve(L.bytes))) return rc;
+    long long *hdr = c->stage[14].reserve<long long>(4);
     if (!hdr) return fail(TWOSD_E_DEVICE, "refresh: pinned staging allocation failed");
     hdr[0] = n_own; hdr[1] = inz - nz0; hdr[2] = (long long)L.bytes; hdr[3] = m;
     HIPCHK(hipMemcpyAsync(c->d_rt_pack, hdr, 32, hipMemcpyHostToDevice, c->stream));
@@ -1638,10 +1466,10 @@ extern "C" int twosd_refresh_assemble(twosd_ctx *c, int G, const void *d_packs, 
     if (nsrc > INT32_MAX / std::max(m, 1)) return fail(TWOSD_E_UNSUPPORTED, "refresh_assemble: too many sources");
     for (int i = 0; i < R; ++i)
         if (order[i] < 1 || order[i] >= nsrc) return fail(TWOSD_E_ARG, "refresh_assemble: source %d outside [1, %lld)", order[i], nsrc);
-    if ((rc = dev_reserve(c, &c->d_gs_heads, (size_t)std::max<long long>(nsrc - 1, 1) * m)) ||
-        (rc = dev_reserve(c, &c->d_gs_cnt, (size_t)4 * nsrc * m)) || (rc = dev_reserve(c, &c->d_gs_tot, (size_t)5 * nsrc)) ||
-        (rc = dev_reserve(c, &c->d_gs_valid, (size_t)nsrc)) || (rc = dev_reserve(c, &c->d_gs_ioff, (size_t)nsrc)) ||
-        (rc = dev_reserve(c, &c->d_gs_irow, (size_t)nzg)) || (rc = dev_reserve(c, &c->d_gs_ival, (size_t)nzg)))
+    if ((rc = c->d_gs_heads.reserve((size_t)std::max<long long>(nsrc - 1, 1) * m)) ||
+        (rc = c->d_gs_cnt.reserve((size_t)4 * nsrc * m)) || (rc = c->d_gs_tot.reserve((size_t)5 * nsrc)) ||
+        (rc = c->d_gs_valid.reserve((size_t)nsrc)) || (rc = c->d_gs_ioff.reserve((size_t)nsrc)) ||
+        (rc = c->d_gs_irow.reserve((size_t)nzg)) || (rc = c->d_gs_ival.reserve((size_t)nzg)))
         return rc;
     // the table: source 0 = this rank's primary (local compute row 0), then every rank's pack
     std::vector<CopySeg> seg;
@@ -1673,8 +1501,8 @@ extern "C" int twosd_refresh_assemble(twosd_ctx *c, int G, const void *d_packs, 
     if (getenv("TWOSD_DEBUG"))
         fprintf(stderr, "refresh_assemble: %lld sources, %lld entries, unpack %.2f ms\n", nsrc, nzg,
                 std::chrono::duration<double, std::milli>(t_copy - t0).count());
-    int *h_tot = stage_buf<int>(c, 9, (size_t)6 * nsrc);
-    long long *h_ioff = stage_buf<long long>(c, 12, (size_t)nsrc);
+    int *h_tot = c->stage[9].reserve<int>((size_t)6 * nsrc);
+    long long *h_ioff = c->stage[12].reserve<long long>((size_t)nsrc);
     if (!h_tot || !h_ioff) return fail(TWOSD_E_DEVICE, "refresh: pinned staging allocation failed");
     int *h_nz = h_tot + 4 * nsrc, *h_valid = h_tot + 5 * nsrc;
     HIPCHK(hipMemcpyAsync(h_tot, c->d_gs_tot, sizeof(int) * 5 * nsrc, hipMemcpyDeviceToHost, c->stream));
@@ -1737,7 +1565,7 @@ static int candidate_picks(twosd_ctx *c, const EpiDevice &E, const double *x, in
                            int *p1, int *pf) {
     int rc;
     if ((rc = prepare_x(c, x))) return rc;
-    if ((rc = dev_reserve(c, &c->d_cpick, (size_t)count))) return rc;   // grow-only: no hipMalloc / hipFree per refresh
+    if ((rc = c->d_cpick.reserve((size_t)count))) return rc;   // grow-only: no reallocation per refresh
     int *d_p = c->d_cpick;
     const double *dv = E.d_dv + (size_t)first * c->k;
     auto picks = [&](int np, int *out) {   // selection runs on c->stream
@@ -1790,10 +1618,10 @@ static int set_candidates(twosd_ctx *c, int level1, int ncand, int n, const int 
                 c->pool.size(), level1, diff, n, filled);
     }
     int rc;
-    int *h = stage_buf<int>(c, 15, cand.size());
+    int *h = c->stage[15].reserve<int>(cand.size());
     if (!h) return fail(TWOSD_E_DEVICE, "pool candidates: pinned staging allocation failed");
     std::copy(cand.begin(), cand.end(), h);
-    if ((rc = dev_reserve(c, &c->d_cand, cand.size()))) return rc;
+    if ((rc = c->d_cand.reserve(cand.size()))) return rc;
     HIPCHK(hipMemcpyAsync(c->d_cand, h, sizeof(int) * cand.size(), hipMemcpyHostToDevice, c->stream));
     c->pool_l1 = level1;
     c->pool_ncand = ncand;
@@ -1896,8 +1724,8 @@ extern "C" int twosd_add_scenarios(twosd_ctx *c, int epi, int N, const double *v
             w[s] = weights[s];
         }
     int rc;
-    if ((rc = dgrow(&E.d_dv, &E.dv_cap, (size_t)(E.count + N) * k, (size_t)E.count * k, c->stream))) return rc;
-    if ((rc = dgrow(&E.d_w, &E.w_cap, (size_t)(E.count + N), (size_t)E.count, c->stream))) return rc;
+    if ((rc = E.d_dv.grow((size_t)(E.count + N) * k, (size_t)E.count * k, c->stream))) return rc;
+    if ((rc = E.d_w.grow((size_t)(E.count + N), (size_t)E.count, c->stream))) return rc;
     if (k) HIPCHK(hipMemcpy(E.d_dv + (size_t)E.count * k, dv.data(), sizeof(double) * N * k, hipMemcpyHostToDevice));
     HIPCHK(hipMemcpy(E.d_w + E.count, w.data(), sizeof(double) * N, hipMemcpyHostToDevice));
     E.w_host.insert(E.w_host.end(), w.begin(), w.end());
@@ -1944,9 +1772,9 @@ extern "C" int twosd_set_distributions(twosd_ctx *c, int k, const int *kind, con
         off[e + 1] = (int)val.size();
     }
     int rc;
-    if ((rc = upload(&c->d_dist_kind, kd)) || (rc = upload(&c->d_dist_off, off)) || (rc = upload(&c->d_dist_val, val)) ||
-        (rc = upload(&c->d_dist_prob, prob)) || (rc = upload(&c->d_dist_p0, p0)) || (rc = upload(&c->d_dist_p1, p1)) ||
-        (rc = upload(&c->d_dist_tmpl, tmpl)))
+    if ((rc = c->d_dist_kind.upload(kd)) || (rc = c->d_dist_off.upload(off)) || (rc = c->d_dist_val.upload(val)) ||
+        (rc = c->d_dist_prob.upload(prob)) || (rc = c->d_dist_p0.upload(p0)) || (rc = c->d_dist_p1.upload(p1)) ||
+        (rc = c->d_dist_tmpl.upload(tmpl)))
         return rc;
     // mean absolute deviation E|V_e - E V_e| per element: the spread of the scenarios (the scale
     // of the selection key's count weight)
@@ -1987,8 +1815,8 @@ extern "C" int twosd_add_sampled_scenarios(twosd_ctx *c, int epi, int N, uint64_
             w[s] = weights[s];
         }
     int rc;
-    if ((rc = dgrow(&E.d_dv, &E.dv_cap, (size_t)(E.count + N) * k, (size_t)E.count * k, c->stream))) return rc;
-    if ((rc = dgrow(&E.d_w, &E.w_cap, (size_t)(E.count + N), (size_t)E.count, c->stream))) return rc;
+    if ((rc = E.d_dv.grow((size_t)(E.count + N) * k, (size_t)E.count * k, c->stream))) return rc;
+    if ((rc = E.d_w.grow((size_t)(E.count + N), (size_t)E.count, c->stream))) return rc;
     SampleParams S{};
     S.N = N; S.k = k; S.seed = seed; S.first_index = first_index;
     S.kind = c->d_dist_kind; S.off = c->d_dist_off; S.val = c->d_dist_val; S.prob = c->d_dist_prob;
@@ -2023,7 +1851,7 @@ extern "C" int twosd_evaluate_sampled(twosd_ctx *c, const double *x, int64_t N_t
     for (int64_t at = 0; at < count; at += chunk) {
         const int n = (int)std::min(chunk, count - at);
         int rc;
-        if ((rc = dgrow(&c->d_dvtmp, &c->dvtmp_cap, (size_t)n * std::max(k, 1), 0, c->stream))) return rc;
+        if ((rc = c->d_dvtmp.grow((size_t)n * std::max(k, 1), 0, c->stream))) return rc;
         SampleParams S{};
         S.N = n; S.k = k; S.seed = seed; S.first_index = (unsigned long long)(first + at);
         S.kind = c->d_dist_kind; S.off = c->d_dist_off; S.val = c->d_dist_val; S.prob = c->d_dist_prob;
@@ -2106,8 +1934,8 @@ static int prepare_elements(twosd_ctx *c) {
     // by row (x_B warm start of the LP kernel), written in place
     const size_t kz = std::max<size_t>(kcnt[P], 1), ez = std::max<size_t>(ecnt[P], 1);
     std::vector<int> kp((size_t)P * (m + 1)), ks((size_t)P * (R + 1)), cap(P + 1);
-    int *ke = stage_buf<int>(c, 5, kz), *ki = stage_buf<int>(c, 6, ez);
-    double *kr = stage_buf<double>(c, 7, kz), *kv = stage_buf<double>(c, 8, ez);
+    int *ke = c->stage[5].reserve<int>(kz), *ki = c->stage[6].reserve<int>(ez);
+    double *kr = c->stage[7].reserve<double>(kz), *kv = c->stage[8].reserve<double>(ez);
     if (!ke || !ki || !kr || !kv) return fail(TWOSD_E_DEVICE, "pool elements: pinned staging allocation failed");
     for (int p = 0; p <= P; ++p) cap[p] = (int)ccnt[p];
     parallel_for(P, [&](int p) {
@@ -2147,15 +1975,15 @@ static int prepare_elements(twosd_ctx *c) {
     });
     const auto t_pe1 = std::chrono::steady_clock::now();
     int rc;
-    if (c->CH > 0 && ((rc = upload_big(c, &c->d_kslot, ks)) || (rc = upload_big(c, &c->d_kix, ki, ecnt[P])) ||
-                      (rc = upload_big(c, &c->d_kv, kv, ecnt[P]))))
+    if (c->CH > 0 && ((rc = c->d_kslot.upload_reserve(ks)) || (rc = c->d_kix.upload_reserve(ki, ecnt[P])) ||
+                      (rc = c->d_kv.upload_reserve(kv, ecnt[P]))))
         return rc;
     const auto t_pe2 = std::chrono::steady_clock::now();
     if (c->CH > 0 && P > 1) {
         // device selection-stream inputs: CSR rows of every basis, and a static record capacity
         // per basis (every row active: m row starts + all its entries)
-        if ((rc = upload_big(c, &c->d_kp, kp)) || (rc = upload_big(c, &c->d_ke, ke, kz)) || (rc = upload_big(c, &c->d_kraw, kr, kz)) ||
-            (rc = upload_big(c, &c->d_sel_ptr, cap)) || (rc = reserve_selection(c, P, cap[P])))
+        if ((rc = c->d_kp.upload_reserve(kp)) || (rc = c->d_ke.upload_reserve(ke, kz)) || (rc = c->d_kraw.upload_reserve(kr, kz)) ||
+            (rc = c->d_sel_ptr.upload_reserve(cap)) || (rc = reserve_selection(c, P, cap[P])))
             return rc;
     }
     c->k_valid = true;
@@ -2330,19 +2158,6 @@ __global__ void __launch_bounds__(kSelStreamThreads) pool_selstream_kernel(
     }
 }
 
-// copy n host elements to a device array grown only when n exceeds its capacity
-template <typename T>
-static int upload_cap(T **d, size_t *cap, const T *h, size_t n) {
-    if (!*d || n > *cap) {
-        const size_t nc = std::max<size_t>(n, 1);
-        int rc = dalloc(d, nc);
-        if (rc) return rc;
-        *cap = nc;
-    }
-    if (n) HIPCHK(hipMemcpy(*d, h, sizeof(T) * n, hipMemcpyHostToDevice));
-    return TWOSD_OK;
-}
-
 // per-x shared data: b = r - T x; per pool basis xbase_p = B_p^{-1} b (sparse rows);
 // coef_e(x); with a pool, the
 // selection stream (active rows that can turn infeasible on the training box of the deltas).
@@ -2359,10 +2174,7 @@ int twosd::prepare_x(twosd_ctx *c, const double *x) {
     const int P = (int)c->pool.size();
     std::vector<double> coef(std::max(k, 1), 1.0);
     for (int e = 0; e < k; ++e) coef[e] = c->pos_col[e] < 0 ? 1.0 : -x[c->pos_col[e]];
-    if (!c->d_xbase || (size_t)P * MP > c->xbase_cap) {
-        if ((rc = dalloc(&c->d_xbase, (size_t)P * MP))) return rc;
-        c->xbase_cap = (size_t)P * MP;
-    }
+    if ((rc = c->d_xbase.fit((size_t)P * MP))) return rc;
     if (c->CH > 0) {
         // everything per x on the device: one upload of [b, coef, box lo, box hi], x_B of every
         // pool basis, then the selection stream (pool_selstream_kernel)
@@ -2375,8 +2187,9 @@ int twosd::prepare_x(twosd_ctx *c, const double *x) {
             std::copy(c->sel_lo.begin(), c->sel_lo.end(), aux.begin() + m + k);
             std::copy(c->sel_hi.begin(), c->sel_hi.end(), aux.begin() + m + 2 * k);
         }
-        if ((rc = upload_cap(&c->d_xaux, &c->xaux_cap, aux.data(), aux.size())) ||
-            (rc = upload_cap(&c->d_kcoef, &c->kcoef_cap, coef.data(), coef.size())))
+        // re-uploaded in place: no reallocation per x
+        if ((rc = c->d_xaux.fit(aux.size())) || (rc = c->d_xaux.copy_from(aux.data(), aux.size())) ||
+            (rc = c->d_kcoef.fit(coef.size())) || (rc = c->d_kcoef.copy_from(coef.data(), coef.size())))
             return rc;
         const size_t tot = (size_t)P * MP;
         hipLaunchKernelGGL(pool_xbase_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, c->stream, P, MP, c->d_brptr,
@@ -2397,7 +2210,7 @@ int twosd::prepare_x(twosd_ctx *c, const double *x) {
             static const bool sel_order = !getenv("TWOSD_SEL_ROWORDER") || atoi(getenv("TWOSD_SEL_ROWORDER")) != 0;   // A/B knob
             hipLaunchKernelGGL(pool_selstream_kernel, dim3(P), dim3(kSelStreamThreads), 0, c->stream, m, MP, k, c->d_xbase,
                                c->d_hb0, c->d_kp, c->d_ke, c->d_kraw, c->d_xaux, box ? 1 : 0, sel_order ? 1 : 0,
-                               c->sel_cw, c->d_sel_ptr, reinterpret_cast<int2 *>(c->d_sel_code), c->d_sel_end, c->d_sel_cinf);
+                               c->sel_cw, c->d_sel_ptr, reinterpret_cast<int2 *>(c->d_sel_code.p), c->d_sel_end, c->d_sel_cinf);
             HIPCHK(hipGetLastError());
         }
         if (getenv("TWOSD_DEBUG") && sel) {
@@ -2434,26 +2247,18 @@ static int select_pool(twosd_ctx *c, const double *d_dv, int N, int *d_pick, int
     HIPCHK(sort_by_pool(d_pick, nullptr, N, P, nullptr, &tb, c->stream));
     HIPCHK(sort_by_pool(d_pick, nullptr, N, np1, nullptr, &tb2, c->stream));
     tb = std::max(tb, tb2);
-    if ((size_t)N > c->order_cap || tb > c->sort_tmp_bytes) {
-        if ((rc = dalloc(&c->d_order, (size_t)N)) || (rc = dalloc(&c->d_sort_tmp, tb))) return rc;
-        c->order_cap = N;
-        c->sort_tmp_bytes = tb;
+    if ((size_t)N > c->d_order.cap || tb > c->d_sort_tmp.cap) {   // both at once, as one workspace
+        if ((rc = c->d_order.alloc((size_t)N)) || (rc = c->d_sort_tmp.alloc(tb))) return rc;
     }
-    if (two && (size_t)N > c->key_cap) {
-        if ((rc = dalloc(&c->d_sel_key, (size_t)N))) return rc;
-        c->key_cap = N;
-    }
+    if (two && (rc = c->d_sel_key.fit((size_t)N))) return rc;
     // partials of the chunked selections (small batches: several pool chunks per scenario tile)
     const int g1 = pool_select_split(N, np1), g2 = two ? pool_refine_split(N, c->pool_ncand) : 1;
     const size_t pneed = (size_t)std::max(g1, g2) * N;
-    if (std::max(g1, g2) > 1 && pneed > c->sel_pcap) {
-        if ((rc = dalloc(&c->d_sel_pkey, pneed)) || (rc = dalloc(&c->d_sel_ppick, pneed))) return rc;
-        c->sel_pcap = pneed;
-    }
+    if (std::max(g1, g2) > 1 && ((rc = c->d_sel_pkey.fit(pneed)) || (rc = c->d_sel_ppick.fit(pneed)))) return rc;
     PoolSelParams S{};
     S.N = N; S.k = c->k; S.npool = np1; S.dv = d_dv;
     S.kcoef = c->d_kcoef;
-    S.cinf = c->d_sel_cinf; S.sptr = c->d_sel_ptr; S.send = c->d_sel_end; S.rec = reinterpret_cast<const int2 *>(c->d_sel_code);
+    S.cinf = c->d_sel_cinf; S.sptr = c->d_sel_ptr; S.send = c->d_sel_end; S.rec = reinterpret_cast<const int2 *>(c->d_sel_code.p);
     S.pick = d_pick;
     S.cw = c->sel_cw;
     S.key = two ? c->d_sel_key : nullptr;
@@ -2495,34 +2300,22 @@ int twosd::run_lp_ex(twosd_ctx *c, const double *x, const double *d_dv, int N, c
     const int NL = list ? o.nlist : N;   // scenarios this launch solves
     int rc;
     if ((rc = prepare_x(c, x))) return rc;
-    if (list && c->pool.size() > 1 && (size_t)N > c->pick_cap) return fail(TWOSD_E_STATE, "LP list mode: no recorded pool picks");
+    if (list && c->pool.size() > 1 && (size_t)N > c->d_pool_pick.cap) return fail(TWOSD_E_STATE, "LP list mode: no recorded pool picks");
     const int m = c->L.m, n = c->L.n, MP = c->MP, R = c->R;
     if (N > c->out_cap) {
         size_t cap = std::max<size_t>(N, 1024);
-        if ((rc = dalloc(&c->d_obj, cap)) || (rc = dalloc(&c->d_status, cap)) || (rc = dalloc(&c->d_iters, cap)) ||
-            (rc = dalloc(&c->d_ops, cap)) || (rc = dalloc(&c->d_etan, cap)))
+        if ((rc = c->d_obj.alloc(cap)) || (rc = c->d_status.alloc(cap)) || (rc = c->d_iters.alloc(cap)) ||
+            (rc = c->d_ops.alloc(cap)) || (rc = c->d_etan.alloc(cap)))
             return rc;
-        dfree(c->d_pi); dfree(c->d_y);
-        c->pi_cap = c->y_cap = 0;
+        c->d_pi.release(); c->d_y.release();
         c->out_cap = (int)cap;
     }
-    if (want_pi && (size_t)NL > c->pi_cap) {
-        if ((rc = dalloc(&c->d_pi, (size_t)c->out_cap * m))) return rc;
-        c->pi_cap = c->out_cap;
-    }
-    if (o.want_key && (size_t)N > c->vkey_cap) {
-        if ((rc = dalloc(&c->d_vkey, (size_t)c->out_cap))) return rc;
-        c->vkey_cap = c->out_cap;
-    }
-    if (o.want_bkey && (size_t)N > c->bkey_cap) {
-        if ((rc = dalloc(&c->d_bkey, (size_t)c->out_cap))) return rc;
-        c->bkey_cap = c->out_cap;
-    }
-    if (want_y && (size_t)N > c->y_cap) {
-        if ((rc = dalloc(&c->d_y, (size_t)c->out_cap * n))) return rc;
-        c->y_cap = c->out_cap;
-    }
-    if (!c->d_queue && (rc = dalloc(&c->d_queue, (size_t)kMaxQueueGroups * kQueueStride))) return rc;
+    // the optional outputs, out_cap rows each, on their first use at this out_cap
+    if (want_pi && (size_t)NL * m > c->d_pi.cap && (rc = c->d_pi.alloc((size_t)c->out_cap * m))) return rc;
+    if (o.want_key && (size_t)N > c->d_vkey.cap && (rc = c->d_vkey.alloc((size_t)c->out_cap))) return rc;
+    if (o.want_bkey && (size_t)N > c->d_bkey.cap && (rc = c->d_bkey.alloc((size_t)c->out_cap))) return rc;
+    if (want_y && (size_t)N * n > c->d_y.cap && (rc = c->d_y.alloc((size_t)c->out_cap * n))) return rc;
+    if (!c->d_queue && (rc = c->d_queue.alloc((size_t)kMaxQueueGroups * kQueueStride))) return rc;
     {
         // eta capacity (pivots per scenario): 2m + 32, at least 64.  256 keeps storm's two 4-wave
         // blocks per CU within the LDS; past 256 the file grows (up to 1024, in steps of 32) as far as
@@ -2545,7 +2338,7 @@ int twosd::run_lp_ex(twosd_ctx *c, const double *x, const double *d_dv, int N, c
         const int nblocks = std::max(1, std::min((NL + kWavesPerBlock - 1) / kWavesPerBlock, bpc * c->num_cus));
         const size_t slots = (size_t)nblocks * kWavesPerBlock;
         if (slots > c->earena_slots || ecap != c->earena_cap) {
-            if ((rc = dalloc(&c->d_eidx, slots * ecap)) || (rc = dalloc(&c->d_evals, slots * ecap))) return rc;
+            if ((rc = c->d_eidx.alloc(slots * ecap)) || (rc = c->d_evals.alloc(slots * ecap))) return rc;
             c->earena_slots = slots;
             c->earena_cap = ecap;
         }
@@ -2581,11 +2374,11 @@ int twosd::run_lp_ex(twosd_ctx *c, const double *x, const double *d_dv, int N, c
             const size_t cap_need = std::max(std::max<size_t>(need, 256) * 4096, c->eo_min_cap);
             if (need > c->eo_rows || c->eo_kmax != kmax || c->eo_cap < cap_need) {
                 const size_t rows = std::max<size_t>(need, 256);
-                if ((rc = dalloc(&c->d_eo_pb, rows)) || (rc = dalloc(&c->d_eo_K, rows)) || (rc = dalloc(&c->d_eo_off, rows)) ||
-                    (rc = dalloc(&c->d_eo_etap, rows * kmax)) || (rc = dalloc(&c->d_eo_etaoff, rows * (kmax + 1))) ||
-                    (rc = dalloc(&c->d_eo_eidx, cap_need)) || (rc = dalloc(&c->d_eo_evals, cap_need)))
+                if ((rc = c->d_eo_pb.alloc(rows)) || (rc = c->d_eo_K.alloc(rows)) || (rc = c->d_eo_off.alloc(rows)) ||
+                    (rc = c->d_eo_etap.alloc(rows * kmax)) || (rc = c->d_eo_etaoff.alloc(rows * (kmax + 1))) ||
+                    (rc = c->d_eo_eidx.alloc(cap_need)) || (rc = c->d_eo_evals.alloc(cap_need)))
                     return rc;
-                if (!c->d_eo_used && (rc = dalloc(&c->d_eo_used, 1))) return rc;
+                if (!c->d_eo_used && (rc = c->d_eo_used.alloc(1))) return rc;
                 c->eo_rows = rows;
                 c->eo_cap = cap_need;
                 c->eo_kmax = kmax;
@@ -2597,36 +2390,27 @@ int twosd::run_lp_ex(twosd_ctx *c, const double *x, const double *d_dv, int N, c
         }
         if (o.want_head) {   // rows: list positions, or scenarios
             const size_t need = list ? (size_t)NL : (size_t)N;
-            if (need > c->head_cap) {
-                if ((rc = dalloc(&c->d_head_out, need * m))) return rc;
-                c->head_cap = need;
-            }
+            if ((rc = c->d_head_out.fit(need * m))) return rc;
             H.head_out = c->d_head_out;
         }
         H.pi_by_pos = list ? 1 : 0;
         H.status = c->d_status; H.iters = c->d_iters; H.ops = c->d_ops; H.etan = c->d_etan;
-        if (!c->d_lpstats && (rc = dalloc(&c->d_lpstats, 6))) return rc;
+        if (!c->d_lpstats && (rc = c->d_lpstats.alloc(6))) return rc;
         if (!list) HIPCHK(hipMemsetAsync(c->d_lpstats + 5, 0, sizeof(unsigned long long), c->stream));
         H.retries = list ? nullptr : c->d_lpstats + 5;   // a list re-solve repeats recorded picks: no retries
         if (!c->d_stamps) {
-            if ((rc = dalloc(&c->d_stamps, 16))) return rc;
+            if ((rc = c->d_stamps.alloc(16))) return rc;
             HIPCHK(hipMemset(c->d_stamps, 0, sizeof(unsigned long long) * 16));
         }
         H.stamps = c->d_stamps;
         H.npool = (int)c->pool.size();
         H.bnnz = c->d_bnnz;
         if (c->want_head && !list) {
-            if ((size_t)N > c->head_cap) {
-                if ((rc = dalloc(&c->d_head_out, (size_t)N * m))) return rc;
-                c->head_cap = N;
-            }
+            if ((rc = c->d_head_out.fit((size_t)N * m))) return rc;
             H.head_out = c->d_head_out;
         }
         if (H.npool > 1) {
-            if (!list && (size_t)N > c->pick_cap) {
-                if ((rc = dalloc(&c->d_pool_pick, (size_t)N))) return rc;
-                c->pick_cap = N;
-            }
+            if (!list && (rc = c->d_pool_pick.fit((size_t)N))) return rc;
             H.pool_pick = c->d_pool_pick;
         }
         if (!list && c->d_kslot && getenv("TWOSD_DEBUG")) {
@@ -2658,11 +2442,7 @@ int twosd::run_lp_ex(twosd_ctx *c, const double *x, const double *d_dv, int N, c
         // from its claim in one load; part of the timed LP launch.  Neither an order nor a pool:
         // position q is scenario q from the primary basis and the kernel reads no record.
         if (order || H.npool > 1) {
-            if ((size_t)NL > c->qrec_cap) {
-                const size_t cap = std::max<size_t>(NL, 1024);
-                if ((rc = dalloc(&c->d_qrec, cap))) return rc;
-                c->qrec_cap = cap;
-            }
+            if ((rc = c->d_qrec.fit(std::max<size_t>(NL, 1024)))) return rc;
             HIPCHK(launch_queue_records(order, H.npool > 1 ? c->d_pool_pick : nullptr, c->d_qrec, NL, c->stream));
             H.qrec = c->d_qrec;
         }
@@ -2872,19 +2652,18 @@ __global__ void __launch_bounds__(256) bounds_backmap_kernel(int N, int n2, int 
 // d_w: the batch's scenario weights (nullable: 1.0), for the objective sum
 static int copy_lp_outputs(twosd_ctx *c, int N, double *obj, double *pi, double *y, int *status, const double *d_w) {
     if (!c->d_lpstats) {
-        int rc = dalloc(&c->d_lpstats, 6);
+        int rc = c->d_lpstats.alloc(6);
         if (rc) return rc;
     }
     if (!c->d_objpart) {
-        int rc = dalloc(&c->d_objpart, (size_t)2 * kObjBlocks);
+        int rc = c->d_objpart.alloc((size_t)2 * kObjBlocks);
         if (rc) return rc;
     }
     const double *d_yout = c->d_y;
     if (c->has_bounds) {   // before the objective sum and the copies: they see the caller's values
-        if (y && (size_t)N > c->yu_cap) {
-            int rc = dalloc(&c->d_yu, (size_t)std::max(N, c->out_cap) * c->n2_user);
-            if (rc) { c->yu_cap = 0; return rc; }
-            c->yu_cap = (size_t)std::max(N, c->out_cap);
+        if (y && (size_t)N * c->n2_user > c->d_yu.cap) {
+            int rc = c->d_yu.alloc((size_t)std::max(N, c->out_cap) * c->n2_user);
+            if (rc) return rc;
         }
         const size_t work = y ? (size_t)N * c->n2_user : (size_t)N;
         hipLaunchKernelGGL(bounds_backmap_kernel, dim3((unsigned)std::min<size_t>(4096, (work + 255) / 256)), dim3(256), 0, c->stream, N,
@@ -2968,8 +2747,9 @@ static int device_moments(twosd_ctx *c, long long N, const double *d_va, const i
     const int R = d_vb ? 3 : 1;
     for (int r = 0; r < R; ++r) out[r] = kMomentsEmpty;
     if (N <= 0) return TWOSD_OK;
-    if (!c->d_mompart) HIPCHK(hipMalloc(&c->d_mompart, sizeof(twosd_moments) * 3 * kMomBlocks));
-    twosd_moments *d_part = (twosd_moments *)c->d_mompart;
+    if (!c->d_mompart)
+        if (int rc = c->d_mompart.alloc(sizeof(twosd_moments) * 3 * kMomBlocks)) return rc;
+    twosd_moments *d_part = (twosd_moments *)c->d_mompart.p;
     if (d_vb)
         hipLaunchKernelGGL(eval_moments_kernel<true>, dim3(kMomBlocks), dim3(256), 0, c->stream, N, d_va, d_sa, d_vb, d_sb, d_part);
     else
@@ -2989,10 +2769,10 @@ extern "C" int twosd_moments_of_values(twosd_ctx *c, int64_t n, const double *ob
     HIPCHK(hipSetDevice(c->device));
     int rc;
     if (n > 0) {
-        if ((rc = dgrow(&c->d_ev_obj, &c->ev_obj_cap, (size_t)n, 0, c->stream))) return rc;
+        if ((rc = c->d_ev_obj.grow((size_t)n, 0, c->stream))) return rc;
         HIPCHK(hipMemcpy(c->d_ev_obj, obj, sizeof(double) * n, hipMemcpyHostToDevice));
         if (status) {
-            if ((rc = dgrow(&c->d_ev_st, &c->ev_st_cap, (size_t)n, 0, c->stream))) return rc;
+            if ((rc = c->d_ev_st.grow((size_t)n, 0, c->stream))) return rc;
             HIPCHK(hipMemcpy(c->d_ev_st, status, sizeof(int) * n, hipMemcpyHostToDevice));
         }
     }
@@ -3011,7 +2791,7 @@ static int64_t eval_chunk_size() {
 static int eval_solve_chunk(twosd_ctx *c, const double *x, int64_t at, int n, uint64_t seed) {
     const int k = c->k;
     int rc;
-    if ((rc = dgrow(&c->d_dvtmp, &c->dvtmp_cap, (size_t)n * std::max(k, 1), 0, c->stream))) return rc;
+    if ((rc = c->d_dvtmp.grow((size_t)n * std::max(k, 1), 0, c->stream))) return rc;
     SampleParams S{};
     S.N = n; S.k = k; S.seed = seed; S.first_index = (unsigned long long)at;
     S.kind = c->d_dist_kind; S.off = c->d_dist_off; S.val = c->d_dist_val; S.prob = c->d_dist_prob;
@@ -3042,8 +2822,8 @@ static int eval_moments_range(twosd_ctx *c, const double *xa, const double *xb, 
         else if (rc) return rc;
         twosd_moments m[3];
         if (xb) {
-            if ((rc = dgrow(&c->d_ev_obj, &c->ev_obj_cap, (size_t)n, 0, c->stream)) ||
-                (rc = dgrow(&c->d_ev_st, &c->ev_st_cap, (size_t)n, 0, c->stream)))
+            if ((rc = c->d_ev_obj.grow((size_t)n, 0, c->stream)) ||
+                (rc = c->d_ev_st.grow((size_t)n, 0, c->stream)))
                 return rc;
             HIPCHK(hipMemcpyAsync(c->d_ev_obj, c->d_obj, sizeof(double) * n, hipMemcpyDeviceToDevice, c->stream));
             HIPCHK(hipMemcpyAsync(c->d_ev_st, c->d_status, sizeof(int) * n, hipMemcpyDeviceToDevice, c->stream));
@@ -3196,7 +2976,7 @@ extern "C" int twosd_solve_values(twosd_ctx *c, const double *x, int N, const do
     for (int s = 0; s < N; ++s)
         for (int e = 0; e < k; ++e) dv[(size_t)s * k + e] = values[(size_t)s * k + e] - template_value(c, e);
     int rc;
-    if ((rc = dgrow(&c->d_dvtmp, &c->dvtmp_cap, (size_t)N * std::max(k, 1), 0, c->stream))) return rc;
+    if ((rc = c->d_dvtmp.grow((size_t)N * std::max(k, 1), 0, c->stream))) return rc;
     HIPCHK(hipMemcpy(c->d_dvtmp, dv.data(), sizeof(double) * dv.size(), hipMemcpyHostToDevice));
     if ((rc = run_lp(c, x, c->d_dvtmp, N, pi != nullptr, y != nullptr))) return rc;
     return copy_lp_outputs(c, N, obj, pi, y, status, nullptr);
@@ -3322,10 +3102,7 @@ extern "C" int twosd_solve_push(twosd_ctx *c, int epi, const double *x, int firs
         c->push_rep_frac = (double)U / count;
         if (U > 0 && full) {
             const int m = c->L.m;
-            if ((size_t)U > c->pi_rep_cap) {
-                if ((rc = dalloc(&c->d_pi_rep, (size_t)U * m))) return rc;
-                c->pi_rep_cap = U;
-            }
+            if ((rc = c->d_pi_rep.fit((size_t)U * m))) return rc;
             hipLaunchKernelGGL(gather_rows_kernel, dim3((unsigned)std::min<size_t>(4096, ((size_t)U * m + 255) / 256)), dim3(256), 0,
                                c->stream, U, m, d_list, c->d_pi, c->d_pi_rep);
             HIPCHK(hipGetLastError());

@@ -1518,82 +1518,60 @@ __global__ void cut_g_final_kernel(int nb, int m, const double *__restrict__ gpa
 }
 
 // ---------------------------------------------------------------------------------
+template <typename T>
+using CutBuf = DevBuf<T, 4>;
 struct CutWs {
-    double *PK = nullptr, *PKT = nullptr, *PKO = nullptr;
-    double *PKTc = nullptr;
-    size_t pktc_cap = 0;
-    float *PKTc32 = nullptr;               // the fp32 pass's chunk source
-    size_t pktc32_cap = 0;
-    float *basec32 = nullptr;              // the fp32 pass's prefilter bases
-    size_t basec32_cap = 0;
+    CutBuf<double> PK, PKT, PKO;
+    CutBuf<double> PKTc;
+    CutBuf<float> PKTc32;               // the fp32 pass's chunk source
+    CutBuf<float> basec32;              // the fp32 pass's prefilter bases
+    // PK rows up to date, the vertices PK / PKT / PKO / phash / tprev hold, and their row length
     int pk_count = 0, pk_vcap = 0, pk_k4 = 0;
-    size_t pk_cap = 0;
-    int *rows = nullptr;
-    int *eord = nullptr;    // elements by ascending row: the order of the restated score's dot
-    unsigned long long *phash = nullptr;   // per vertex: hash of its PK row (bits)
-    int *tprev = nullptr;                  // per vertex: previous vertex with a bit-identical PK row, or -1
-    unsigned long long *tw_hs = nullptr;   // twin rebuild by sort: sorted hashes, vertex ids in / out, cub scratch
-    int *tw_vin = nullptr, *tw_vout = nullptr;
-    void *tw_tmp = nullptr;
-    size_t tw_cap = 0, tw_tmp_bytes = 0;
-    int *vmap = nullptr, *nvc = nullptr;   // per x: the argmax's vertices and their count
-    size_t vmap_cap = 0;
-    double *PKOc = nullptr, *basec = nullptr;   // per x: their PKO rows and bases (vmap order)
-    size_t pkoc_cap = 0;
-    double *coef = nullptr, *bvec = nullptr, *base = nullptr, *partial = nullptr, *sums = nullptr;
-    double *gpart = nullptr, *g = nullptr;
-    int *arg = nullptr, *flag = nullptr;
-    double *val = nullptr;
-    unsigned long long *hist = nullptr, *hist_part = nullptr;
-    size_t hpart_cap = 0;
-    double *part2 = nullptr;
-    double *tp_m = nullptr;
-    int *tp_i = nullptr, *tp_f = nullptr;
-    size_t tp_cap = 0;
-    int *cand = nullptr, *tcand = nullptr;    // candidate logs (whole tiles / tail ranges)
-    unsigned long long *fstats = nullptr;     // fixup counters of the last cut (3)
-    size_t cand_cap = 0, tcand_cap = 0;
-    unsigned long long *band_bits = nullptr;
+    CutBuf<int> rows;
+    CutBuf<int> eord;    // elements by ascending row: the order of the restated score's dot
+    CutBuf<unsigned long long> phash;   // per vertex: hash of its PK row (bits)
+    CutBuf<int> tprev;                  // per vertex: previous vertex with a bit-identical PK row, or -1
+    CutBuf<unsigned long long> tw_hs;   // twin rebuild by sort: sorted hashes, vertex ids in / out, cub scratch
+    CutBuf<int> tw_vin, tw_vout;
+    CutBuf<char> tw_tmp;
+    CutBuf<int> vmap, nvc;   // per x: the argmax's vertices and their count
+    CutBuf<double> PKOc, basec;   // per x: their PKO rows and bases (vmap order)
+    CutBuf<double> coef, bvec, base, partial, sums;
+    CutBuf<double> gpart, g;
+    CutBuf<int> arg, flag;
+    CutBuf<double> val;
+    CutBuf<unsigned long long> hist, hist_part;
+    CutBuf<double> part2;
+    CutBuf<double> tp_m;
+    CutBuf<int> tp_i, tp_f;
+    CutBuf<int> cand, tcand;    // candidate logs (whole tiles / tail ranges)
+    CutBuf<unsigned long long> fstats;     // fixup counters of the last cut (3)
+    CutBuf<unsigned long long> band_bits;
     // per epigraph: max |dv[., e]| over its scenarios (bits), the rows folded in so far
-    std::vector<unsigned long long *> dmax;
+    std::vector<CutBuf<unsigned long long>> dmax;
     std::vector<int> dmax_rows, dmax_k;
-    size_t base_cap = 0, part_cap = 0, n_cap = 0, hist_cap = 0, gpart_cap = 0, sums_cap = 0, part2_cap = 0;
     int m = 0, vec_m = 0;
     std::vector<double> h_coef, h_bvec;   // pinned-lifetime host staging for async uploads
 };
 
 static CutWs *cws(twosd_ctx *c) {
-    if (!c->cut_ws) c->cut_ws = new CutWs();
-    return (CutWs *)c->cut_ws;
+    if (!c->cut_ws) c->cut_ws.reset(new CutWs());
+    return c->cut_ws.get();
 }
 
-
-void cut_free(twosd_ctx *c) {
-    if (!c->cut_ws) return;
-    CutWs *w = (CutWs *)c->cut_ws;
-    hipFree(w->PK); hipFree(w->PKT); hipFree(w->PKO); hipFree(w->PKTc); hipFree(w->PKTc32); hipFree(w->basec32); hipFree(w->rows); hipFree(w->eord); hipFree(w->coef); hipFree(w->bvec); hipFree(w->base);
-    hipFree(w->partial); hipFree(w->sums); hipFree(w->gpart); hipFree(w->g); hipFree(w->arg); hipFree(w->flag);
-    hipFree(w->val); hipFree(w->hist); hipFree(w->part2); hipFree(w->hist_part);
-    hipFree(w->tp_m); hipFree(w->tp_i); hipFree(w->tp_f);
-    hipFree(w->cand); hipFree(w->tcand); hipFree(w->band_bits); hipFree(w->fstats);
-    hipFree(w->phash); hipFree(w->tprev); hipFree(w->tw_hs); hipFree(w->tw_vin); hipFree(w->tw_vout); hipFree(w->tw_tmp); hipFree(w->vmap); hipFree(w->nvc); hipFree(w->PKOc); hipFree(w->basec);
-    for (auto *p : w->dmax) hipFree(p);
-    delete w;
-    c->cut_ws = nullptr;
-}
+void cut_free(CutWs *w) { delete w; }
 
 void cut_truncate_pk(twosd_ctx *c, int size) {
     if (!c->cut_ws) return;
-    CutWs *w = (CutWs *)c->cut_ws;
+    CutWs *w = c->cut_ws.get();
     if (w->pk_count > size) w->pk_count = size;   // twin links point to lower vertices: still valid
 }
 
 void cut_invalidate_pk(twosd_ctx *c) {
     if (!c->cut_ws) return;
-    CutWs *w = (CutWs *)c->cut_ws;
+    CutWs *w = c->cut_ws.get();
     w->pk_count = 0;
-    if (w->rows) hipFree(w->rows);
-    w->rows = nullptr;   // forces re-upload of the element rows (and their order)
+    w->rows.release();   // forces re-upload of the element rows (and their order)
 }
 
 #define HIPCHK(expr)                                                                               \
@@ -1605,21 +1583,11 @@ void cut_invalidate_pk(twosd_ctx *c) {
 // a cut that returns before the argmax (no scenarios) leaves no fixup counters: clear the last
 // cut's, so twosd_cut_stats does not report them as this cut's
 static int clear_cut_stats(twosd_ctx *c) {
-    CutWs *w = c->cut_ws ? (CutWs *)c->cut_ws : nullptr;
+    CutWs *w = c->cut_ws.get();
     if (w && w->fstats) {
         HIPCHK(hipMemsetAsync(w->fstats, 0, sizeof(unsigned long long) * 16, c->stream));
         HIPCHK(hipStreamSynchronize(c->stream));
     }
-    return TWOSD_OK;
-}
-
-template <typename T>
-static int realloc_dev(T **p, size_t n) {
-    if (*p) hipFree(*p);
-    *p = nullptr;
-    hipError_t e = hipMalloc((void **)p, sizeof(T) * std::max<size_t>(n, 1));
-    if (e != hipSuccess) return fail(TWOSD_E_DEVICE, "cut workspace hipMalloc(%zu): %s", sizeof(T) * n, hipGetErrorString(e));
-    if (poison_byte(4) >= 0) { hipMemset(*p, poison_byte(4), sizeof(T) * std::max<size_t>(n, 1)); hipDeviceSynchronize(); }
     return TWOSD_OK;
 }
 
@@ -1716,7 +1684,7 @@ static int update_pk(twosd_ctx *c) {
     const int nv = c->dvs.size, k = c->k, k4 = (std::max(k, 1) + 3) & ~3, m = c->L.m;
     int rc;
     if (!w->rows || w->pk_k4 != k4 || w->m != m) {
-        if ((rc = realloc_dev(&w->rows, std::max(k, 1))) || (rc = realloc_dev(&w->eord, std::max(k, 1)))) return rc;
+        if ((rc = w->rows.alloc(std::max(k, 1))) || (rc = w->eord.alloc(std::max(k, 1)))) return rc;
         if (k) HIPCHK(hipMemcpy(w->rows, c->pos_row.data(), sizeof(int) * k, hipMemcpyHostToDevice));
         // the restated score's element order: ascending row (the dense dot over the m rows), element
         // order within a row
@@ -1730,9 +1698,9 @@ static int update_pk(twosd_ctx *c) {
     }
     if (nv > w->pk_vcap) {
         const int vcap = std::max(nv, 2 * w->pk_vcap + 256);
-        if ((rc = realloc_dev(&w->PK, (size_t)vcap * k4)) || (rc = realloc_dev(&w->PKT, (size_t)vcap * k4)) ||
-            (rc = realloc_dev(&w->PKO, (size_t)vcap * k4)) || (rc = realloc_dev(&w->phash, vcap)) ||
-            (rc = realloc_dev(&w->tprev, vcap)))
+        if ((rc = w->PK.alloc((size_t)vcap * k4)) || (rc = w->PKT.alloc((size_t)vcap * k4)) ||
+            (rc = w->PKO.alloc((size_t)vcap * k4)) || (rc = w->phash.alloc(vcap)) ||
+            (rc = w->tprev.alloc(vcap)))
             return rc;
         w->pk_vcap = vcap;
         w->pk_count = 0;
@@ -1750,23 +1718,13 @@ static int update_pk(twosd_ctx *c) {
             hipLaunchKernelGGL(cut_twin_prev_kernel, dim3((nn + 3) / 4), dim3(256), 0, c->stream, w->pk_count, nv, k4, w->PK,
                                w->phash, w->tprev);
         } else {                                             // a rebuild: sort every vertex by hash
-            if ((size_t)nv > w->tw_cap) {
-                hipFree(w->tw_hs); hipFree(w->tw_vin); hipFree(w->tw_vout);
-                w->tw_hs = nullptr; w->tw_vin = w->tw_vout = nullptr;
-                if ((rc = realloc_dev(&w->tw_hs, nv)) || (rc = realloc_dev(&w->tw_vin, nv)) || (rc = realloc_dev(&w->tw_vout, nv))) return rc;
-                w->tw_cap = nv;
-            }
+            if ((rc = w->tw_hs.fit(nv)) || (rc = w->tw_vin.fit(nv)) || (rc = w->tw_vout.fit(nv))) return rc;
             size_t need = 0;
-            HIPCHK(hipcub::DeviceRadixSort::SortPairs(nullptr, need, w->phash, w->tw_hs, w->tw_vin, w->tw_vout, nv, 0, 64, c->stream));
-            if (need > w->tw_tmp_bytes) {
-                hipFree(w->tw_tmp);
-                w->tw_tmp = nullptr;
-                HIPCHK(hipMalloc(&w->tw_tmp, need));
-                w->tw_tmp_bytes = need;
-            }
+            HIPCHK(hipcub::DeviceRadixSort::SortPairs(nullptr, need, w->phash.p, w->tw_hs.p, w->tw_vin.p, w->tw_vout.p, nv, 0, 64, c->stream));
+            if ((rc = w->tw_tmp.fit(need))) return rc;
             hipLaunchKernelGGL(cut_iota_kernel, dim3((nv + 255) / 256), dim3(256), 0, c->stream, w->tw_vin, nv);
             // (the earlier vertices' hashes are kept in phash; only the new ones were hashed above)
-            HIPCHK(hipcub::DeviceRadixSort::SortPairs(w->tw_tmp, need, w->phash, w->tw_hs, w->tw_vin, w->tw_vout, nv, 0, 64,
+            HIPCHK(hipcub::DeviceRadixSort::SortPairs(w->tw_tmp.p, need, w->phash.p, w->tw_hs.p, w->tw_vin.p, w->tw_vout.p, nv, 0, 64,
                                                       c->stream));
             hipLaunchKernelGGL(cut_twin_sorted_kernel, dim3((nv + 255) / 256), dim3(256), 0, c->stream, nv, k4, w->PK, w->tw_hs,
                                w->tw_vout, w->tprev);
@@ -1810,17 +1768,11 @@ static int cut_partial_impl(twosd_ctx *c, int epi, const double *x, double tie_r
     }
     for (int e = 0; e < k; ++e) coef[e] = c->pos_col[e] < 0 ? 1.0 : -x[c->pos_col[e]];
     if (!w->coef || !w->bvec || !w->g || w->vec_m != m) {
-        if ((rc = realloc_dev(&w->coef, 256)) || (rc = realloc_dev(&w->bvec, m)) || (rc = realloc_dev(&w->g, m))) return rc;
+        if ((rc = w->coef.alloc(256)) || (rc = w->bvec.alloc(m)) || (rc = w->g.alloc(m))) return rc;
         w->vec_m = m;
     }
-    if ((size_t)nv > w->base_cap) {
-        if ((rc = realloc_dev(&w->base, nv))) return rc;
-        w->base_cap = nv;
-    }
-    if ((size_t)N > w->n_cap) {
-        if ((rc = realloc_dev(&w->arg, N)) || (rc = realloc_dev(&w->val, N)) || (rc = realloc_dev(&w->flag, N))) return rc;
-        w->n_cap = N;
-    }
+    if ((rc = w->base.fit(nv))) return rc;
+    if ((rc = w->arg.fit(N)) || (rc = w->val.fit(N)) || (rc = w->flag.fit(N))) return rc;
     HIPCHK(hipMemcpyAsync(w->coef, coef.data(), sizeof(double) * k4, hipMemcpyHostToDevice, c->stream));
     HIPCHK(hipMemcpyAsync(w->bvec, bvec.data(), sizeof(double) * m, hipMemcpyHostToDevice, c->stream));
     const int ntiles = (N + kCutTile2 - 1) / kCutTile2;
@@ -1863,12 +1815,8 @@ static int cut_partial_impl(twosd_ctx *c, int epi, const double *x, double tie_r
     const int merge_blocks = ntail > 0 ? std::max(1, std::min((ntail + 3) / 4, c->num_cus)) : 0;
     const int resc_blocks = std::max(1, std::min((N + 255) / 256, c->num_cus));
     const size_t slots = (size_t)nblocks * 4 + (size_t)fix_blocks * 4 + (size_t)merge_blocks * 4 + (size_t)resc_blocks * 4;
-    if ((size_t)ntail * S > w->tp_cap) {
-        if ((rc = realloc_dev(&w->tp_m, (size_t)ntail * S)) || (rc = realloc_dev(&w->tp_i, (size_t)ntail * S)) ||
-            (rc = realloc_dev(&w->tp_f, (size_t)ntail * S)))
-            return rc;
-        w->tp_cap = (size_t)ntail * S;
-    }
+    if ((rc = w->tp_m.fit((size_t)ntail * S)) || (rc = w->tp_i.fit((size_t)ntail * S)) || (rc = w->tp_f.fit((size_t)ntail * S)))
+        return rc;
     // candidate logs: rows padded to whole tiles (the padding scenarios of a tile log too)
     const size_t cand_need = (size_t)full * kCutTile2 * 4 * kCandC;
     const size_t tcand_need = (size_t)(ntiles - full) * kCutTile2 * S * 4 * kCandC;
@@ -1881,21 +1829,15 @@ static int cut_partial_impl(twosd_ctx *c, int epi, const double *x, double tie_r
             return fail(TWOSD_E_UNSUPPORTED, "cut: %d scenarios need %zu candidate-log slots (32-bit offsets: at most %zu)", N,
                         std::max(cand_need, tcand_need), log_max);
     }
-    if (cand_need > w->cand_cap) {
-        if ((rc = realloc_dev(&w->cand, cand_need))) return rc;
-        w->cand_cap = cand_need;
-    }
-    if (tcand_need > w->tcand_cap) {
-        if ((rc = realloc_dev(&w->tcand, tcand_need))) return rc;
-        w->tcand_cap = tcand_need;
-    }
+    if ((rc = w->cand.fit(cand_need))) return rc;
+    if ((rc = w->tcand.fit(tcand_need))) return rc;
     // band_bits: [0] fp64 band, [1] fp32 band, [2] fp32 operands out of range, [3] the active band, [4] the pass
-    if (!w->band_bits && (rc = realloc_dev(&w->band_bits, 8))) return rc;
-    if (!w->fstats && (rc = realloc_dev(&w->fstats, 16))) return rc;
+    if (!w->band_bits && (rc = w->band_bits.alloc(8))) return rc;
+    if (!w->fstats && (rc = w->fstats.alloc(16))) return rc;
     HIPCHK(hipMemsetAsync(w->fstats, 0, sizeof(unsigned long long) * 16, c->stream));
     // the epigraph's max |dv| per element, folded in for the rows added since the last cut
     if ((int)w->dmax.size() <= epi) {
-        w->dmax.resize(epi + 1, nullptr);
+        w->dmax.resize(epi + 1);
         w->dmax_rows.resize(epi + 1, 0);
         w->dmax_k.resize(epi + 1, -1);
     }
@@ -1905,7 +1847,7 @@ static int cut_partial_impl(twosd_ctx *c, int epi, const double *x, double tie_r
     // mean the rows were replaced: fold everything in again (a too-small dmax would narrow the
     // decision band and mark near-tied rows decided without a fixup).
     if (w->dmax_k[epi] != k || w->dmax_rows[epi] > N) {
-        if ((rc = realloc_dev(&w->dmax[epi], std::max(k, 1)))) return rc;
+        if ((rc = w->dmax[epi].alloc(std::max(k, 1)))) return rc;
         HIPCHK(hipMemsetAsync(w->dmax[epi], 0, sizeof(unsigned long long) * std::max(k, 1), c->stream));
         w->dmax_k[epi] = k;
         w->dmax_rows[epi] = 0;
@@ -1916,10 +1858,7 @@ static int cut_partial_impl(twosd_ctx *c, int epi, const double *x, double tie_r
                            E.d_dv, w->dmax[epi]);
         w->dmax_rows[epi] = N;
     }
-    if (slots * (k + 1) > w->part_cap) {
-        if ((rc = realloc_dev(&w->partial, slots * (k + 1)))) return rc;
-        w->part_cap = slots * (k + 1);
-    }
+    if ((rc = w->partial.fit(slots * (k + 1)))) return rc;
     HIPCHK(hipMemsetAsync(d_hist, 0, sizeof(unsigned long long) * std::max(nv, 1), c->stream));
     HIPCHK(hipMemsetAsync(w->band_bits, 0, sizeof(unsigned long long) * 8, c->stream));
     // band: the MFMA score and the restated one both add base[v] to a (k + 1)-term dot and differ
@@ -1939,10 +1878,7 @@ static int cut_partial_impl(twosd_ctx *c, int epi, const double *x, double tie_r
     P.N = N; P.k = k; P.k4 = k4; P.nv = nv; P.vcap = w->pk_vcap; P.m = m;
     static const int hist_lds_max = getenv("TWOSD_HIST_LDS") ? atoi(getenv("TWOSD_HIST_LDS")) : kHistLds;
     P.hist_lds = nv <= hist_lds_max ? 1 : 0;
-    if (P.hist_lds && (size_t)nblocks * nv > w->hpart_cap) {
-        if ((rc = realloc_dev(&w->hist_part, (size_t)nblocks * nv))) return rc;
-        w->hpart_cap = (size_t)nblocks * nv;
-    }
+    if (P.hist_lds && (rc = w->hist_part.fit((size_t)nblocks * nv))) return rc;
     P.hist_part = w->hist_part;
     P.tie_rel = tie_rel; P.inv_total = 1.0 / total_weight;
     P.band_bits = w->band_bits + 3;
@@ -1954,30 +1890,15 @@ static int cut_partial_impl(twosd_ctx *c, int epi, const double *x, double tie_r
         // same picks; more re-decided rows)
         const bool twins = !getenv("TWOSD_CUT_TWINS") || atoi(getenv("TWOSD_CUT_TWINS")) != 0;
         const int vcap32 = (nv + 31) & ~31, rows = 4 * KB;
-        if ((size_t)rows * vcap32 > w->pktc_cap) {
-            if ((rc = realloc_dev(&w->PKTc, (size_t)rows * vcap32))) return rc;
-            w->pktc_cap = (size_t)rows * vcap32;
-        }
-        if ((size_t)nv > w->vmap_cap) {
-            if ((rc = realloc_dev(&w->vmap, nv))) return rc;
-            w->vmap_cap = nv;
-        }
-        if (!w->nvc && (rc = realloc_dev(&w->nvc, 1))) return rc;
-        if ((size_t)nv > w->pkoc_cap) {
-            if ((rc = realloc_dev(&w->PKOc, (size_t)nv * k4)) || (rc = realloc_dev(&w->basec, (size_t)vcap32))) return rc;
-            w->pkoc_cap = nv;
-        }
+        if ((rc = w->PKTc.fit((size_t)rows * vcap32))) return rc;
+        if ((rc = w->vmap.fit(nv))) return rc;
+        if (!w->nvc && (rc = w->nvc.alloc(1))) return rc;
+        if ((size_t)nv * k4 > w->PKOc.cap && ((rc = w->PKOc.alloc((size_t)nv * k4)) || (rc = w->basec.alloc((size_t)vcap32)))) return rc;
         hipLaunchKernelGGL(cut_compact_kernel, dim3(1), dim3(1024), 0, c->stream, nv, w->base, twins ? w->tprev : nullptr, w->vmap,
                            w->nvc, w->fstats + 9);
         const int rows32 = want32 ? kr32(KB32) : 0;
-        if (want32 && (size_t)rows32 * vcap32 > w->pktc32_cap) {
-            if ((rc = realloc_dev(&w->PKTc32, (size_t)rows32 * vcap32))) return rc;
-            w->pktc32_cap = (size_t)rows32 * vcap32;
-        }
-        if (want32 && (size_t)vcap32 > w->basec32_cap) {
-            if ((rc = realloc_dev(&w->basec32, (size_t)vcap32))) return rc;
-            w->basec32_cap = vcap32;
-        }
+        if (want32 && (rc = w->PKTc32.fit((size_t)rows32 * vcap32))) return rc;
+        if (want32 && (rc = w->basec32.fit((size_t)vcap32))) return rc;
         const size_t tot2 = (size_t)std::max(rows, rows32) * vcap32;
         hipLaunchKernelGGL(cut_pktc_kernel, dim3((unsigned)std::min<size_t>(4096, (tot2 + 255) / 256)), dim3(256), 0, c->stream, k,
                            rows, w->pk_vcap, vcap32, w->PKT, w->coef, w->base, w->vmap, w->nvc, w->PKTc, rows32,
@@ -2007,10 +1928,7 @@ static int cut_partial_impl(twosd_ctx *c, int epi, const double *x, double tie_r
     hipLaunchKernelGGL(cut_fixup_kernel, dim3(fix_blocks), dim3(256), 0, c->stream, P, nblocks * 4);
     hipLaunchKernelGGL(cut_rescan_kernel, dim3(resc_blocks), dim3(256), 0, c->stream, P,
                        nblocks * 4 + fix_blocks * 4 + merge_blocks * 4);
-    if ((size_t)(k + 1) * kReduceBlocks > w->part2_cap) {
-        if ((rc = realloc_dev(&w->part2, (size_t)(k + 1) * kReduceBlocks))) return rc;
-        w->part2_cap = (size_t)(k + 1) * kReduceBlocks;
-    }
+    if ((rc = w->part2.fit((size_t)(k + 1) * kReduceBlocks))) return rc;
     hipLaunchKernelGGL(cut_reduce1_kernel, dim3(kReduceBlocks, k + 1), dim3(256), 0, c->stream, (int)slots, k + 1,
                        w->partial, w->part2);
     hipLaunchKernelGGL(cut_reduce2_kernel, dim3((k + 1 + 63) / 64), dim3(64), 0, c->stream, k + 1, w->part2, d_sums);
@@ -2028,10 +1946,7 @@ static int cut_finalize_impl(twosd_ctx *c, const double *x, const unsigned long 
     const int chunk = std::max(32, (nv + 511) / 512);
     const int nb = std::max(1, (nv + chunk - 1) / chunk);
     int rc;
-    if ((size_t)nb * m > w->gpart_cap) {
-        if ((rc = realloc_dev(&w->gpart, (size_t)nb * m))) return rc;
-        w->gpart_cap = (size_t)nb * m;
-    }
+    if ((rc = w->gpart.fit((size_t)nb * m))) return rc;
     hipLaunchKernelGGL(cut_g_partial_kernel, dim3(nb), dim3(256), 0, c->stream, nv, m, chunk, d_hist, c->dvs.V, w->gpart);
     hipLaunchKernelGGL(cut_g_final_kernel, dim3((m + 255) / 256), dim3(256), 0, c->stream, nb, m, w->gpart, w->g);
     HIPCHK(hipGetLastError());
@@ -2078,14 +1993,8 @@ extern "C" int twosd_build_cut(twosd_ctx *c, int epi, const double *x, double ti
     const EpiDevice &E = c->epis[epi];
     CutWs *w = cws(c);
     const int nv = c->dvs.size;
-    if ((size_t)nv > w->hist_cap) {
-        if ((rc = realloc_dev(&w->hist, nv))) return rc;
-        w->hist_cap = nv;
-    }
-    if ((size_t)(c->k + 1) > w->sums_cap) {
-        if ((rc = realloc_dev(&w->sums, c->k + 1))) return rc;
-        w->sums_cap = c->k + 1;
-    }
+    if ((rc = w->hist.fit(nv))) return rc;
+    if ((rc = w->sums.fit(c->k + 1))) return rc;
     if (E.count == 0 || E.total_weight <= 0.0) {
         // no scenarios: the reference returns the zero cut with weight_mark = total weight
         *alpha = 0.0;
@@ -2115,7 +2024,7 @@ extern "C" int twosd_build_cut(twosd_ctx *c, int epi, const double *x, double ti
 extern "C" int twosd_cut_stats(twosd_ctx *c, int64_t *out) {
     if (!c || !out) return fail(TWOSD_E_ARG, "cut_stats: NULL");
     for (int i = 0; i < 4; ++i) out[i] = 0;
-    CutWs *w = c->cut_ws ? (CutWs *)c->cut_ws : nullptr;
+    CutWs *w = c->cut_ws.get();
     if (!w || !w->fstats) return TWOSD_OK;
     unsigned long long h[16] = {};
     HIPCHK(hipSetDevice(c->device));
@@ -2135,7 +2044,7 @@ extern "C" int twosd_cut_pass(twosd_ctx *c, int *fp32, double *band) {
     if (!c || !fp32) return fail(TWOSD_E_ARG, "cut_pass: NULL");
     *fp32 = 0;
     if (band) *band = 0.0;
-    CutWs *w = c->cut_ws ? (CutWs *)c->cut_ws : nullptr;
+    CutWs *w = c->cut_ws.get();
     if (!w || !w->band_bits) return TWOSD_OK;
     unsigned long long h[8] = {};
     HIPCHK(hipSetDevice(c->device));

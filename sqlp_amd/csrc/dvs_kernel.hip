@@ -196,47 +196,33 @@ __global__ void dvs_fill_kernel(int *p, int n, int v) {
 }
 
 // ---------------------------------------------------------------------------------
+template <typename T>
+using WsBuf = DevBuf<T, 8>;
 struct DvsWs {
-    uint64_t *chash = nullptr, *cfp = nullptr;
-    int *nanflag = nullptr, *out = nullptr, *slot = nullptr, *isnew = nullptr, *scan = nullptr, *tt = nullptr;
-    size_t ccap = 0, ttcap = 0;
-    void *cub_tmp = nullptr;
-    size_t cub_bytes = 0;
-    double *pis = nullptr;        // staging for host-provided candidates
-    size_t pis_cap = 0;
-    int *nanhost = nullptr;
+    WsBuf<uint64_t> chash, cfp;   // per candidate, sized together: chash.cap candidates
+    WsBuf<int> nanflag, out, slot, isnew, scan;
+    WsBuf<int> tt;                // batch table: tt.cap slots (a power of two)
+    WsBuf<char> cub_tmp;          // hipcub scratch
+    WsBuf<double> pis;            // staging for host-provided candidates
 };
 
 static DvsWs *ws_of(twosd_ctx *c) {
-    if (!c->dvs_ws) c->dvs_ws = new DvsWs();
-    return (DvsWs *)c->dvs_ws;
+    if (!c->dvs_ws) c->dvs_ws.reset(new DvsWs());
+    return c->dvs_ws.get();
 }
 
 static int nblocks_for(int count) { return std::max(1, std::min((count + 3) / 4, 8192)); }
 
 int dvs_init(twosd_ctx *c) {
-    dvs_free(c);
+    c->dvs = DvsDevice();
+    c->dvs_ws.reset();
     c->dvs.m = c->L.m;
     c->dvs.size = 0;
     cut_truncate_pk(c, 0);
     return TWOSD_OK;
 }
 
-void dvs_free(twosd_ctx *c) {
-    DvsDevice &D = c->dvs;
-    if (D.V) hipFree(D.V);
-    if (D.hash) hipFree(D.hash);
-    if (D.fp) hipFree(D.fp);
-    if (D.table) hipFree(D.table);
-    D = DvsDevice();
-    if (c->dvs_ws) {
-        DvsWs *w = (DvsWs *)c->dvs_ws;
-        hipFree(w->chash); hipFree(w->cfp); hipFree(w->nanflag); hipFree(w->out); hipFree(w->slot);
-        hipFree(w->isnew); hipFree(w->scan); hipFree(w->tt); hipFree(w->cub_tmp); hipFree(w->pis);
-        delete w;
-        c->dvs_ws = nullptr;
-    }
-}
+void dvs_free(DvsWs *w) { delete w; }
 
 #define HIPCHK(expr)                                                                               \
     do {                                                                                           \
@@ -249,20 +235,17 @@ static int ensure_capacity(twosd_ctx *c, int need) {
     const int m = D.m;
     if (need > D.cap) {
         size_t ncap = std::max<size_t>((size_t)need, (size_t)D.cap * 2 + 256);
-        size_t cap = D.cap;
         int rc;
-        size_t c1 = cap, c2 = cap, c3 = cap;
-        if ((rc = dgrow(&D.V, &c1, ncap * m, (size_t)D.size * m, c->stream))) return rc;
-        if ((rc = dgrow(&D.hash, &c2, ncap, (size_t)D.size, c->stream))) return rc;
-        if ((rc = dgrow(&D.fp, &c3, ncap, (size_t)D.size, c->stream))) return rc;
+        if ((rc = D.V.regrow(ncap * m, (size_t)D.size * m, c->stream))) return rc;
+        if ((rc = D.hash.regrow(ncap, (size_t)D.size, c->stream))) return rc;
+        if ((rc = D.fp.regrow(ncap, (size_t)D.size, c->stream))) return rc;
         D.cap = (int)ncap;
     }
     // table load factor <= 1/2
     if ((size_t)D.tcap < 2 * (size_t)need || !D.table) {
         int tc = 1024;
         while ((size_t)tc < 2 * (size_t)need) tc <<= 1;
-        if (D.table) hipFree(D.table);
-        HIPCHK(hipMalloc(&D.table, sizeof(int) * tc));
+        if (int rc = D.table.alloc(tc)) return rc;
         D.tcap = tc;
         hipLaunchKernelGGL(dvs_fill_kernel, dim3((tc + 255) / 256), dim3(256), 0, c->stream, D.table, tc, -1);
         if (D.size)
@@ -270,15 +253,6 @@ static int ensure_capacity(twosd_ctx *c, int need) {
                                D.table, tc - 1);
         HIPCHK(hipGetLastError());
     }
-    return TWOSD_OK;
-}
-
-template <typename T>
-static int ws_grow(T **p, size_t need) {
-    if (*p) hipFree(*p);
-    *p = nullptr;
-    hipError_t e = hipMalloc((void **)p, sizeof(T) * std::max<size_t>(need, 1));
-    if (e != hipSuccess) return fail(TWOSD_E_DEVICE, "dvs workspace hipMalloc: %s", hipGetErrorString(e));
     return TWOSD_OK;
 }
 
@@ -291,31 +265,22 @@ int dvs_push_device(twosd_ctx *c, int count, const double *d_pis, int *d_out_ind
     DvsWs *w = ws_of(c);
     const int m = D.m;
     int rc;
-    if ((size_t)count > w->ccap) {
+    if ((size_t)count > w->scan.cap) {   // scan is the last of the seven: all are sized, or none counts
         size_t cc = std::max<size_t>(count, 1024);
-        if ((rc = ws_grow(&w->chash, cc)) || (rc = ws_grow(&w->cfp, cc)) || (rc = ws_grow(&w->nanflag, cc)) ||
-            (rc = ws_grow(&w->out, cc)) || (rc = ws_grow(&w->slot, cc)) || (rc = ws_grow(&w->isnew, cc)) ||
-            (rc = ws_grow(&w->scan, cc)))
+        if ((rc = w->chash.alloc(cc)) || (rc = w->cfp.alloc(cc)) || (rc = w->nanflag.alloc(cc)) || (rc = w->out.alloc(cc)) ||
+            (rc = w->slot.alloc(cc)) || (rc = w->isnew.alloc(cc)) || (rc = w->scan.alloc(cc)))
             return rc;
-        w->ccap = cc;
         size_t need = 0;
-        hipcub::DeviceScan::ExclusiveSum(nullptr, need, w->isnew, w->scan, (int)cc, c->stream);
-        if (need > w->cub_bytes) {
-            if (w->cub_tmp) hipFree(w->cub_tmp);
-            HIPCHK(hipMalloc(&w->cub_tmp, need));
-            w->cub_bytes = need;
-        }
+        hipcub::DeviceScan::ExclusiveSum(nullptr, need, w->isnew.p, w->scan.p, (int)cc, c->stream);
+        if ((rc = w->cub_tmp.fit(need))) return rc;
     }
     size_t ttneed = 1024;
     while (ttneed < 2 * (size_t)count) ttneed <<= 1;
-    if (ttneed > w->ttcap) {
-        if ((rc = ws_grow(&w->tt, ttneed))) return rc;
-        w->ttcap = ttneed;
-    }
+    if ((rc = w->tt.fit(ttneed))) return rc;
     if ((rc = ensure_capacity(c, D.size + count))) return rc;
-    const int ttmask = (int)w->ttcap - 1;
+    const int ttmask = (int)w->tt.cap - 1;
     const int nb = nblocks_for(count);
-    hipLaunchKernelGGL(dvs_fill_kernel, dim3((w->ttcap + 255) / 256), dim3(256), 0, c->stream, w->tt, (int)w->ttcap, -1);
+    hipLaunchKernelGGL(dvs_fill_kernel, dim3((w->tt.cap + 255) / 256), dim3(256), 0, c->stream, w->tt, (int)w->tt.cap, -1);
     if (d_hash) {   // keys computed by the producer (LP kernel epilogue)
         HIPCHK(hipMemcpyAsync(w->chash, d_hash, sizeof(uint64_t) * count, hipMemcpyDeviceToDevice, c->stream));
         HIPCHK(hipMemcpyAsync(w->cfp, d_fp, sizeof(uint64_t) * count, hipMemcpyDeviceToDevice, c->stream));
@@ -330,8 +295,8 @@ int dvs_push_device(twosd_ctx *c, int count, const double *d_pis, int *d_out_ind
                        w->nanflag, w->out, w->tt, ttmask, w->slot);
     hipLaunchKernelGGL(dvs_flag_kernel, dim3((count + 255) / 256), dim3(256), 0, c->stream, count, w->out, w->nanflag,
                        w->tt, w->slot, w->isnew);
-    size_t tb = w->cub_bytes;
-    HIPCHK(hipcub::DeviceScan::ExclusiveSum(w->cub_tmp, tb, w->isnew, w->scan, count, c->stream));
+    size_t tb = w->cub_tmp.cap;
+    HIPCHK(hipcub::DeviceScan::ExclusiveSum(w->cub_tmp.p, tb, w->isnew.p, w->scan.p, count, c->stream));
     hipLaunchKernelGGL(dvs_assign_kernel, dim3(nb), dim3(256), 0, c->stream, count, m, D.size, d_pis, w->chash, w->cfp,
                        w->nanflag, w->tt, w->slot, w->scan, w->out, D.V, D.hash, D.fp, D.table, D.tcap - 1);
     HIPCHK(hipGetLastError());
@@ -356,11 +321,7 @@ extern "C" int twosd_dvs_push(twosd_ctx *c, int count, const double *pis, int *o
     if (count > 0) {
         DvsWs *w = ws_of(c);
         const size_t need = (size_t)count * c->dvs.m;
-        if (need > w->pis_cap) {
-            int rc = ws_grow(&w->pis, need);
-            if (rc) return rc;
-            w->pis_cap = need;
-        }
+        if (int rc = w->pis.fit(need)) return rc;
         HIPCHK(hipMemcpy(w->pis, pis, sizeof(double) * need, hipMemcpyHostToDevice));
         hipEvent_t e0 = c->ev[2], e1 = c->ev[3];
         HIPCHK(hipEventRecord(e0, c->stream));

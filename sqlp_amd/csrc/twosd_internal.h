@@ -5,6 +5,7 @@
 #include <string>
 #include <vector>
 #include "twosd_hip.h"
+#include "devbuf.h"
 
 namespace twosd {
 
@@ -222,12 +223,13 @@ double sparse_basis_residual(const HostLP &L, const std::vector<int> &head, cons
 
 // ---- dual vertex set kernels (dvs_kernel.hip) ------------------------------------
 struct DvsDevice {
-    int m = 0, cap = 0, size = 0;
-    double *V = nullptr;          // cap x m
-    uint64_t *hash = nullptr;     // cap: reference hash (bits of round16(L1 norm))
-    uint64_t *fp = nullptr;       // cap: fingerprint of (hash, rounded components)
-    int *table = nullptr;         // tcap slots: vertex id or -1
-    int tcap = 0;                 // power of two
+    int m = 0, size = 0;
+    int cap = 0;                  // vertices V, hash and fp hold
+    DevBuf<double> V;             // cap x m
+    DevBuf<uint64_t> hash;        // cap: reference hash (bits of round16(L1 norm))
+    DevBuf<uint64_t> fp;          // cap: fingerprint of (hash, rounded components)
+    DevBuf<int, 8> table;         // tcap slots: vertex id or -1
+    int tcap = 0;                 // slots in use of table: a power of two
 };
 
 // ---- cut kernels (cut_kernel.hip) --------------------------------------------------

@@ -112,30 +112,23 @@ __global__ void vkey_flag_kernel(int N, const unsigned long long *__restrict__ v
     }
 }
 
+template <typename T>
+using WsBuf = DevBuf<T, 8>;
 struct VkeyWs {
-    unsigned long long *keys = nullptr;
-    int *first = nullptr, *cnt = nullptr, *counts = nullptr;
-    unsigned cap = 0;
-    char *flag = nullptr;
-    int *list = nullptr, *nsel = nullptr;
-    size_t ncap = 0;
-    void *tmp = nullptr;
-    size_t tmp_bytes = 0;
+    WsBuf<unsigned long long> keys;        // the table: cap slots (a power of two)
+    WsBuf<int> first, cnt;
+    unsigned cap = 0;                      // slots of keys / first / cnt
+    WsBuf<char> flag;                      // per scenario (the batch size they were last sized for: flag.cap)
+    WsBuf<int> list, counts, nsel;
+    WsBuf<char> tmp;                       // hipcub scratch
 };
 
 static VkeyWs *vws(twosd_ctx *c) {
-    if (!c->vkey_ws) c->vkey_ws = new VkeyWs();
-    return static_cast<VkeyWs *>(c->vkey_ws);
+    if (!c->vkey_ws) c->vkey_ws.reset(new VkeyWs());
+    return c->vkey_ws.get();
 }
 
-void vkey_free(twosd_ctx *c) {
-    VkeyWs *w = static_cast<VkeyWs *>(c->vkey_ws);
-    if (!w) return;
-    hipFree(w->keys); hipFree(w->first); hipFree(w->cnt); hipFree(w->counts); hipFree(w->flag); hipFree(w->list);
-    hipFree(w->nsel); hipFree(w->tmp);
-    delete w;
-    c->vkey_ws = nullptr;
-}
+void vkey_free(VkeyWs *w) { delete w; }
 
 // representatives (first scenario of every distinct key among the optimal scenarios of
 // [0, N)), ascending, into *d_list; their number into *U (host); d_counts (nullable): the
@@ -145,32 +138,18 @@ int vkey_first_occurrences(twosd_ctx *c, int N, const unsigned long long *d_vkey
     VkeyWs *w = vws(c);
     unsigned cap = 1024;
     while (cap < 2u * (unsigned)N) cap <<= 1;
+    int rc;
     if (cap > w->cap) {
-        hipFree(w->keys); hipFree(w->first); hipFree(w->cnt);
-        w->keys = nullptr; w->first = nullptr; w->cnt = nullptr; w->cap = 0;
-        HIPCHK(hipMalloc(&w->keys, sizeof(unsigned long long) * cap));
-        HIPCHK(hipMalloc(&w->first, sizeof(int) * cap));
-        HIPCHK(hipMalloc(&w->cnt, sizeof(int) * cap));
+        w->cap = 0;
+        if ((rc = w->keys.alloc(cap)) || (rc = w->first.alloc(cap)) || (rc = w->cnt.alloc(cap))) return rc;
         w->cap = cap;
     }
-    if ((size_t)N > w->ncap) {
-        hipFree(w->flag); hipFree(w->list); hipFree(w->counts);
-        w->flag = nullptr; w->list = nullptr; w->counts = nullptr; w->ncap = 0;
-        HIPCHK(hipMalloc(&w->flag, (size_t)N));
-        HIPCHK(hipMalloc(&w->list, sizeof(int) * (size_t)N));
-        HIPCHK(hipMalloc(&w->counts, sizeof(int) * (size_t)N));
-        w->ncap = N;
-    }
-    if (!w->nsel) HIPCHK(hipMalloc(&w->nsel, sizeof(int)));
+    if ((rc = w->flag.fit((size_t)N)) || (rc = w->list.fit((size_t)N)) || (rc = w->counts.fit((size_t)N))) return rc;
+    if (!w->nsel && (rc = w->nsel.alloc(1))) return rc;
     size_t need = 0;
-    HIPCHK(hipcub::DeviceSelect::Flagged(nullptr, need, hipcub::CountingInputIterator<int>(0), w->flag, w->list, w->nsel, N,
+    HIPCHK(hipcub::DeviceSelect::Flagged(nullptr, need, hipcub::CountingInputIterator<int>(0), w->flag.p, w->list.p, w->nsel.p, N,
                                          c->stream));
-    if (need > w->tmp_bytes) {
-        hipFree(w->tmp);
-        w->tmp = nullptr; w->tmp_bytes = 0;
-        HIPCHK(hipMalloc(&w->tmp, need));
-        w->tmp_bytes = need;
-    }
+    if ((rc = w->tmp.fit(need))) return rc;
     const unsigned mask = w->cap - 1;
     const int nb = std::max(1, std::min(4096, (N + 255) / 256));
     hipLaunchKernelGGL(vkey_clear_kernel, dim3(std::min(4096u, (w->cap + 255) / 256)), dim3(256), 0, c->stream, w->keys, w->first,
@@ -180,7 +159,7 @@ int vkey_first_occurrences(twosd_ctx *c, int N, const unsigned long long *d_vkey
     hipLaunchKernelGGL(vkey_flag_kernel, dim3(nb), dim3(256), 0, c->stream, N, d_vkey, d_status, w->keys, w->first, mask,
                        w->flag);
     HIPCHK(hipGetLastError());
-    HIPCHK(hipcub::DeviceSelect::Flagged(w->tmp, need, hipcub::CountingInputIterator<int>(0), w->flag, w->list, w->nsel, N,
+    HIPCHK(hipcub::DeviceSelect::Flagged(w->tmp.p, need, hipcub::CountingInputIterator<int>(0), w->flag.p, w->list.p, w->nsel.p, N,
                                          c->stream));
     HIPCHK(hipMemcpyAsync(U, w->nsel, sizeof(int), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));

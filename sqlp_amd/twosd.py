@@ -114,6 +114,11 @@ class SDContext:
         h = C.c_void_p()
         check(self.lib.twosd_create(device, C.byref(h)))
         self.h = h
+        self._set_problem(sp2, sto, positions)
+
+    def _set_problem(self, sp2: spStageProblem, sto=None, positions=None):
+        """Template and random-element layout of this handle (twosd_set_template clears the
+        basis, scenarios, dual vertex set and cuts of an earlier one)."""
         self.sp2 = sp2
         self.m, self.n1, self.n2 = sp2.shape
         Tcp, Trv, Tnz = sp2.T
