@@ -409,6 +409,83 @@ int twosd_cut_partial(twosd_ctx *ctx, int epi, const double *x, double tie_rel, 
 int twosd_cut_finalize(twosd_ctx *ctx, const double *x, const uint64_t *d_hist_u64, const double *d_sums_f64,
                        double *alpha, double *beta);
 
+/*
+ * Stored picks (no reference counterpart: the reference's readme lists "Need to implement
+ * stopping criteria" and src/sd_algorithm/plugin/stopping_rule.jl is an empty file).  With its
+ * argmax picks fixed, a cut is a linear function of the scenario weights, so the in-sample
+ * stopping rule of SD re-forms cuts under resampled weights without repeating the argmax.
+ *   picks_keep: snapshot the picks of the last twosd_build_cut / twosd_cut_partial of epigraph epi
+ *     (a device-to-device copy on the context's stream, no host round trip) with the scenario
+ *     count n and |V| = nv of that cut.  A handle costs 4 bytes per scenario of device memory.
+ *     TWOSD_E_STATE if the last cut call was not for epi, took the empty-epigraph path, or the
+ *     template, the positions or the vertex set were reset since.
+ *   picks_info / picks_get (out[n], 0-based vertex indices) / picks_release; picks_count: live handles.
+ * twosd_set_template, twosd_set_random_positions and twosd_destroy drop every handle.  After
+ * twosd_dvs_clear / twosd_dvs_truncate a handle whose nv exceeds the new size is unusable
+ * (TWOSD_E_STATE on use; release it).  Scenario rows are append-only, so a handle stays valid while
+ * its epigraph grows: it covers the first n scenarios.
+ */
+int twosd_picks_keep(twosd_ctx *ctx, int epi, int *handle);
+int twosd_picks_info(twosd_ctx *ctx, int handle, int *epi, int *n, int *nv);
+int twosd_picks_get(twosd_ctx *ctx, int handle, int *out);
+int twosd_picks_release(twosd_ctx *ctx, int handle);
+int twosd_picks_count(twosd_ctx *ctx, int *live);
+
+/*
+ * Bootstrap replicate counts (no reference counterpart: plugin/stopping_rule.jl is empty).
+ * Replicate b (0 <= b < M) gives the scenario with global index g (as in the sampler) the count
+ * c_b(g), an independent Poisson(1) draw and a pure function of (seed, g, b): Philox4x32-10 with
+ * counter (g_lo, g_hi, b >> 2, 1) and key (seed_lo, seed_hi) -- the last counter word keeps the
+ * stream apart from the scenario stream, which uses 0 -- whose output word b & 3 is u, and
+ * c = #{ j : u >= T_j } over T_j = round-half-even(2^32 sum_{i<=j} e^-1 / i!), j = 0..11:
+ *   0x5e2d58d9 0xbc5ab1b1 0xeb715e1e 0xfb239797 0xff1025f6 0xffd90f3c
+ *   0xfffa8b72 0xffff540c 0xffffed1f 0xfffffe21 0xffffffd5 0xfffffffc
+ * (counts 0..12).  count_of_word: host code only, no context.  bootstrap_counts: the device draw
+ * of scenarios [first_index, first_index + count), out[s * M + b]; 1 <= M <= 64, count <= 2^24.
+ */
+int twosd_bootstrap_count_of_word(uint32_t u);
+int twosd_bootstrap_counts(twosd_ctx *ctx, int M, uint64_t seed, uint64_t first_index, int64_t count, uint8_t *out);
+
+/*
+ * Re-formed cuts under bootstrap weights (the device part of the in-sample stopping rule; no
+ * reference counterpart: plugin/stopping_rule.jl is empty).  For each of the H handles (all of
+ * epigraph epi) and each row b of M + 1 -- row 0 the identity replicate (all counts 1), row 1 + b
+ * replicate b -- with c(s) the count of scenario index_offset + s and N_j the handle's scenarios:
+ *     W_jb = sum_{s < N_j} c(s) w_s,   p_s = c(s) w_s / W_jb,
+ *     g = sum_s p_s pi_pick(s),  S_e = sum_s p_s PK[pick(s), e] dv[s, e],
+ *     alpha = g.r + sum_{e rhs} S_e (+ c0 once for a template with general bounds),
+ *     beta = -T'g - sum_{e in T} S_e e_col(e),   weight_mark = W_jb
+ * (build_sasa_cut's formula, epigraph.jl:125-146, with the picks fixed; dual vectors of length mv).
+ * W_jb = 0 gives the zero cut with weight_mark 0, the reference's empty-epigraph cut.
+ * total_weight[b] = sum_{s < N} c(s) w_s over all scenarios the epigraph holds now.
+ * Outputs (host): alpha[b * H + j], beta[(b * H + j) * n1 + i], weight_mark[b * H + j] (nullable),
+ * total_weight[M + 1] (nullable).  Row 0 equals the cut twosd_build_cut returned up to rounding.
+ * Weights are summed as integers (w 2^58 / total weight, rounded), so weight_mark and
+ * total_weight carry a relative error of at most N 2^-59 total / W and are the same bits on
+ * every run; the fp64 sums use a fixed shard layout (the same bits on every run, and the same
+ * for H handles in one call as in H calls).
+ * TWOSD_E_ARG unless 0 <= M <= 64 (M = 0: the identity row alone), H >= 1 and every handle
+ * belongs to epi; TWOSD_E_UNSUPPORTED for k beyond the cut envelope of 127.
+ *
+ * Multi-GPU split, as twosd_cut_partial_len / _partial / _finalize: each rank runs reform_partial
+ * over its own scenarios (index_offset = the global index of its first one; its handles mirror the
+ * other ranks', vertex sets identical) into caller DEVICE buffers of *n_u64 uint64 (the totals,
+ * the W_jb and the per-vertex weights: integers, exact under any order of summation) and *n_f64
+ * doubles (the unnormalised S_e); the caller sums them over the ranks and every rank finalizes.
+ * total_weight: the GLOBAL total scenario weight of the epigraph, the same value on every rank
+ * (it fixes the integer scale).  twosd_reform_cuts is partial then finalize on one context.
+ */
+int twosd_reform_cuts(twosd_ctx *ctx, int epi, int H, const int *handles, int M, uint64_t seed, uint64_t index_offset,
+                      double *alpha, double *beta, double *weight_mark, double *total_weight);
+int twosd_reform_partial_len(twosd_ctx *ctx, int H, const int *handles, int M, int64_t *n_u64, int64_t *n_f64);
+int twosd_reform_partial(twosd_ctx *ctx, int epi, int H, const int *handles, int M, uint64_t seed, uint64_t index_offset,
+                         double total_weight, uint64_t *d_u64, double *d_f64);
+int twosd_reform_finalize(twosd_ctx *ctx, int H, const int *handles, int M, double total_weight, const uint64_t *d_u64,
+                          const double *d_f64, double *alpha, double *beta, double *weight_mark, double *total_weight_out);
+/* Device time of the last twosd_reform_cuts on the context's stream (HIP events), milliseconds:
+ * [0] the partial sums (histograms, delta streaming, reductions), [1] the finalize with its copies. */
+int twosd_reform_last_ms(twosd_ctx *ctx, double *ms2);
+
 /* Timing of the last kernel phases on the context's stream (HIP events), microseconds:
  * [0] LP kernel, [1] dedup push, [2] argmax+cut partial, [3] cut finalize,
  * [4] warm-start pool selection of the last LP batch (0 without a pool). */

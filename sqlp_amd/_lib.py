@@ -93,6 +93,18 @@ SIGNATURES = [
     ("twosd_refresh_assemble", I, [P, I, P, C.c_int64, I, P, P, P, P]),
     ("twosd_pool_candidate_picks", I, [P, I, P, I, I, I, P, P]),
     ("twosd_pool_set_candidates", I, [P, I, I, I, P, P]),
+    ("twosd_picks_keep", I, [P, I, P]),
+    ("twosd_picks_info", I, [P, I, P, P, P]),
+    ("twosd_picks_get", I, [P, I, P]),
+    ("twosd_picks_release", I, [P, I]),
+    ("twosd_picks_count", I, [P, P]),
+    ("twosd_bootstrap_count_of_word", I, [C.c_uint32]),
+    ("twosd_bootstrap_counts", I, [P, I, C.c_uint64, C.c_uint64, C.c_int64, P]),
+    ("twosd_reform_cuts", I, [P, I, I, P, I, C.c_uint64, C.c_uint64, P, P, P, P]),
+    ("twosd_reform_partial_len", I, [P, I, P, I, P, P]),
+    ("twosd_reform_partial", I, [P, I, I, P, I, C.c_uint64, C.c_uint64, D, P, P]),
+    ("twosd_reform_finalize", I, [P, I, P, I, D, P, P, P, P, P, P]),
+    ("twosd_reform_last_ms", I, [P, P]),
 ]
 
 

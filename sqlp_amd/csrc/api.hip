@@ -449,6 +449,7 @@ extern "C" int twosd_set_random_positions(twosd_ctx *c, int k, const int *row, c
     c->k_valid = false;
     c->has_dist = false;
     cut_invalidate_pk(c);
+    c->boot = twosd::BootState();   // stored picks and the re-formation's template copies
     return TWOSD_OK;
 }
 

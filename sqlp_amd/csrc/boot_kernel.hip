@@ -1,0 +1,687 @@
+// boot_kernel.hip -- the in-sample stopping rule's device part: stored argmax picks and the
+// bootstrap re-formation of cuts from them on gfx950.
+//
+// Reference: none.  yhz0/SQLP lists "Need to implement stopping criteria" in its readme and
+// src/sd_algorithm/plugin/stopping_rule.jl is an empty file.  The rule built here is SD's own
+// (Higle and Sen; Sen and Liu 2016): resample the observations, re-form every cut of the master
+// from the argmax picks it was built with, and look at the gap at the incumbent.
+//
+// A cut is linear in the scenario weights once its picks a(s) are fixed (cut_finalize_impl):
+//     g = sum_s p_s pi_a(s),  alpha = g.r + sum_{e rhs} S_e (+ c0),  beta = -T'g - sum_{e in T} S_e e_col(e)
+//     S_e = sum_s p_s PK[a(s), e] dv[s, e]
+// Replicate b weighs scenario s (global index g = index_offset + s) by c_b(g) w_s with
+// c_b(g) ~ Poisson(1), a pure function of (seed, g, b): Philox4x32-10, counter (g_lo, g_hi, b >> 2, 1),
+// key (seed_lo, seed_hi), word b & 3 through the 12 thresholds of the Poisson(1) CDF.  Row 0 of every
+// output is the identity replicate (all counts 1), row 1 + b is replicate b.  Each sum is normalised
+// by the replicate's own total W_jb = sum_{s < N_j} c_b w_s, so independent counts (no atomics on
+// floating point, the same draws under any sharding) serve where the literature resamples a
+// multinomial.
+//
+// Weights are integers: q_s = rn(w_s 2^58 / total_weight) (total_weight: the caller's global total,
+// the same on every rank), so sum_s c q_s <= 12 * 2^58 < 2^62 is exact in uint64 and independent of
+// the order of its terms: the per-vertex weights, W_jb and the epigraph totals are bit-identical on
+// every run and add exactly across ranks.  The S_e sums are fp64 with a fixed shard layout.
+//
+// Kernels:
+//   boot_counts_kernel   the counts themselves (diagnostic: twosd_bootstrap_counts)
+//   boot_weight_kernel   sum_{s < n} c_b(s) q_s per replicate (W_jb with n = N_j; the totals with n = N)
+//   boot_hist_kernel     the per-vertex weights (M + 1 per pick) as uint64 block histograms in LDS
+//                        (windows of 2048 vertices x one Philox call of 4 replicates = 64 KB), flushed
+//                        with integer atomics
+//   boot_reform_kernel   streams the epigraph's N x k deltas once per replicate group of 16: a wave
+//                        walks tiles of 64 scenarios; lanes = scenarios for the Philox draws, then
+//                        lanes = elements (e = lane, lane + 64) while the tile's scenarios go by one
+//                        at a time with wave-uniform picks and counts (v_readlane); 16 + 1
+//                        accumulators per element stay in VGPRs (KE = 2: 127 VGPRs, no scratch)
+//   boot_reduce_kernel   the blocks' S partials summed in block order
+//   boot_g_kernel        gpart = (per-vertex weights) x V for 8 replicate rows at a time, skipping the
+//                        vertices no scenario picked (the identity row's weight is 0)
+//   boot_final_kernel    g, alpha, beta per (handle, replicate), normalised by W_jb
+#include <hip/hip_runtime.h>
+#include <math.h>
+#include <algorithm>
+#include <cmath>
+#include <vector>
+#include "twosd_ctx.h"
+#include "philox.h"
+
+namespace twosd {
+
+constexpr int kBootMaxM = 64;            // bootstrap replicates per call
+constexpr int kBootGroup = 16;           // replicates whose accumulators a wave holds at once (4 Philox calls)
+constexpr int kBootMaxChunks = 512;      // blocks per (handle, replicate group): the S partials' shard count
+constexpr int kBootRB = 8;               // replicate rows per block of boot_g_kernel
+constexpr double kBootFix = 288230376151711744.0;   // 2^58: sum of 12 q_s stays below 2^62
+
+// Poisson(1) count of a uniform 32-bit word: #{ j : u >= T_j }, T_j = rne(2^32 sum_{i<=j} e^-1 / i!)
+TWOSD_HD int boot_count_of_word(uint32_t u) {
+    return (int)(u >= 0x5e2d58d9u) + (int)(u >= 0xbc5ab1b1u) + (int)(u >= 0xeb715e1eu) + (int)(u >= 0xfb239797u) +
+           (int)(u >= 0xff1025f6u) + (int)(u >= 0xffd90f3cu) + (int)(u >= 0xfffa8b72u) + (int)(u >= 0xffff540cu) +
+           (int)(u >= 0xffffed1fu) + (int)(u >= 0xfffffe21u) + (int)(u >= 0xffffffd5u) + (int)(u >= 0xfffffffcu);
+}
+
+// the four counts of replicates 4 Q .. 4 Q + 3 for global scenario g
+TWOSD_HD Philox4 boot_words(unsigned long long g, int Q, unsigned long long seed) {
+    return philox4x32_10((uint32_t)g, (uint32_t)(g >> 32), (uint32_t)Q, 1u, (uint32_t)seed, (uint32_t)(seed >> 32));
+}
+
+__device__ __forceinline__ unsigned long long boot_q(double w, double scale) {
+    return w > 0.0 ? (unsigned long long)__double2ull_rn(w * scale) : 0ull;   // NaN and w <= 0 weigh nothing
+}
+
+__global__ void __launch_bounds__(256) boot_counts_kernel(int M, unsigned long long seed, unsigned long long first, long long count,
+                                                          uint8_t *__restrict__ out) {
+    const int nq = (M + 3) / 4;
+    const long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (idx >= count * nq) return;
+    const long long s = idx / nq;
+    const int Q = (int)(idx - s * nq);
+    const Philox4 r = boot_words(first + (unsigned long long)s, Q, seed);
+#pragma unroll
+    for (int t = 0; t < 4; ++t)
+        if (4 * Q + t < M) out[s * M + 4 * Q + t] = (uint8_t)boot_count_of_word(r.v[t]);
+}
+
+// out[0] += sum q_s, out[1 + b] += sum c_b(s) q_s over s < n; blockIdx.y = the Philox call Q of four
+// replicates, the last y the identity row.  Integer sums: any order gives the same bits.  One atomic
+// per block and replicate (a few blocks: every wave adding to the same 33 words took 0.5 ms).
+__global__ void __launch_bounds__(256) boot_weight_kernel(int n, const double *__restrict__ w, double scale, int M,
+                                                          unsigned long long seed, unsigned long long off,
+                                                          unsigned long long *__restrict__ out) {
+    __shared__ unsigned long long sh[4][4];
+    const int nq = (M + 3) / 4, Q = blockIdx.y;
+    unsigned long long a[4] = {0ull, 0ull, 0ull, 0ull};
+    for (int s = blockIdx.x * 256 + threadIdx.x; s < n; s += gridDim.x * 256) {
+        const unsigned long long q = boot_q(w[s], scale);
+        if (Q == nq) { a[0] += q; continue; }
+        const Philox4 r = boot_words(off + (unsigned long long)s, Q, seed);
+#pragma unroll
+        for (int t = 0; t < 4; ++t) a[t] += (unsigned long long)boot_count_of_word(r.v[t]) * q;
+    }
+#pragma unroll
+    for (int t = 0; t < 4; ++t)
+        for (int o = 32; o > 0; o >>= 1) a[t] += __shfl_xor(a[t], o);
+    if ((threadIdx.x & 63) == 0)
+        for (int t = 0; t < 4; ++t) sh[threadIdx.x >> 6][t] = a[t];
+    __syncthreads();
+    if (threadIdx.x >= 4) return;
+    const int t = threadIdx.x;
+    const unsigned long long v = sh[0][t] + sh[1][t] + sh[2][t] + sh[3][t];
+    if (!v) return;
+    if (Q == nq) {
+        if (t == 0) atomicAdd(&out[0], v);
+    } else if (4 * Q + t < M) {
+        atomicAdd(&out[1 + 4 * Q + t], v);
+    }
+}
+
+// hist[row][v] += sum over the scenarios s < n with pick v of c_row(s) q_s, through a block
+// histogram in LDS: blockIdx.y = the Philox call Q of four replicates (the last y: the identity
+// row), blockIdx.z = a window of kBootVW vertices (a pick outside it is another block's).  Integer
+// sums: the atomics' order does not show in the result.
+constexpr int kBootVW = 2048;
+__global__ void __launch_bounds__(1024) boot_hist_kernel(int n, int nv, int nvs, int M, const int *__restrict__ picks,
+                                                         const double *__restrict__ w, double scale, unsigned long long seed,
+                                                         unsigned long long off, unsigned long long *__restrict__ hist) {
+    __shared__ unsigned long long hl[4 * kBootVW];
+    const int nq = (M + 3) / 4, Q = blockIdx.y;
+    const int v0 = blockIdx.z * kBootVW, v1 = min(nv, v0 + kBootVW);
+    for (int i = threadIdx.x; i < 4 * kBootVW; i += 1024) hl[i] = 0ull;
+    __syncthreads();
+    for (int s = blockIdx.x * 1024 + threadIdx.x; s < n; s += gridDim.x * 1024) {
+        const int pick = picks[s];
+        if (pick < v0 || pick >= v1) continue;
+        const unsigned long long q = boot_q(w[s], scale);
+        if (!q) continue;
+        if (Q == nq) {
+            __hip_atomic_fetch_add(&hl[pick - v0], q, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+            continue;
+        }
+        const Philox4 r = boot_words(off + (unsigned long long)s, Q, seed);
+#pragma unroll
+        for (int t = 0; t < 4; ++t) {
+            const int cnt = (4 * Q + t < M) ? boot_count_of_word(r.v[t]) : 0;
+            if (cnt)
+                __hip_atomic_fetch_add(&hl[t * kBootVW + pick - v0], (unsigned long long)cnt * q, __ATOMIC_RELAXED,
+                                       __HIP_MEMORY_SCOPE_WORKGROUP);
+        }
+    }
+    __syncthreads();
+    for (int i = threadIdx.x; i < 4 * kBootVW; i += 1024) {
+        const unsigned long long h = hl[i];
+        if (!h) continue;
+        const int row = Q == nq ? 0 : 1 + 4 * Q + i / kBootVW;
+        atomicAdd(&hist[(size_t)row * nvs + v0 + i % kBootVW], h);
+    }
+}
+
+struct BootParams {
+    int n, k, k4, nv, M, ngroups, tpb;   // tpb: 64-scenario tiles per block
+    double scale;
+    unsigned long long seed, off;
+    const double *dv, *w, *PK;
+    const int *picks;
+    double *slots;                       // nchunks x (M + 1) x k
+};
+
+// KE: elements per lane (k <= 64 KE)
+template <int KE>
+__global__ void __launch_bounds__(256) boot_reform_kernel(BootParams P) {
+    __shared__ double comb[(kBootGroup + 1) * KE * 64];
+    const int lane = threadIdx.x & 63;
+    const int wid = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int grp = blockIdx.x % P.ngroups, chunk = blockIdx.x / P.ngroups;
+    const int ntiles = (P.n + 63) >> 6;
+    const int t0 = chunk * P.tpb, t1 = min(ntiles, t0 + P.tpb);
+    int ec[KE];                       // this lane's elements, clamped to k - 1
+#pragma unroll
+    for (int u = 0; u < KE; ++u) ec[u] = min(lane + 64 * u, P.k - 1);
+    double acc[kBootGroup + 1][KE];
+#pragma unroll
+    for (int r = 0; r <= kBootGroup; ++r)
+#pragma unroll
+        for (int u = 0; u < KE; ++u) acc[r][u] = 0.0;
+
+    for (int t = t0 + wid; t < t1; t += 4) {
+        // lanes = the tile's scenarios
+        const int s = t * 64 + lane;
+        const bool valid = s < P.n;
+        const int pick = valid ? P.picks[s] : -1;
+        const bool ok = pick >= 0 && pick < P.nv;          // a scenario without a pick weighs in W only
+        const unsigned long long q = ok ? boot_q(P.w[s], P.scale) : 0ull;
+        unsigned chi[kBootGroup];                           // high word of (double)count: 0 for count 0
+#pragma unroll
+        for (int qd = 0; qd < kBootGroup / 4; ++qd) {
+            const int Q = grp * (kBootGroup / 4) + qd;
+            Philox4 r;
+            r.v[0] = r.v[1] = r.v[2] = r.v[3] = 0u;
+            if (4 * Q < P.M) r = boot_words(P.off + (unsigned long long)s, Q, P.seed);   // wave-uniform
+#pragma unroll
+            for (int tt = 0; tt < 4; ++tt) {
+                const int cnt = (4 * Q + tt < P.M) ? boot_count_of_word(r.v[tt]) : 0;
+                chi[4 * qd + tt] = (unsigned)__double2hiint((double)cnt);
+            }
+        }
+        const double qf = (double)q;
+        const int qlo = __double2loint(qf), qhi = __double2hiint(qf);
+        const int pk0 = ok ? pick : 0;
+        // lanes = elements; the scenarios go by four at a time, the next four's rows (8 KE loads of
+        // 512 B each) in flight under the current four's arithmetic.  A lane past k reads element
+        // k - 1 again (no divergent load) and its sums are never stored; a step past the tile's
+        // last scenario reads that scenario again with weight 0.
+        const int nvalid = min(64, P.n - t * 64);
+        const double *dvt = P.dv + (size_t)(t * 64) * P.k;
+        auto load4 = [&](int i0, double (&d)[4][KE], double (&p)[4][KE]) {
+#pragma unroll
+            for (int u4 = 0; u4 < 4; ++u4) {
+                const int i = min(i0 + u4, nvalid - 1);
+                const int pv = __builtin_amdgcn_readlane(pk0, i);
+#pragma unroll
+                for (int u = 0; u < KE; ++u) {
+                    d[u4][u] = dvt[(size_t)i * P.k + ec[u]];
+                    p[u4][u] = P.PK[(size_t)pv * P.k4 + ec[u]];
+                }
+            }
+        };
+        auto work4 = [&](int i0, const double (&d)[4][KE], const double (&p)[4][KE]) {
+#pragma unroll
+            for (int u4 = 0; u4 < 4; ++u4) {
+                const int i = min(i0 + u4, 63);
+                const double wq = i0 + u4 < nvalid ? __hiloint2double(__builtin_amdgcn_readlane(qhi, i), __builtin_amdgcn_readlane(qlo, i)) : 0.0;
+                double term[KE];
+#pragma unroll
+                for (int u = 0; u < KE; ++u) term[u] = wq * p[u4][u] * d[u4][u];
+#pragma unroll
+                for (int r = 0; r < kBootGroup; ++r) {
+                    const double cd = __hiloint2double(__builtin_amdgcn_readlane((int)chi[r], i), 0);   // wave-uniform count
+#pragma unroll
+                    for (int u = 0; u < KE; ++u) acc[r][u] = fma(cd, term[u], acc[r][u]);
+                }
+#pragma unroll
+                for (int u = 0; u < KE; ++u) acc[kBootGroup][u] += term[u];
+            }
+        };
+        double da[4][KE], pa[4][KE], db[4][KE], pb[4][KE];
+        load4(0, da, pa);
+        for (int i0 = 0; i0 < nvalid; i0 += 8) {
+            if (i0 + 4 < nvalid) load4(i0 + 4, db, pb);
+            work4(i0, da, pa);
+            if (i0 + 4 >= nvalid) break;
+            if (i0 + 8 < nvalid) load4(i0 + 8, da, pa);
+            work4(i0 + 4, db, pb);
+        }
+    }
+    // the block's four waves combined in wave order
+    for (int wv = 0; wv < 4; ++wv) {
+        if (wid == wv) {
+#pragma unroll
+            for (int r = 0; r <= kBootGroup; ++r)
+#pragma unroll
+                for (int u = 0; u < KE; ++u) {
+                    double &d = comb[(r * KE + u) * 64 + lane];
+                    d = wv == 0 ? acc[r][u] : d + acc[r][u];
+                }
+        }
+        __syncthreads();
+    }
+    const int B = P.M + 1;
+    double *out = P.slots + (size_t)chunk * B * P.k;
+    for (int idx = threadIdx.x; idx < (kBootGroup + 1) * KE * 64; idx += 256) {
+        const int r = idx / (KE * 64), e = idx % (KE * 64);
+        const int row = r == kBootGroup ? (grp == 0 ? 0 : -1) : 1 + grp * kBootGroup + r;
+        if (row >= 0 && row < B && e < P.k) out[(size_t)row * P.k + e] = comb[idx];
+    }
+}
+
+// S[row][e] = sum over the chunks in a fixed order: 8 segments of consecutive chunks summed side by
+// side (32 outputs per block), then the segments in order
+__global__ void __launch_bounds__(256) boot_reduce_kernel(int nchunks, int width, const double *__restrict__ slots,
+                                                          double *__restrict__ out) {
+    __shared__ double sh[8][32];
+    const int li = threadIdx.x & 31, seg = threadIdx.x >> 5;
+    const int idx = blockIdx.x * 32 + li;
+    const int per = (nchunks + 7) / 8;
+    const int c0 = seg * per, c1 = min(nchunks, c0 + per);
+    double s = 0.0;
+    if (idx < width)
+        for (int c = c0; c < c1; ++c) s += slots[(size_t)c * width + idx];
+    sh[seg][li] = s;
+    __syncthreads();
+    if (seg != 0 || idx >= width) return;
+    double t = 0.0;
+#pragma unroll
+    for (int g = 0; g < 8; ++g) t += sh[g][li];
+    out[idx] = t;
+}
+
+// gpart[c][b][i] = sum_{v in vertex chunk c} hist[b][v] V[v][i] for rows b0 .. b0 + 7 (blockIdx.y)
+__global__ void __launch_bounds__(256) boot_g_kernel(int nv, int nvs, int m, int chunk, int B,
+                                                     const unsigned long long *__restrict__ hist, const double *__restrict__ V,
+                                                     double *__restrict__ gpart) {
+    const int b0 = blockIdx.y * kBootRB;
+    const int v0 = blockIdx.x * chunk, v1 = min(nv, v0 + chunk);
+    for (int i = threadIdx.x; i < m; i += 256) {
+        double acc[kBootRB];
+#pragma unroll
+        for (int r = 0; r < kBootRB; ++r) acc[r] = 0.0;
+        for (int v = v0; v < v1; ++v) {
+            if (hist[v] == 0ull) continue;   // row 0 (all counts 1): no scenario picks v, so no replicate weighs it
+            const double x = V[(size_t)v * m + i];
+#pragma unroll
+            for (int r = 0; r < kBootRB; ++r)
+                if (b0 + r < B) acc[r] = fma((double)hist[(size_t)(b0 + r) * nvs + v], x, acc[r]);
+        }
+#pragma unroll
+        for (int r = 0; r < kBootRB; ++r)
+            if (b0 + r < B) gpart[((size_t)blockIdx.x * B + b0 + r) * m + i] = acc[r];
+    }
+}
+
+// one block per replicate row b of one handle: g = sum of the vertex chunks (chunk order), then
+// alpha = (g.r + sum_{e rhs} S_e) / Wq (+ c0), beta = (-T'g - sum_{e in T} S_e e_col) / Wq; Wq = 0:
+// the zero cut with weight_mark 0 (the reference's empty-epigraph cut).  Outputs at index b * H + j.
+__global__ void __launch_bounds__(256) boot_final_kernel(int B, int H, int j, int m, int n1, int k, int nbc,
+                                                         const double *__restrict__ gpart, const double *__restrict__ r,
+                                                         const double *__restrict__ T, const int *__restrict__ col,
+                                                         const double *__restrict__ S, const unsigned long long *__restrict__ Wq,
+                                                         double wunit, double c0, double *__restrict__ alpha,
+                                                         double *__restrict__ beta, double *__restrict__ wm) {
+    __shared__ double gs[1024];
+    __shared__ double as;
+    const int b = blockIdx.x;
+    const size_t o = (size_t)b * H + j;
+    double *bo = beta + o * n1;
+    const unsigned long long wq = Wq[b];
+    if (wq == 0ull) {
+        for (int jj = threadIdx.x; jj < n1; jj += 256) bo[jj] = 0.0;
+        if (threadIdx.x == 0) { alpha[o] = 0.0; wm[o] = 0.0; }
+        return;
+    }
+    for (int i = threadIdx.x; i < m; i += 256) {
+        double s = 0.0;
+        for (int c = 0; c < nbc; ++c) s += gpart[((size_t)c * B + b) * m + i];
+        gs[i] = s;
+    }
+    __syncthreads();
+    for (int jj = threadIdx.x; jj < n1; jj += 256) {
+        double s = 0.0;
+        for (int i = 0; i < m; ++i) s = fma(T[(size_t)i * n1 + jj], gs[i], s);
+        bo[jj] = -s;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        double a = 0.0;
+        for (int i = 0; i < m; ++i) a = fma(gs[i], r[i], a);
+        for (int e = 0; e < k; ++e) {
+            const double se = S[(size_t)b * k + e];
+            if (col[e] < 0) a += se;
+            else bo[col[e]] -= se;
+        }
+        as = a;
+    }
+    __syncthreads();
+    const double inv = 1.0 / (double)wq;
+    for (int jj = threadIdx.x; jj < n1; jj += 256) bo[jj] *= inv;
+    if (threadIdx.x == 0) {
+        alpha[o] = as * inv + c0;
+        wm[o] = (double)wq * wunit;
+    }
+}
+
+#define HIPCHK(expr)                                                                               \
+    do {                                                                                           \
+        hipError_t _e = (expr);                                                                    \
+        if (_e != hipSuccess) return fail(TWOSD_E_DEVICE, "%s: %s", #expr, hipGetErrorString(_e)); \
+    } while (0)
+
+static PickSet *pick_of(twosd_ctx *c, int handle) {
+    if (handle < 0 || handle >= (int)c->boot.picks.size() || !c->boot.picks[handle].live) return nullptr;
+    return &c->boot.picks[handle];
+}
+
+// a usable handle, or the error code with its message
+static int usable_pick(twosd_ctx *c, int handle, const char *what, PickSet **out) {
+    PickSet *h = pick_of(c, handle);
+    if (!h)
+        return fail(TWOSD_E_ARG, "%s: pick handle %d does not exist (released, or dropped by twosd_set_template / "
+                    "twosd_set_random_positions)", what, handle);
+    if (h->stale || h->nv > c->dvs.size)
+        return fail(TWOSD_E_STATE, "%s: pick handle %d names vertices below %d, but the vertex set was cleared or truncated "
+                    "below that since", what, handle, h->nv);
+    *out = h;
+    return TWOSD_OK;
+}
+
+struct BootLayout {
+    int H, B, nvs, k;
+    size_t o_wj, o_hist, n_u64, n_f64;   // u64: [B totals][H x B Wj][H x B x nvs hist]; f64: H x B x k sums
+};
+
+static int boot_layout(twosd_ctx *c, int epi, int H, const int *handles, int M, const char *what, BootLayout *L) {
+    if (!c || !c->has_template) return fail(TWOSD_E_STATE, "%s: no template", what);
+    if (H < 1 || !handles) return fail(TWOSD_E_ARG, "%s: H = %d handles (at least 1)", what, H);
+    if (M < 0 || M > kBootMaxM) return fail(TWOSD_E_ARG, "%s: M = %d replicates outside [0, %d]", what, M, kBootMaxM);
+    if (c->k > 127) return fail(TWOSD_E_UNSUPPORTED, "k = %d random elements exceeds the cut kernel envelope (127)", c->k);
+    int nvs = 1;
+    for (int j = 0; j < H; ++j) {
+        PickSet *h = nullptr;
+        int rc = usable_pick(c, handles[j], what, &h);
+        if (rc) return rc;
+        if (epi >= 0 && h->epi != epi)
+            return fail(TWOSD_E_ARG, "%s: pick handle %d belongs to epigraph %d, not %d", what, handles[j], h->epi, epi);
+        nvs = std::max(nvs, h->nv);
+    }
+    L->H = H; L->B = M + 1; L->nvs = nvs; L->k = c->k;
+    L->o_wj = (size_t)L->B;
+    L->o_hist = L->o_wj + (size_t)H * L->B;
+    L->n_u64 = L->o_hist + (size_t)H * L->B * nvs;
+    L->n_f64 = std::max<size_t>((size_t)H * L->B * c->k, 1);
+    return TWOSD_OK;
+}
+
+static int boot_partial_impl(twosd_ctx *c, int epi, const BootLayout &L, const int *handles, int M, unsigned long long seed,
+                             unsigned long long off, double total_weight, unsigned long long *d_u64, double *d_f64) {
+    const EpiDevice &E = c->epis[epi];
+    const int k = c->k, B = L.B;
+    const double scale = kBootFix / total_weight;
+    const double *PK = nullptr;
+    int k4 = 0, rc;
+    if ((rc = cut_pk_current(c, &PK, &k4))) return rc;
+    HIPCHK(hipMemsetAsync(d_u64, 0, sizeof(unsigned long long) * L.n_u64, c->stream));
+    const int nq = (M + 3) / 4;
+    auto weights = [&](int n, unsigned long long *out) {
+        if (n <= 0) return;
+        hipLaunchKernelGGL(boot_weight_kernel, dim3(std::max(1, std::min((n + 8191) / 8192, 32)), nq + 1), dim3(256), 0, c->stream, n,
+                           E.d_w.p, scale, M, seed, off, out);
+    };
+    weights(E.count, d_u64);
+    const int ngroups = std::max(1, (M + kBootGroup - 1) / kBootGroup);
+    // the blocks' shard layout of a handle depends on its own scenario count alone
+    auto shard = [](int n, int *tpb, int *nchunks) {
+        const int ntiles = (n + 63) / 64;
+        const int want = std::min(kBootMaxChunks, (ntiles + 3) / 4);
+        *tpb = (ntiles + want - 1) / want;
+        *nchunks = (ntiles + *tpb - 1) / *tpb;
+    };
+    size_t slots_need = 1;
+    for (int j = 0; j < L.H; ++j) {
+        const PickSet &h = c->boot.picks[handles[j]];
+        if (h.n > E.count)
+            return fail(TWOSD_E_STATE, "reform: pick handle %d holds %d scenarios, epigraph %d only %d", handles[j], h.n, epi, E.count);
+        int tpb, nchunks;
+        shard(h.n, &tpb, &nchunks);
+        slots_need = std::max(slots_need, (size_t)nchunks * B * k);
+    }
+    if ((rc = c->boot.slots.fit(slots_need))) return rc;   // once, before the first launch that writes it
+    for (int j = 0; j < L.H; ++j) {
+        const PickSet &h = c->boot.picks[handles[j]];
+        weights(h.n, d_u64 + L.o_wj + (size_t)j * B);
+        hipLaunchKernelGGL(boot_hist_kernel, dim3(std::max(1, std::min((h.n + 8191) / 8192, 64)), nq + 1, (h.nv + kBootVW - 1) / kBootVW),
+                           dim3(1024), 0, c->stream, h.n, h.nv, L.nvs, M, h.d.p, E.d_w.p, scale, seed, off,
+                           d_u64 + L.o_hist + (size_t)j * B * L.nvs);
+        if (k == 0) continue;
+        int tpb, nchunks;
+        shard(h.n, &tpb, &nchunks);
+        BootParams P{};
+        P.n = h.n; P.k = k; P.k4 = k4; P.nv = h.nv; P.M = M; P.ngroups = ngroups; P.tpb = tpb;
+        P.scale = scale; P.seed = seed; P.off = off;
+        P.dv = E.d_dv; P.w = E.d_w; P.PK = PK; P.picks = h.d;
+        P.slots = c->boot.slots;
+        if (k <= 64) hipLaunchKernelGGL(boot_reform_kernel<1>, dim3(nchunks * ngroups), dim3(256), 0, c->stream, P);
+        else hipLaunchKernelGGL(boot_reform_kernel<2>, dim3(nchunks * ngroups), dim3(256), 0, c->stream, P);
+        hipLaunchKernelGGL(boot_reduce_kernel, dim3((B * k + 31) / 32), dim3(256), 0, c->stream, nchunks, B * k, c->boot.slots.p,
+                           d_f64 + (size_t)j * B * k);
+    }
+    HIPCHK(hipGetLastError());
+    return TWOSD_OK;
+}
+
+static int boot_template(twosd_ctx *c) {
+    BootState &S = c->boot;
+    if (S.tmpl_ready) return TWOSD_OK;
+    int rc;
+    std::vector<int> col(std::max(c->k, 1), -1);
+    for (int e = 0; e < c->k; ++e) col[e] = c->pos_col[e];
+    std::vector<double> T = c->T;
+    if (T.empty()) T.push_back(0.0);
+    if ((rc = S.d_T.upload(T)) || (rc = S.d_r.upload(c->r)) || (rc = S.d_col.upload(col))) return rc;
+    S.tmpl_ready = true;
+    return TWOSD_OK;
+}
+
+static int boot_finalize_impl(twosd_ctx *c, const BootLayout &L, const int *handles, double total_weight,
+                              const unsigned long long *d_u64, const double *d_f64, double *alpha, double *beta,
+                              double *weight_mark, double *total_out) {
+    BootState &S = c->boot;
+    const int B = L.B, H = L.H, m = c->L.m, n1 = c->n1, k = c->k;
+    int rc;
+    if ((rc = boot_template(c))) return rc;
+    const size_t rows = (size_t)B * H;
+    if ((rc = S.d_alpha.fit(rows)) || (rc = S.d_beta.fit(std::max<size_t>(rows * n1, 1))) || (rc = S.d_wm.fit(rows))) return rc;
+    const double wunit = total_weight / kBootFix;
+    // vertex chunks of 32 or more, at most 256 of them
+    if ((rc = S.gpart.fit((size_t)std::max(1, (L.nvs + 31) / 32) * B * m))) return rc;
+    for (int j = 0; j < H; ++j) {
+        const PickSet &h = c->boot.picks[handles[j]];
+        const int chunk = std::max(32, (h.nv + 255) / 256);
+        const int nbc = std::max(1, (h.nv + chunk - 1) / chunk);
+        const unsigned long long *hist = d_u64 + L.o_hist + (size_t)j * B * L.nvs;
+        hipLaunchKernelGGL(boot_g_kernel, dim3(nbc, (B + kBootRB - 1) / kBootRB), dim3(256), 0, c->stream, h.nv, L.nvs, m, chunk, B,
+                           hist, c->dvs.V, S.gpart.p);
+        hipLaunchKernelGGL(boot_final_kernel, dim3(B), dim3(256), 0, c->stream, B, H, j, m, n1, k, nbc, S.gpart.p, S.d_r.p, S.d_T.p,
+                           S.d_col.p, d_f64 + (size_t)j * B * k, d_u64 + L.o_wj + (size_t)j * B, wunit, c->has_bounds ? c->c0 : 0.0,
+                           S.d_alpha.p, S.d_beta.p, S.d_wm.p);
+    }
+    HIPCHK(hipGetLastError());
+    std::vector<unsigned long long> tw(B);
+    HIPCHK(hipMemcpyAsync(alpha, S.d_alpha, sizeof(double) * rows, hipMemcpyDeviceToHost, c->stream));
+    if (n1 > 0) HIPCHK(hipMemcpyAsync(beta, S.d_beta, sizeof(double) * rows * n1, hipMemcpyDeviceToHost, c->stream));
+    if (weight_mark) HIPCHK(hipMemcpyAsync(weight_mark, S.d_wm, sizeof(double) * rows, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipMemcpyAsync(tw.data(), d_u64, sizeof(unsigned long long) * B, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    if (total_out)
+        for (int b = 0; b < B; ++b) total_out[b] = (double)tw[b] * wunit;
+    return TWOSD_OK;
+}
+
+}  // namespace twosd
+
+using namespace twosd;
+
+extern "C" int twosd_bootstrap_count_of_word(uint32_t u) { return boot_count_of_word(u); }
+
+extern "C" int twosd_bootstrap_counts(twosd_ctx *c, int M, uint64_t seed, uint64_t first_index, int64_t count, uint8_t *out) {
+    if (!c) return fail(TWOSD_E_ARG, "bootstrap_counts: ctx is NULL");
+    if (M < 1 || M > kBootMaxM) return fail(TWOSD_E_ARG, "bootstrap_counts: M = %d replicates outside [1, %d]", M, kBootMaxM);
+    if (count < 0 || count > (1ll << 24) || (count > 0 && !out))
+        return fail(TWOSD_E_ARG, "bootstrap_counts: count = %lld outside [0, 2^24] or out NULL", (long long)count);
+    if (count == 0) return TWOSD_OK;
+    HIPCHK(hipSetDevice(c->device));
+    int rc;
+    if ((rc = c->boot.counts.fit((size_t)count * M))) return rc;
+    const long long total = count * ((M + 3) / 4);
+    hipLaunchKernelGGL(boot_counts_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, c->stream, M,
+                       (unsigned long long)seed, (unsigned long long)first_index, (long long)count, c->boot.counts.p);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(out, c->boot.counts, (size_t)count * M, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    return TWOSD_OK;
+}
+
+extern "C" int twosd_picks_keep(twosd_ctx *c, int epi, int *handle) {
+    if (!c || !c->has_template) return fail(TWOSD_E_STATE, "picks_keep: no template");
+    if (!handle) return fail(TWOSD_E_ARG, "picks_keep: handle is NULL");
+    if (epi < 0 || epi >= (int)c->epis.size()) return fail(TWOSD_E_ARG, "picks_keep: epigraph %d does not exist", epi);
+    if (c->last_cut_epi < 0)
+        return fail(TWOSD_E_STATE, "picks_keep: no cut to keep the picks of (none built, or the template, the positions or "
+                    "the vertex set were reset since)");
+    if (c->last_cut_epi != epi)
+        return fail(TWOSD_E_STATE, "picks_keep: the last cut was built on epigraph %d, not %d", c->last_cut_epi, epi);
+    const int *arg = cut_last_arg(c);
+    if (c->last_cut_n <= 0 || !arg)
+        return fail(TWOSD_E_STATE, "picks_keep: the last cut of epigraph %d took the empty-epigraph path (no picks)", epi);
+    HIPCHK(hipSetDevice(c->device));
+    std::vector<PickSet> &v = c->boot.picks;
+    int id = 0;
+    while (id < (int)v.size() && v[id].live) ++id;
+    if (id == (int)v.size()) v.emplace_back();
+    PickSet &h = v[id];
+    int rc;
+    if ((rc = h.d.alloc(c->last_cut_n))) return rc;
+    HIPCHK(hipMemcpyAsync(h.d, arg, sizeof(int) * c->last_cut_n, hipMemcpyDeviceToDevice, c->stream));
+    h.epi = epi; h.n = c->last_cut_n; h.nv = c->last_cut_nv; h.live = true; h.stale = false;
+    *handle = id;
+    return TWOSD_OK;
+}
+
+extern "C" int twosd_picks_info(twosd_ctx *c, int handle, int *epi, int *n, int *nv) {
+    if (!c) return fail(TWOSD_E_ARG, "picks_info: ctx is NULL");
+    PickSet *h = nullptr;
+    int rc = usable_pick(c, handle, "picks_info", &h);
+    if (rc) return rc;
+    if (epi) *epi = h->epi;
+    if (n) *n = h->n;
+    if (nv) *nv = h->nv;
+    return TWOSD_OK;
+}
+
+extern "C" int twosd_picks_get(twosd_ctx *c, int handle, int *out) {
+    if (!c || !out) return fail(TWOSD_E_ARG, "picks_get: NULL");
+    PickSet *h = nullptr;
+    int rc = usable_pick(c, handle, "picks_get", &h);
+    if (rc) return rc;
+    HIPCHK(hipSetDevice(c->device));
+    HIPCHK(hipMemcpyAsync(out, h->d, sizeof(int) * h->n, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    return TWOSD_OK;
+}
+
+extern "C" int twosd_picks_release(twosd_ctx *c, int handle) {
+    if (!c) return fail(TWOSD_E_ARG, "picks_release: ctx is NULL");
+    PickSet *h = pick_of(c, handle);
+    if (!h) return fail(TWOSD_E_ARG, "picks_release: pick handle %d does not exist", handle);
+    HIPCHK(hipSetDevice(c->device));
+    HIPCHK(hipStreamSynchronize(c->stream));   // a re-formation reading it has finished
+    *h = PickSet();
+    return TWOSD_OK;
+}
+
+extern "C" int twosd_picks_count(twosd_ctx *c, int *live) {
+    if (!c || !live) return fail(TWOSD_E_ARG, "picks_count: NULL");
+    int n = 0;
+    for (const PickSet &h : c->boot.picks) n += h.live ? 1 : 0;
+    *live = n;
+    return TWOSD_OK;
+}
+
+extern "C" int twosd_reform_partial_len(twosd_ctx *c, int H, const int *handles, int M, int64_t *n_u64, int64_t *n_f64) {
+    BootLayout L;
+    int rc = boot_layout(c, -1, H, handles, M, "reform_partial_len", &L);
+    if (rc) return rc;
+    if (n_u64) *n_u64 = (int64_t)L.n_u64;
+    if (n_f64) *n_f64 = (int64_t)L.n_f64;
+    return TWOSD_OK;
+}
+
+static int check_epi(twosd_ctx *c, int epi, const char *what) {
+    if (!c || !c->has_template) return fail(TWOSD_E_STATE, "%s: no template", what);
+    if (epi < 0 || epi >= (int)c->epis.size()) return fail(TWOSD_E_ARG, "%s: epigraph %d does not exist", what, epi);
+    return TWOSD_OK;
+}
+
+extern "C" int twosd_reform_partial(twosd_ctx *c, int epi, int H, const int *handles, int M, uint64_t seed, uint64_t index_offset,
+                                    double total_weight, uint64_t *d_u64, double *d_f64) {
+    BootLayout L;
+    int rc = boot_layout(c, -1, H, handles, M, "reform_partial", &L);   // a dropped handle is named before the epigraph
+    if (rc || (rc = check_epi(c, epi, "reform_partial")) || (rc = boot_layout(c, epi, H, handles, M, "reform_partial", &L))) return rc;
+    if (!d_u64 || !d_f64) return fail(TWOSD_E_ARG, "reform_partial: device buffers NULL");
+    if (!(total_weight > 0.0) || !std::isfinite(total_weight)) return fail(TWOSD_E_ARG, "reform_partial: total_weight must be > 0");
+    HIPCHK(hipSetDevice(c->device));
+    if ((rc = boot_partial_impl(c, epi, L, handles, M, seed, index_offset, total_weight, (unsigned long long *)d_u64, d_f64))) return rc;
+    HIPCHK(hipStreamSynchronize(c->stream));
+    return TWOSD_OK;
+}
+
+extern "C" int twosd_reform_finalize(twosd_ctx *c, int H, const int *handles, int M, double total_weight, const uint64_t *d_u64,
+                                     const double *d_f64, double *alpha, double *beta, double *weight_mark, double *total_weight_out) {
+    BootLayout L;
+    int rc = boot_layout(c, -1, H, handles, M, "reform_finalize", &L);
+    if (rc) return rc;
+    if (!d_u64 || !d_f64 || !alpha || (c->n1 > 0 && !beta)) return fail(TWOSD_E_ARG, "reform_finalize: NULL buffers");
+    if (!(total_weight > 0.0) || !std::isfinite(total_weight)) return fail(TWOSD_E_ARG, "reform_finalize: total_weight must be > 0");
+    HIPCHK(hipSetDevice(c->device));
+    return boot_finalize_impl(c, L, handles, total_weight, (const unsigned long long *)d_u64, d_f64, alpha, beta, weight_mark,
+                              total_weight_out);
+}
+
+extern "C" int twosd_reform_cuts(twosd_ctx *c, int epi, int H, const int *handles, int M, uint64_t seed, uint64_t index_offset,
+                                 double *alpha, double *beta, double *weight_mark, double *total_weight) {
+    BootLayout L;
+    int rc = boot_layout(c, -1, H, handles, M, "reform_cuts", &L);
+    if (rc || (rc = check_epi(c, epi, "reform_cuts")) || (rc = boot_layout(c, epi, H, handles, M, "reform_cuts", &L))) return rc;
+    if (!alpha || (c->n1 > 0 && !beta)) return fail(TWOSD_E_ARG, "reform_cuts: alpha/beta NULL");
+    const EpiDevice &E = c->epis[epi];
+    if (!(E.total_weight > 0.0)) return fail(TWOSD_E_STATE, "reform_cuts: epigraph %d holds no scenario weight", epi);
+    HIPCHK(hipSetDevice(c->device));
+    if ((rc = c->boot.u64.fit(L.n_u64)) || (rc = c->boot.f64.fit(L.n_f64))) return rc;
+    HIPCHK(hipEventRecord(c->ev[4], c->stream));
+    if ((rc = boot_partial_impl(c, epi, L, handles, M, seed, index_offset, E.total_weight, c->boot.u64, c->boot.f64))) return rc;
+    HIPCHK(hipEventRecord(c->ev[5], c->stream));
+    if ((rc = boot_finalize_impl(c, L, handles, E.total_weight, c->boot.u64, c->boot.f64, alpha, beta, weight_mark, total_weight)))
+        return rc;
+    HIPCHK(hipEventRecord(c->ev[6], c->stream));
+    HIPCHK(hipEventSynchronize(c->ev[6]));
+    float ms1 = 0, ms2 = 0;
+    hipEventElapsedTime(&ms1, c->ev[4], c->ev[5]);
+    hipEventElapsedTime(&ms2, c->ev[5], c->ev[6]);
+    c->boot.ms[0] = ms1;
+    c->boot.ms[1] = ms2;
+    return TWOSD_OK;
+}
+
+extern "C" int twosd_reform_last_ms(twosd_ctx *c, double *ms2) {
+    if (!c || !ms2) return fail(TWOSD_E_ARG, "reform_last_ms: NULL");
+    ms2[0] = c->boot.ms[0];
+    ms2[1] = c->boot.ms[1];
+    return TWOSD_OK;
+}

@@ -1562,12 +1562,17 @@ static CutWs *cws(twosd_ctx *c) {
 void cut_free(CutWs *w) { delete w; }
 
 void cut_truncate_pk(twosd_ctx *c, int size) {
+    // stored picks over vertices past `size` name vertices that no longer exist
+    for (PickSet &h : c->boot.picks)
+        if (h.live && h.nv > size) h.stale = true;
+    if (c->last_cut_nv > size) c->last_cut_epi = -1;
     if (!c->cut_ws) return;
     CutWs *w = c->cut_ws.get();
     if (w->pk_count > size) w->pk_count = size;   // twin links point to lower vertices: still valid
 }
 
 void cut_invalidate_pk(twosd_ctx *c) {
+    c->last_cut_epi = -1;
     if (!c->cut_ws) return;
     CutWs *w = c->cut_ws.get();
     w->pk_count = 0;
@@ -1971,6 +1976,16 @@ static int cut_finalize_impl(twosd_ctx *c, const double *x, const unsigned long 
     return TWOSD_OK;
 }
 
+const int *cut_last_arg(twosd_ctx *c) { return c->cut_ws ? c->cut_ws->arg.p : nullptr; }
+
+int cut_pk_current(twosd_ctx *c, const double **PK, int *k4) {
+    int rc = update_pk(c);
+    if (rc) return rc;
+    *PK = c->cut_ws->PK;
+    *k4 = c->cut_ws->pk_k4;
+    return TWOSD_OK;
+}
+
 }  // namespace twosd
 
 using namespace twosd;
@@ -1995,7 +2010,9 @@ extern "C" int twosd_build_cut(twosd_ctx *c, int epi, const double *x, double ti
     const int nv = c->dvs.size;
     if ((rc = w->hist.fit(nv))) return rc;
     if ((rc = w->sums.fit(c->k + 1))) return rc;
+    c->last_cut_epi = -1;   // set again once this cut's picks are in place (twosd_picks_keep)
     if (E.count == 0 || E.total_weight <= 0.0) {
+        c->last_cut_epi = epi; c->last_cut_n = 0; c->last_cut_nv = nv;
         // no scenarios: the reference returns the zero cut with weight_mark = total weight
         *alpha = 0.0;
         for (int j = 0; j < c->n1; ++j) beta[j] = 0.0;
@@ -2013,6 +2030,7 @@ extern "C" int twosd_build_cut(twosd_ctx *c, int epi, const double *x, double ti
     hipEventElapsedTime(&ms2, c->ev[5], c->ev[6]);
     c->t_us[2] = 1e3 * ms1;
     c->t_us[3] = 1e3 * ms2;
+    c->last_cut_epi = epi; c->last_cut_n = E.count; c->last_cut_nv = nv;
     if (weight_mark) *weight_mark = E.total_weight;
     if (max_val) HIPCHK(hipMemcpy(max_val, w->val, sizeof(double) * E.count, hipMemcpyDeviceToHost));
     if (max_val && c->has_bounds)   // scores of the canonical LP: the caller's objective adds the shift's constant
@@ -2070,7 +2088,9 @@ extern "C" int twosd_cut_partial(twosd_ctx *c, int epi, const double *x, double 
     if (!(total_weight > 0.0)) return fail(TWOSD_E_ARG, "cut_partial: total_weight must be > 0");
     HIPCHK(hipSetDevice(c->device));
     const EpiDevice &E = c->epis[epi];
+    c->last_cut_epi = -1;
     if (E.count == 0) {
+        c->last_cut_epi = epi; c->last_cut_n = 0; c->last_cut_nv = c->dvs.size;
         HIPCHK(hipMemsetAsync(d_hist, 0, sizeof(uint64_t) * std::max(c->dvs.size, 1), c->stream));
         HIPCHK(hipMemsetAsync(d_sums, 0, sizeof(double) * (c->k + 1), c->stream));
         HIPCHK(hipStreamSynchronize(c->stream));
@@ -2083,6 +2103,7 @@ extern "C" int twosd_cut_partial(twosd_ctx *c, int epi, const double *x, double 
     float ms = 0;
     hipEventElapsedTime(&ms, c->ev[4], c->ev[5]);
     c->t_us[2] = 1e3 * ms;
+    c->last_cut_epi = epi; c->last_cut_n = E.count; c->last_cut_nv = c->dvs.size;
     CutWs *w = cws(c);
     if (max_val) HIPCHK(hipMemcpy(max_val, w->val, sizeof(double) * E.count, hipMemcpyDeviceToHost));
     if (max_val && c->has_bounds)   // scores of the canonical LP: the caller's objective adds the shift's constant

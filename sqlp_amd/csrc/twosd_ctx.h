@@ -29,6 +29,31 @@ struct PoolBasis {
     int hb_row = -1;              // >= 0: head not materialised yet; row of c->pool_hb (4 head + type)
 };
 
+// stored picks of one cut (twosd_picks_keep): the argmax's vertex index of each of the n scenarios
+// the epigraph held then, over the first nv vertices of the set
+struct PickSet {
+    DevBuf<int> d;                // n picks
+    int epi = -1, n = 0, nv = 0;
+    bool live = false;
+    bool stale = false;           // the vertex set was truncated below nv since: unusable
+};
+
+// bootstrap re-formation (boot_kernel.hip): the pick handles, the template's device copies the
+// finalize kernel reads, and the workspaces of a call.  twosd_set_template and
+// twosd_set_random_positions assign a fresh one (every handle dropped).
+struct BootState {
+    std::vector<PickSet> picks;
+    bool tmpl_ready = false;
+    DevBuf<double> d_T, d_r;      // dense T (m x n1), r (m)
+    DevBuf<int> d_col;            // k: first-stage column of each random element, -1 for an rhs element
+    DevBuf<double> slots, gpart;  // the blocks' S partials of one handle; the vertex chunks' g partials
+    DevBuf<double> d_alpha, d_beta, d_wm;   // outputs of a call, (M + 1) x H rows
+    DevBuf<unsigned long long> u64;   // twosd_reform_cuts' own partial buffers (the split's are the caller's)
+    DevBuf<double> f64;
+    DevBuf<uint8_t> counts;
+    double ms[2] = {0, 0};        // device time of the last twosd_reform_cuts: partial sums, finalize (with its copies)
+};
+
 struct CutWs;    // cut_kernel.hip
 struct DvsWs;    // dvs_kernel.hip
 struct VkeyWs;   // vkey.hip
@@ -159,6 +184,10 @@ struct TemplateState {
     std::unique_ptr<twosd::DvsWs, void (*)(twosd::DvsWs *)> dvs_ws{nullptr, twosd::dvs_free};   // dvs scratch (dvs_kernel.hip)
     // cut workspace (cut_kernel.hip)
     std::unique_ptr<twosd::CutWs, void (*)(twosd::CutWs *)> cut_ws{nullptr, twosd::cut_free};
+    // the last twosd_build_cut / twosd_cut_partial whose picks still sit in the cut workspace:
+    // its epigraph (-1: none, or invalidated since), scenarios (0: the empty-epigraph path), |V|
+    int last_cut_epi = -1, last_cut_n = 0, last_cut_nv = 0;
+    twosd::BootState boot;        // stored picks and the re-formation's buffers (boot_kernel.hip)
     // dual-vertex key workspace (vkey.hip) and the key output of the LP kernel
     std::unique_ptr<twosd::VkeyWs, void (*)(twosd::VkeyWs *)> vkey_ws{nullptr, twosd::vkey_free};
     twosd::DevBuf<unsigned long long> d_vkey, d_bkey;
@@ -252,4 +281,8 @@ int dvs_push_device(twosd_ctx *c, int count, const double *d_pis, int *d_out_ind
 // cut (cut_kernel.hip)
 void cut_invalidate_pk(twosd_ctx *c);
 void cut_truncate_pk(twosd_ctx *c, int size);   // V truncated to size: PK rows past it are stale
+// for boot_kernel.hip: the picks of the last cut (device, last_cut_n ints), and PK (|V| x k4,
+// brought up to date with the vertex set)
+const int *cut_last_arg(twosd_ctx *c);
+int cut_pk_current(twosd_ctx *c, const double **PK, int *k4);
 }  // namespace twosd

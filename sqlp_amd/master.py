@@ -295,10 +295,26 @@ class sdCell:
     def solve_master(self):
         """optimize!(cell.master) (algorithm.jl:104-112): returns x; stores the cut-row
         multipliers for the next iteration's cut removal."""
+        epi_rows, alpha, beta, _ = self.cuts.rows()
+        res, lam, obj = self.solve_master_rows(epi_rows, alpha, beta)
+        self.master_status = res.status
+        if res.status != OPTIMAL:
+            raise RuntimeError(f"master not solved: {res.status}")
+        # multiplier of every master row, in master order, for remove_cuts_by_multiplier
+        self._row_duals = lam
+        self.master_obj = obj
+        return res.z[:self.n1].copy()
+
+    def solve_master_rows(self, epi_rows, alpha, beta):
+        """The cell's regularised master (root-stage rows and bounds, prox term of the current rho
+        and centre) over the given epigraph rows eta_epi >= alpha + beta'x: (QPResult, the cut rows'
+        multipliers, objective value with the prox constant).  Changes nothing in the cell;
+        solve_master is this on the cell's own rows (the stopping rule passes re-formed ones)."""
         E = len(self.epi)
         n1 = self.n1
         nz = n1 + E
-        epi_rows, alpha, beta, _ = self.cuts.rows()
+        epi_rows = np.asarray(epi_rows, dtype=np.int64)
+        alpha = np.asarray(alpha, dtype=np.float64)
         for e in range(E):
             if not np.any(epi_rows == e):
                 raise RuntimeError(f"epigraph {e} has no cut: the master is unbounded")
@@ -315,15 +331,9 @@ class sdCell:
             Gc[np.arange(len(alpha)), n1 + epi_rows] = -1.0
         Gb, hb = _bound_rows(self.sp1.ylb, self.sp1.yub, nz)
         res = qp_solve(H, g, Aeq, beq, np.vstack([G, Gc, Gb]), np.concatenate([h, -alpha, hb]))
-        self.master_status = res.status
-        if res.status != OPTIMAL:
-            raise RuntimeError(f"master not solved: {res.status}")
         lam = res.lam[G.shape[0]:G.shape[0] + len(alpha)]
-        # multiplier of every master row, in master order, for remove_cuts_by_multiplier
-        self._row_duals = lam
         const = 0.5 * self.rho * float(self.reg_center @ self.reg_center) if self.reg_center is not None else 0.0
-        self.master_obj = res.obj + const
-        return res.z[:n1].copy()
+        return res, lam, res.obj + const
 
     def cut_duals(self):
         """Per epigraph, the multipliers of its non-incumbent cut rows (epicon_ref order)."""
@@ -333,11 +343,13 @@ class sdCell:
 
 
 def sd_iteration(cell: sdCell, scenario_list, update_incumbent_cut=True, quad_scalar_schedule=None,
-                 tie_rel=0.0):
+                 tie_rel=0.0, keep_picks=False):
     """sd_iteration! (algorithm.jl:39-115).  scenario_list[i] = element values (k) of the new
     scenario of epigraph i.  Steps 1-3 and 5-6 (the data-parallel hot segment) run on the GPU
     (twosd.sd_iteration_solve / sd_iteration_cuts); cut removal, incumbent selection,
-    the prox schedule and the master solve run here."""
+    the prox schedule and the master solve run here.  keep_picks: every new cut keeps its argmax
+    picks on the device (for stopping.bootstrap_gap_test), and the picks of cuts that left the
+    epigraphs are released."""
     if quad_scalar_schedule is None:
         quad_scalar_schedule = ConstantQuadScalarSchedule(0.1)
     assert len(scenario_list) == len(cell.epi)                        # algorithm.jl:42
@@ -348,7 +360,10 @@ def sd_iteration(cell: sdCell, scenario_list, update_incumbent_cut=True, quad_sc
         cell.cuts.remove_cuts_by_multiplier(cell.epi, cell.cut_duals())
     epi_info_last = [twosd.sdEpigraphInfo.of(e) for e in cell.epi]    # algorithm.jl:76
     twosd.sd_iteration_cuts(cell.epi, cell.x_candidate, cell.x_incumbent, cell.dual_vertices,
-                            update_incumbent_cut=update_incumbent_cut, tie_rel=tie_rel)
+                            update_incumbent_cut=update_incumbent_cut, tie_rel=tie_rel, keep_picks=keep_picks)
+    if keep_picks:   # removed cuts and the replaced incumbent cut no longer need their picks
+        for epi in cell.epi:
+            twosd.release_unused_picks(epi)
     cell.improvement_info = twosd.check_improvement(
         epi_info_last, cell.epi, cell.objf_original(cell.x_candidate), cell.objf_original(cell.x_incumbent),
         cell.x_candidate, cell.x_incumbent)
@@ -358,3 +373,27 @@ def sd_iteration(cell: sdCell, scenario_list, update_incumbent_cut=True, quad_sc
     cell.add_regularization(cell.x_incumbent, rho)
     cell.sync_cuts()
     cell.x_candidate = cell.solve_master()
+
+
+def sd_run(cell: sdCell, next_scenarios, max_iter, min_iter=0, check_every=10, stop=None, **iteration_args):
+    """The SD loop with its in-sample stopping rule (the reference has none: its readme lists
+    "Need to implement stopping criteria", plugin/stopping_rule.jl is empty).  Runs
+    sd_iteration(cell, next_scenarios(it), keep_picks=True) for it = 0, 1, ... and, every
+    check_every iterations once min_iter have run, calls stop(cell) -- default
+    stopping.bootstrap_gap_test -- ending when its result has .passed, or after max_iter.
+    Returns (iterations run, the last test result or None)."""
+    if check_every < 1:
+        raise ValueError("check_every must be at least 1")
+    if stop is None:
+        from . import stopping
+        stop = stopping.bootstrap_gap_test
+    result = None
+    it = 0
+    while it < max_iter:
+        sd_iteration(cell, next_scenarios(it), keep_picks=True, **iteration_args)
+        it += 1
+        if it >= min_iter and it % check_every == 0:
+            result = stop(cell)
+            if result.passed:
+                break
+    return it, result

@@ -16,6 +16,7 @@ from __future__ import annotations
 
 import ctypes as C
 from dataclasses import dataclass, field
+from typing import Optional
 
 import numpy as np
 
@@ -95,10 +96,12 @@ def canonical_form(W, q, r, sense, ylb=None, yub=None) -> CanonicalForm:
 
 @dataclass
 class sdCut:
-    """eta >= alpha + beta'x (epigraph.jl:5-12); never scaled."""
+    """eta >= alpha + beta'x (epigraph.jl:5-12); never scaled.  picks: the handle of the argmax
+    picks the cut was built with (twosd_picks_keep; build_sasa_cut(keep_picks=True)), or None."""
     alpha: float
     beta: np.ndarray
     weight_mark: float
+    picks: Optional[int] = None
 
 
 class SDContext:
@@ -541,6 +544,7 @@ class sdEpigraph:
         self.scenario_weight: list = []
         self.cuts: list = []
         self.incumbent_cut = None
+        self._pick_handles: set = set()   # live pick handles kept for this epigraph's cuts
 
     @property
     def total_scenario_weight(self) -> float:
@@ -811,10 +815,154 @@ def argmax_procedure(epi: sdEpigraph, x, dual_vertices: sdDualVertexSet, tie_rel
     return mv, ma
 
 
-def build_sasa_cut(epi: sdEpigraph, x, dual_vertices: sdDualVertexSet, tie_rel=DEFAULT_TIE_REL) -> sdCut:
-    """build_sasa_cut(epi, x, V) (epigraph.jl:125-146)."""
+def build_sasa_cut(epi: sdEpigraph, x, dual_vertices: sdDualVertexSet, tie_rel=DEFAULT_TIE_REL,
+                   keep_picks=False) -> sdCut:
+    """build_sasa_cut(epi, x, V) (epigraph.jl:125-146).  keep_picks: the cut carries a handle of
+    its argmax picks (cut.picks, 4 bytes per scenario on the device) for reform_cuts; a cut of an
+    epigraph without scenarios has none."""
     cut, _, _ = _build_cut(epi, x, tie_rel, want_argmax=False)
+    if keep_picks and epi.num_scenarios > 0 and epi.total_scenario_weight > 0.0:
+        cut.picks = keep_picks_of_last_cut(epi)
     return cut
+
+
+# -- stored picks and bootstrap re-formation (the in-sample stopping rule's device part; the
+#    reference's plugin/stopping_rule.jl is an empty file) ------------------------------------
+def keep_picks_of_last_cut(epi: sdEpigraph) -> int:
+    """twosd_picks_keep: a handle of the picks of the last cut built on epi."""
+    h = C.c_int()
+    check(epi.ctx.lib.twosd_picks_keep(epi.ctx.h, epi.index, C.byref(h)))
+    epi._pick_handles.add(h.value)
+    return h.value
+
+
+def picks_info(ctx: SDContext, handle):
+    """(epigraph index, scenarios, |V|) of a pick handle."""
+    e, n, nv = C.c_int(), C.c_int(), C.c_int()
+    check(ctx.lib.twosd_picks_info(ctx.h, int(handle), C.byref(e), C.byref(n), C.byref(nv)))
+    return e.value, n.value, nv.value
+
+
+def picks_get(ctx: SDContext, handle) -> np.ndarray:
+    """The stored picks (0-based vertex indices) of a handle."""
+    out = np.zeros(picks_info(ctx, handle)[1], dtype=np.int32)
+    check(ctx.lib.twosd_picks_get(ctx.h, int(handle), ptr(out)))
+    return out
+
+
+def picks_release(ctx: SDContext, handle):
+    check(ctx.lib.twosd_picks_release(ctx.h, int(handle)))
+
+
+def picks_count(ctx: SDContext) -> int:
+    """Live pick handles of the context."""
+    n = C.c_int()
+    check(ctx.lib.twosd_picks_count(ctx.h, C.byref(n)))
+    return n.value
+
+
+def bootstrap_count_of_word(u: int) -> int:
+    """Poisson(1) count of a uniform 32-bit word (twosd_bootstrap_count_of_word; host code)."""
+    return int(_lib.load().twosd_bootstrap_count_of_word(C.c_uint32(int(u))))
+
+
+def bootstrap_counts(ctx: SDContext, M, seed, first_index, count) -> np.ndarray:
+    """The device draw of the replicate counts of scenarios [first_index, first_index + count):
+    uint8 (count, M)."""
+    out = np.zeros((int(count), int(M)), dtype=np.uint8)
+    check(ctx.lib.twosd_bootstrap_counts(ctx.h, int(M), C.c_uint64(seed), C.c_uint64(first_index), C.c_int64(count),
+                                         ptr(out)))
+    return out
+
+
+@dataclass
+class ReformedCuts:
+    """reform_cuts' result: row 0 the identity replicate, row 1 + b bootstrap replicate b."""
+    alpha: np.ndarray          # (M + 1, H)
+    beta: np.ndarray           # (M + 1, H, n1)
+    weight_mark: np.ndarray    # (M + 1, H)
+    total_weight: np.ndarray   # (M + 1,)
+
+    def cut(self, b, j) -> sdCut:
+        return sdCut(float(self.alpha[b, j]), self.beta[b, j], float(self.weight_mark[b, j]))
+
+
+def _handles_of(cuts):
+    hs = []
+    for cut in cuts:
+        h = cut.picks if isinstance(cut, sdCut) else cut
+        if h is None:
+            raise ValueError("reform_cuts: a cut carries no picks (build it with keep_picks=True)")
+        hs.append(int(h))
+    return np.ascontiguousarray(hs, dtype=np.int32)
+
+
+def reform_cuts(epi: sdEpigraph, cuts, M, seed, index_offset=0) -> ReformedCuts:
+    """twosd_reform_cuts: every cut of `cuts` (sdCut with picks, or pick handles) re-formed from its
+    picks under the identity weights (row 0) and M Poisson(1) bootstrap replicates of the scenario
+    weights (seed; index_offset = the global index of the epigraph's first scenario)."""
+    ctx = epi.ctx
+    hs = _handles_of(cuts)
+    H, B = len(hs), int(M) + 1
+    alpha = np.zeros((B, H))
+    beta = np.zeros((B, H, ctx.n1))
+    wm = np.zeros((B, H))
+    tw = np.zeros(B)
+    check(ctx.lib.twosd_reform_cuts(ctx.h, epi.index, H, ptr(hs), int(M), C.c_uint64(seed), C.c_uint64(index_offset),
+                                    ptr(alpha), ptr(beta), ptr(wm), ptr(tw)))
+    return ReformedCuts(alpha, beta, wm, tw)
+
+
+def reform_last_ms(ctx: SDContext):
+    """Device milliseconds of the last reform_cuts: [partial sums, finalize]."""
+    out = np.zeros(2)
+    check(ctx.lib.twosd_reform_last_ms(ctx.h, ptr(out)))
+    return out
+
+
+def reform_partial_len(ctx: SDContext, cuts, M):
+    hs = _handles_of(cuts)
+    a, b = C.c_int64(), C.c_int64()
+    check(ctx.lib.twosd_reform_partial_len(ctx.h, len(hs), ptr(hs), int(M), C.byref(a), C.byref(b)))
+    return a.value, b.value
+
+
+def reform_partial(epi: sdEpigraph, cuts, M, seed, index_offset, total_weight, d_u64_ptr, d_f64_ptr):
+    """This rank's part of reform_cuts into caller device buffers (reform_partial_len entries);
+    total_weight: the global total scenario weight, the same on every rank."""
+    ctx = epi.ctx
+    hs = _handles_of(cuts)
+    check(ctx.lib.twosd_reform_partial(ctx.h, epi.index, len(hs), ptr(hs), int(M), C.c_uint64(seed),
+                                       C.c_uint64(index_offset), float(total_weight), C.c_void_p(d_u64_ptr),
+                                       C.c_void_p(d_f64_ptr)))
+
+
+def reform_finalize(ctx: SDContext, cuts, M, total_weight, d_u64_ptr, d_f64_ptr) -> ReformedCuts:
+    """The re-formed cuts from the ranks' summed partial buffers."""
+    hs = _handles_of(cuts)
+    H, B = len(hs), int(M) + 1
+    alpha = np.zeros((B, H))
+    beta = np.zeros((B, H, ctx.n1))
+    wm = np.zeros((B, H))
+    tw = np.zeros(B)
+    check(ctx.lib.twosd_reform_finalize(ctx.h, H, ptr(hs), int(M), float(total_weight), C.c_void_p(d_u64_ptr),
+                                        C.c_void_p(d_f64_ptr), ptr(alpha), ptr(beta), ptr(wm), ptr(tw)))
+    return ReformedCuts(alpha, beta, wm, tw)
+
+
+def release_unused_picks(epi: sdEpigraph, keep=()) -> int:
+    """Release the pick handles of epi's context that belong to epi and are referenced neither by
+    epi.cuts nor by epi.incumbent_cut (nor listed in `keep`); returns how many were released."""
+    used = {int(h) for h in keep}
+    for cut in list(epi.cuts) + [epi.incumbent_cut]:
+        if cut is not None and cut.picks is not None:
+            used.add(int(cut.picks))
+    freed = 0
+    for h in sorted(epi._pick_handles - used):
+        picks_release(epi.ctx, h)
+        epi._pick_handles.discard(h)
+        freed += 1
+    return freed
 
 
 def _build_cut(epi, x, tie_rel, want_argmax):
@@ -881,13 +1029,14 @@ def sd_iteration_solve(epis, scenario_values, x_candidate, x_incumbent, V: sdDua
 
 
 def sd_iteration_cuts(epis, x_candidate, x_incumbent, V: sdDualVertexSet, update_incumbent_cut=True,
-                      tie_rel=DEFAULT_TIE_REL):
+                      tie_rel=DEFAULT_TIE_REL, keep_picks=False):
     """algorithm.jl:79-85: build_sasa_cut at x_candidate appended to epi.cuts and, if
-    update_incumbent_cut, at x_incumbent as epi.incumbent_cut."""
+    update_incumbent_cut, at x_incumbent as epi.incumbent_cut.  keep_picks: every new cut carries
+    its picks (build_sasa_cut)."""
     for epi in epis:
-        epi.cuts.append(build_sasa_cut(epi, x_candidate, V, tie_rel))
+        epi.cuts.append(build_sasa_cut(epi, x_candidate, V, tie_rel, keep_picks=keep_picks))
         if update_incumbent_cut:
-            epi.incumbent_cut = build_sasa_cut(epi, x_incumbent, V, tie_rel)
+            epi.incumbent_cut = build_sasa_cut(epi, x_incumbent, V, tie_rel, keep_picks=keep_picks)
 
 
 def sd_iteration_hot_path(epis, scenario_values, x_candidate, x_incumbent, V: sdDualVertexSet,
