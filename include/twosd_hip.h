@@ -262,6 +262,36 @@ int twosd_add_sampled_scenarios(twosd_ctx *ctx, int epi, int N, uint64_t seed, u
                                 const double *weights);
 int twosd_get_scenarios(twosd_ctx *ctx, int epi, int first, int count, double *values);
 
+/*
+ * Variance-reduced scenario streams (no reference counterpart: the reference's readme lists
+ * "Implement SMPS sampling methods (antithetic, stratified)" as open).  A sampling plan makes
+ * groups of `group` = G consecutive global scenario indices [G b, G b + G) dependent; a stream
+ * stays a pure function of (seed, global index, element, plan), so any sharding on group
+ * boundaries reproduces it.  With u1, u2 the uniforms the i.i.d. sampler forms for (index g,
+ * element e) from Philox counter (g_lo, g_hi, e, 0):
+ *   IID         the stream of twosd_add_sampled_scenarios, bit for bit (a NULL plan means IID).
+ *   ANTITHETIC  pair p = g >> 1; both members use the words of index 2p.  The even member is the
+ *               i.i.d. draw of index 2p; the odd member mirrors it: DISCRETE and UNIFORM at
+ *               1 - u1, NORMAL with the Box-Muller z negated.
+ *   LHS         block b = g / S, position j = g % S: per (b, e) a uniform random permutation perm of
+ *               0..S-1 (inside-out Fisher-Yates: for i = 1..S-1, t = mulhi32(word_i, i + 1),
+ *               perm[i] = perm[t], perm[t] = i; word_i = word i & 3 of Philox counter
+ *               (b_lo, b_hi, e, 2 + (i >> 2))), and member j draws at
+ *               u = min((perm[j] + u1(g, e)) / S, 1 - 2^-53): DISCRETE and UNIFORM as the i.i.d.
+ *               sampler at u, NORMAL mean + sd * Phi^-1(max(u, 2^-54)).
+ * Every call that takes a plan requires its first index, its count and its batch to be multiples
+ * of G; TWOSD_E_ARG otherwise, and for an unknown mode, a group that contradicts the mode
+ * (IID: 1, ANTITHETIC: 2) or S outside [2, 256].
+ */
+#define TWOSD_SAMPLING_IID        0   /* group 1 */
+#define TWOSD_SAMPLING_ANTITHETIC 1   /* group 2 */
+#define TWOSD_SAMPLING_LHS        2   /* group S, 2 <= S <= 256, any integer */
+typedef struct twosd_sampling { int mode; int group; } twosd_sampling;
+
+/* twosd_add_sampled_scenarios under a sampling plan (NULL / IID: that call itself). */
+int twosd_add_sampled_scenarios_vr(twosd_ctx *ctx, int epi, int N, uint64_t seed, uint64_t first_index,
+                                   const double *weights, const twosd_sampling *plan);
+
 /* evaluate(sp1, sp2, sto, x; N) (smps_routines.jl:67-82), stage-2 part, on device-drawn
  * scenarios [first, first+count) of the stream `seed` (a shard of N_total):
  * *s2 = sum in index order of (1/N_total) * obj.  The caller adds c'x (and, across ranks,
@@ -318,6 +348,39 @@ int twosd_evaluate_paired(twosd_ctx *ctx, const double *xa, const double *xb, in
 int twosd_evaluate_ci(twosd_ctx *ctx, const double *x, uint64_t seed, int64_t first, int64_t batch, int64_t n_max,
                       double z, double rel_tol, double abs_tol, double offset, twosd_moments *out,
                       double *half_width, int *converged);
+
+/*
+ * The estimators above on a variance-reduced stream (twosd_sampling).  The members of a group
+ * are dependent, so the observations are the GROUP MEANS: in every twosd_moments these calls
+ * return, n and n_bad count groups (a group counts only if all G of its LPs are optimal; the
+ * values of a group left out are never read into a sum), and mean, m2, min and max are of group
+ * means.  The scenarios behind a record are G (n + n_bad).  The mean of a group v[0 .. G) is
+ * K + (sum_{i = 0 .. G-1} (v[i] - K)) / G with K = v[0], the sum taken in index order from 0.0,
+ * every operation rounded to nearest, no fused multiply-add -- the same bits under any launch
+ * shape.  The moments of the means are those of twosd_moments_of_values, taken per chunk on
+ * m_b - K0 with K0 = the chunk's entry 0 (0 when that entry is not optimal or not finite) and K0
+ * added back to mean, min and max: the records merge at the size of the spread, and min / max are
+ * the means' own bits whenever m_b / 2 <= K0 <= 2 m_b.  A NULL plan or G = 1 is the namesake call
+ * itself.
+ *   moments_of_values_grouped: the caller's obj[n] / status[n] (nullable) in groups of G,
+ *     1 <= G <= 256; TWOSD_E_ARG unless n is a multiple of G.
+ *   evaluate_moments_vr / _paired_vr: first and count multiples of G.  The chunk of 2^20
+ *     scenarios is rounded down to a multiple of G.  Paired: a and b are reduced to group means and
+ *     diff holds the moments of mean_a - mean_b per group.
+ *   evaluate_ci_vr: first and batch multiples of G with batch / G >= 2; n_max is clipped down to
+ *     a multiple of G (TWOSD_E_ARG if that leaves less than batch).  The stop rule is
+ *     twosd_evaluate_ci's on the group moments: hw = z sqrt(m2 / (n - 1) / n), n in groups.
+ */
+int twosd_moments_of_values_grouped(twosd_ctx *ctx, int64_t n, int G, const double *obj, const int *status,
+                                    twosd_moments *out);
+int twosd_evaluate_moments_vr(twosd_ctx *ctx, const double *x, int64_t first, int64_t count, uint64_t seed,
+                              twosd_moments *out, const twosd_sampling *plan);
+int twosd_evaluate_paired_vr(twosd_ctx *ctx, const double *xa, const double *xb, int64_t first, int64_t count,
+                             uint64_t seed, twosd_moments *a, twosd_moments *b, twosd_moments *diff,
+                             const twosd_sampling *plan);
+int twosd_evaluate_ci_vr(twosd_ctx *ctx, const double *x, uint64_t seed, int64_t first, int64_t batch, int64_t n_max,
+                         double z, double rel_tol, double abs_tol, double offset, twosd_moments *out,
+                         double *half_width, int *converged, const twosd_sampling *plan);
 
 /*
  * solve_problem! (smps_routines.jl:50-62) for scenarios [first, first+count) of epigraph

@@ -105,7 +105,19 @@ SIGNATURES = [
     ("twosd_reform_partial", I, [P, I, I, P, I, C.c_uint64, C.c_uint64, D, P, P]),
     ("twosd_reform_finalize", I, [P, I, P, I, D, P, P, P, P, P, P]),
     ("twosd_reform_last_ms", I, [P, P]),
+    ("twosd_add_sampled_scenarios_vr", I, [P, I, I, C.c_uint64, C.c_uint64, P, P]),
+    ("twosd_moments_of_values_grouped", I, [P, C.c_int64, I, P, P, P]),
+    ("twosd_evaluate_moments_vr", I, [P, P, C.c_int64, C.c_int64, C.c_uint64, P, P]),
+    ("twosd_evaluate_paired_vr", I, [P, P, P, C.c_int64, C.c_int64, C.c_uint64, P, P, P, P]),
+    ("twosd_evaluate_ci_vr", I, [P, P, C.c_uint64, C.c_int64, C.c_int64, C.c_int64, D, D, D, D, P, P, P, P]),
 ]
+
+SAMPLING_IID, SAMPLING_ANTITHETIC, SAMPLING_LHS = 0, 1, 2
+
+
+class SamplingPlan(C.Structure):
+    """struct twosd_sampling (include/twosd_hip.h)."""
+    _fields_ = [("mode", I), ("group", I)]
 
 
 

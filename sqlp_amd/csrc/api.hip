@@ -1799,8 +1799,57 @@ extern "C" int twosd_set_distributions(twosd_ctx *c, int k, const int *kind, con
     return TWOSD_OK;
 }
 
+// a caller's sampling plan -> (mode, G); NULL means i.i.d.
+static int sampling_plan(const twosd_sampling *plan, const char *who, int *mode, int *G) {
+    *mode = TWOSD_SAMPLING_IID;
+    *G = 1;
+    if (!plan) return TWOSD_OK;
+    switch (plan->mode) {
+    case TWOSD_SAMPLING_IID:
+        if (plan->group != 1) return fail(TWOSD_E_ARG, "%s: an IID plan has group 1, not %d", who, plan->group);
+        break;
+    case TWOSD_SAMPLING_ANTITHETIC:
+        if (plan->group != 2) return fail(TWOSD_E_ARG, "%s: an ANTITHETIC plan has group 2, not %d", who, plan->group);
+        break;
+    case TWOSD_SAMPLING_LHS:
+        if (plan->group < 2 || plan->group > 256)
+            return fail(TWOSD_E_ARG, "%s: an LHS plan needs 2 <= group <= 256, not %d", who, plan->group);
+        break;
+    default:
+        return fail(TWOSD_E_ARG, "%s: unknown sampling mode %d", who, plan->mode);
+    }
+    *mode = plan->mode;
+    *G = plan->group;
+    return TWOSD_OK;
+}
+
+// `what` = value must be a whole number of groups
+static int whole_groups(const char *who, const char *what, unsigned long long value, int G) {
+    if (G > 1 && value % (unsigned long long)G)
+        return fail(TWOSD_E_ARG, "%s: %s = %llu is no multiple of the sampling group %d", who, what, value, G);
+    return TWOSD_OK;
+}
+
+static int add_sampled(twosd_ctx *c, int epi, int N, uint64_t seed, uint64_t first_index, const double *weights, int mode,
+                       int G);
+
 extern "C" int twosd_add_sampled_scenarios(twosd_ctx *c, int epi, int N, uint64_t seed, uint64_t first_index,
                                            const double *weights) {
+    return add_sampled(c, epi, N, seed, first_index, weights, TWOSD_SAMPLING_IID, 1);
+}
+
+extern "C" int twosd_add_sampled_scenarios_vr(twosd_ctx *c, int epi, int N, uint64_t seed, uint64_t first_index,
+                                              const double *weights, const twosd_sampling *plan) {
+    int mode, G, rc;
+    if ((rc = sampling_plan(plan, "add_sampled_scenarios", &mode, &G))) return rc;
+    if (N > 0 && ((rc = whole_groups("add_sampled_scenarios", "first_index", first_index, G)) ||
+                  (rc = whole_groups("add_sampled_scenarios", "N", (unsigned long long)N, G))))
+        return rc;
+    return add_sampled(c, epi, N, seed, first_index, weights, mode, G);
+}
+
+static int add_sampled(twosd_ctx *c, int epi, int N, uint64_t seed, uint64_t first_index, const double *weights, int mode,
+                       int G) {
     if (!c || !c->has_template) return fail(TWOSD_E_STATE, "add_sampled_scenarios: no template");
     if (!c->has_dist) return fail(TWOSD_E_STATE, "add_sampled_scenarios: no distributions (twosd_set_distributions)");
     if (epi < 0 || epi >= (int)c->epis.size()) return fail(TWOSD_E_ARG, "add_sampled_scenarios: epigraph %d does not exist", epi);
@@ -1822,7 +1871,7 @@ extern "C" int twosd_add_sampled_scenarios(twosd_ctx *c, int epi, int N, uint64_
     S.N = N; S.k = k; S.seed = seed; S.first_index = first_index;
     S.kind = c->d_dist_kind; S.off = c->d_dist_off; S.val = c->d_dist_val; S.prob = c->d_dist_prob;
     S.p0 = c->d_dist_p0; S.p1 = c->d_dist_p1; S.tmpl = c->d_dist_tmpl; S.out = E.d_dv + (size_t)E.count * k;
-    HIPCHK(launch_sample(S, c->stream));
+    HIPCHK(launch_sample_plan(S, mode, G, c->stream));
     HIPCHK(hipMemcpyAsync(E.d_w + E.count, w.data(), sizeof(double) * N, hipMemcpyHostToDevice, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
     E.w_host.insert(E.w_host.end(), w.begin(), w.end());
@@ -2625,6 +2674,41 @@ __global__ void __launch_bounds__(256) eval_moments_kernel(long long N, const do
         for (int r = 0; r < R; ++r) out[r] = twosd_moments{n, (hi - lo) - n, mean[r], n > 1 ? q[r] : 0.0, mn[r], mx[r]};
 }
 
+// Group means of a variance-reduced stream (twosd_sampling): the members of a
+// group of G consecutive entries are dependent, so the moments are taken over the groups' means.
+// One thread per group: status[b] = optimal iff all G entries are (else the first other status),
+// and only then mean[b] = K + (sum_{i < G} (v[i] - K)) / G with K = v[0], the sum in index order
+// from 0.0 -- a fixed order whatever the launch shape, the pivot keeping the sum at the size of the
+// spread.  The values of a group left out are never loaded (they may be NaN); its mean reads 0.
+// The means are stored relative to the chunk's pivot K0 = v[0] (0 when entry 0 is not optimal or
+// not finite), mean[b] = m_b - K0, and *pivot = K0: the moments kernel's block records then merge
+// at the size of the spread, not of the values (the merge's d d term loses 2^-53 |mean| / sd per
+// step), and the host adds K0 back to mean, min and max.  m_b - K0 is exact, and min / max the
+// means' own bits, whenever m_b / 2 <= K0 <= 2 m_b.
+// The paired form runs it on each array: a group counts when it is optimal in both, which the
+// moments kernel sees from the two group statuses, and it forms the difference of the means itself.
+__global__ void __launch_bounds__(256) group_means_kernel(long long ngroups, int G, const double *__restrict__ v,
+                                                          const int *__restrict__ st, double *__restrict__ mean,
+                                                          int *__restrict__ gst, double *__restrict__ pivot) {
+    const long long b = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= ngroups) return;
+    const double K0 = ((!st || st[0] == TWOSD_LP_OPTIMAL) && isfinite(v[0])) ? v[0] : 0.0;
+    if (b == 0) *pivot = K0;
+    const long long lo = b * G;
+    int bad = TWOSD_LP_OPTIMAL;
+    if (st)
+        for (int i = 0; i < G && bad == TWOSD_LP_OPTIMAL; ++i) bad = st[lo + i];
+    double m = 0.0;
+    if (bad == TWOSD_LP_OPTIMAL) {
+        const double K = v[lo];
+        double s = 0.0;
+        for (int i = 0; i < G; ++i) s = __dadd_rn(s, __dadd_rn(v[lo + i], -K));
+        m = __dadd_rn(__dadd_rn(K, __ddiv_rn(s, (double)G)), -K0);
+    }
+    mean[b] = m;
+    gst[b] = bad;
+}
+
 // Template with general bounds: the LP's outputs back into the caller's space.  yu[s][j] =
 // off[j] + sign[j] * y[s][src[j]] - y[s][src2[j]] (a term with index -1 is absent: fixed columns
 // have no LP column, only free ones a second), one thread per output entry, j fastest, so a wave
@@ -2764,7 +2848,36 @@ static int device_moments(twosd_ctx *c, long long N, const double *d_va, const i
     return TWOSD_OK;
 }
 
-extern "C" int twosd_moments_of_values(twosd_ctx *c, int64_t n, const double *obj, const int *status, twosd_moments *out) {
+// device_moments over the means of groups of G consecutive entries (N a multiple of G; G = 1: the
+// entries themselves): group_means_kernel into the context's group buffers, then the moments
+// kernel unchanged on the N / G means and group statuses
+static int device_moments_grouped(twosd_ctx *c, long long N, int G, const double *d_va, const int *d_sa, const double *d_vb,
+                                  const int *d_sb, twosd_moments *out) {
+    if (G <= 1 || N <= 0) return device_moments(c, N, d_va, d_sa, d_vb, d_sb, out);
+    const long long ng = N / G;
+    const int R = d_vb ? 2 : 1;
+    int rc;
+    if ((rc = c->d_gm_mean.fit((size_t)R * ng + 2)) || (rc = c->d_gm_st.fit((size_t)R * ng))) return rc;   // + the two pivots
+    double *d_piv = c->d_gm_mean + (size_t)R * ng;
+    const unsigned nb = (unsigned)((ng + 255) / 256);
+    hipLaunchKernelGGL(group_means_kernel, dim3(nb), dim3(256), 0, c->stream, ng, G, d_va, d_sa, c->d_gm_mean.p, c->d_gm_st.p, d_piv);
+    HIPCHK(hipGetLastError());
+    if (d_vb) {
+        hipLaunchKernelGGL(group_means_kernel, dim3(nb), dim3(256), 0, c->stream, ng, G, d_vb, d_sb, c->d_gm_mean + ng,
+                           c->d_gm_st + ng, d_piv + 1);
+        HIPCHK(hipGetLastError());
+    }
+    double piv[2] = {0.0, 0.0};
+    HIPCHK(hipMemcpyAsync(piv, d_piv, sizeof(double) * (d_vb ? 2 : 1), hipMemcpyDeviceToHost, c->stream));   // device_moments drains the stream
+    if ((rc = device_moments(c, ng, c->d_gm_mean, c->d_gm_st, d_vb ? c->d_gm_mean + ng : nullptr, d_vb ? c->d_gm_st + ng : nullptr, out)))
+        return rc;
+    const double back[3] = {piv[0], piv[1], piv[0] - piv[1]};   // the difference record is of (a - K0a) - (b - K0b)
+    for (int r = 0; r < (d_vb ? 3 : 1); ++r)
+        if (out[r].n > 0) { out[r].mean += back[r]; out[r].min += back[r]; out[r].max += back[r]; }
+    return TWOSD_OK;
+}
+
+static int moments_of_values(twosd_ctx *c, int64_t n, int G, const double *obj, const int *status, twosd_moments *out) {
     if (!c) return fail(TWOSD_E_STATE, "moments_of_values: no context");
     if (!out || n < 0 || (n > 0 && !obj)) return fail(TWOSD_E_ARG, "moments_of_values: bad arguments");
     HIPCHK(hipSetDevice(c->device));
@@ -2777,19 +2890,35 @@ extern "C" int twosd_moments_of_values(twosd_ctx *c, int64_t n, const double *ob
             HIPCHK(hipMemcpy(c->d_ev_st, status, sizeof(int) * n, hipMemcpyHostToDevice));
         }
     }
-    return device_moments(c, n, c->d_ev_obj, status ? c->d_ev_st : nullptr, nullptr, nullptr, out);
+    return device_moments_grouped(c, n, G, c->d_ev_obj, status ? c->d_ev_st : nullptr, nullptr, nullptr, out);
 }
 
-static int64_t eval_chunk_size() {
+extern "C" int twosd_moments_of_values(twosd_ctx *c, int64_t n, const double *obj, const int *status, twosd_moments *out) {
+    return moments_of_values(c, n, 1, obj, status, out);
+}
+
+extern "C" int twosd_moments_of_values_grouped(twosd_ctx *c, int64_t n, int G, const double *obj, const int *status,
+                                               twosd_moments *out) {
+    if (G < 1 || G > 256) return fail(TWOSD_E_ARG, "moments_of_values_grouped: need 1 <= G <= 256, not %d", G);
+    if (n > 0 && n % G) return fail(TWOSD_E_ARG, "moments_of_values_grouped: n = %lld is no multiple of G = %d", (long long)n, G);
+    return moments_of_values(c, n, G, obj, status, out);
+}
+
+// scenarios per evaluate chunk; for a plan with G > 1 rounded down to whole groups (at least one)
+static int64_t eval_chunk_size(int G) {
     int64_t chunk = 1 << 20;
     if (const char *e = getenv("TWOSD_EVAL_CHUNK")) chunk = std::min<int64_t>(std::max<int64_t>(atoll(e), 1), 1 << 24);   // test hook
+    if (G > 1) chunk = std::max<int64_t>(chunk / G * G, G);
     return chunk;
 }
+
+// the sampling plan of an evaluate call: (mode, group) of twosd_sampling, i.i.d. by default
+struct EvalPlan { int mode = TWOSD_SAMPLING_IID, G = 1; };
 
 // scenarios [at, at + n) of stream `seed` drawn into d_dvtmp and solved at x; copy_lp_outputs adds
 // the bounds' constant to d_obj and keeps the last-LP statistics current (nothing is copied out).
 // TWOSD_OK, or TWOSD_E_LP with d_obj / d_status still set, or a failure.
-static int eval_solve_chunk(twosd_ctx *c, const double *x, int64_t at, int n, uint64_t seed) {
+static int eval_solve_chunk(twosd_ctx *c, const double *x, int64_t at, int n, uint64_t seed, const EvalPlan &pl) {
     const int k = c->k;
     int rc;
     if ((rc = c->d_dvtmp.grow((size_t)n * std::max(k, 1), 0, c->stream))) return rc;
@@ -2797,7 +2926,7 @@ static int eval_solve_chunk(twosd_ctx *c, const double *x, int64_t at, int n, ui
     S.N = n; S.k = k; S.seed = seed; S.first_index = (unsigned long long)at;
     S.kind = c->d_dist_kind; S.off = c->d_dist_off; S.val = c->d_dist_val; S.prob = c->d_dist_prob;
     S.p0 = c->d_dist_p0; S.p1 = c->d_dist_p1; S.tmpl = c->d_dist_tmpl; S.out = c->d_dvtmp;
-    HIPCHK(launch_sample(S, c->stream));
+    HIPCHK(launch_sample_plan(S, pl.mode, pl.G, c->stream));
     if ((rc = run_lp(c, x, c->d_dvtmp, n, false, false))) return rc;
     return copy_lp_outputs(c, n, nullptr, nullptr, nullptr, nullptr, nullptr);
 }
@@ -2810,15 +2939,16 @@ static int eval_check_state(twosd_ctx *c, const char *who) {
 }
 
 // moments over [first, first + count) at xa (xb: the paired form, out[0 .. 3) = a, b, a - b);
-// *lp_bad: some LP was not optimal (counted in n_bad; not a failure here)
+// *lp_bad: some LP was not optimal (counted in n_bad; not a failure here).  Under a plan with
+// G > 1 (first and count whole groups) the moments are of the group means, n / n_bad in groups.
 static int eval_moments_range(twosd_ctx *c, const double *xa, const double *xb, int64_t first, int64_t count, uint64_t seed,
-                              twosd_moments *out, bool *lp_bad) {
+                              twosd_moments *out, bool *lp_bad, const EvalPlan &pl = EvalPlan()) {
     const int R = xb ? 3 : 1;
-    const int64_t chunk = eval_chunk_size();
+    const int64_t chunk = eval_chunk_size(pl.G);
     for (int r = 0; r < R; ++r) out[r] = kMomentsEmpty;
     for (int64_t at = 0; at < count; at += chunk) {
         const int n = (int)std::min(chunk, count - at);
-        int rc = eval_solve_chunk(c, xa, first + at, n, seed);
+        int rc = eval_solve_chunk(c, xa, first + at, n, seed, pl);
         if (rc == TWOSD_E_LP) *lp_bad = true;
         else if (rc) return rc;
         twosd_moments m[3];
@@ -2829,50 +2959,88 @@ static int eval_moments_range(twosd_ctx *c, const double *xa, const double *xb, 
             HIPCHK(hipMemcpyAsync(c->d_ev_obj, c->d_obj, sizeof(double) * n, hipMemcpyDeviceToDevice, c->stream));
             HIPCHK(hipMemcpyAsync(c->d_ev_st, c->d_status, sizeof(int) * n, hipMemcpyDeviceToDevice, c->stream));
             HIPCHK(hipStreamSynchronize(c->stream));   // the next solve may reallocate d_obj / d_status
-            rc = eval_solve_chunk(c, xb, first + at, n, seed);
+            rc = eval_solve_chunk(c, xb, first + at, n, seed, pl);
             if (rc == TWOSD_E_LP) *lp_bad = true;
             else if (rc) return rc;
-            if ((rc = device_moments(c, n, c->d_ev_obj, c->d_ev_st, c->d_obj, c->d_status, m))) return rc;
-        } else if ((rc = device_moments(c, n, c->d_obj, c->d_status, nullptr, nullptr, m)))
+            if ((rc = device_moments_grouped(c, n, pl.G, c->d_ev_obj, c->d_ev_st, c->d_obj, c->d_status, m))) return rc;
+        } else if ((rc = device_moments_grouped(c, n, pl.G, c->d_obj, c->d_status, nullptr, nullptr, m)))
             return rc;
         for (int r = 0; r < R; ++r) twosd_moments_merge(&out[r], &m[r], &out[r]);
     }
     return TWOSD_OK;
 }
 
-static int eval_lp_result(bool lp_bad, const twosd_moments &m, const char *who) {
+static int eval_lp_result(bool lp_bad, const twosd_moments &m, const char *who, int G = 1) {
     if (!lp_bad) return TWOSD_OK;
+    if (G > 1)
+        return fail(TWOSD_E_LP, "%s: %lld of %lld scenario groups hold an LP that is not optimal (left out of the moments, see n_bad)",
+                    who, (long long)m.n_bad, (long long)(m.n + m.n_bad));
     return fail(TWOSD_E_LP, "%s: %lld of %lld scenario LPs not optimal (left out of the moments, see n_bad)", who,
                 (long long)m.n_bad, (long long)(m.n + m.n_bad));
 }
 
-extern "C" int twosd_evaluate_moments(twosd_ctx *c, const double *x, int64_t first, int64_t count, uint64_t seed,
-                                      twosd_moments *out) {
+// the plan of an evaluate call, with `first` and `count` checked for whole groups
+static int eval_plan(const twosd_sampling *plan, const char *who, int64_t first, int64_t count, const char *count_name,
+                     EvalPlan *pl) {
+    int rc;
+    if ((rc = sampling_plan(plan, who, &pl->mode, &pl->G))) return rc;
+    if (first >= 0 && (rc = whole_groups(who, "first", (unsigned long long)first, pl->G))) return rc;
+    if (count >= 0 && (rc = whole_groups(who, count_name, (unsigned long long)count, pl->G))) return rc;
+    return TWOSD_OK;
+}
+
+static int evaluate_moments(twosd_ctx *c, const double *x, int64_t first, int64_t count, uint64_t seed, twosd_moments *out,
+                            const EvalPlan &pl) {
     int rc = eval_check_state(c, "evaluate_moments");
     if (rc) return rc;
     if (!out || first < 0 || count < 0 || (c->n1 > 0 && !x)) return fail(TWOSD_E_ARG, "evaluate_moments: bad arguments");
     HIPCHK(hipSetDevice(c->device));
     bool lp_bad = false;
-    if ((rc = eval_moments_range(c, x, nullptr, first, count, seed, out, &lp_bad))) return rc;
-    return eval_lp_result(lp_bad, *out, "evaluate_moments");
+    if ((rc = eval_moments_range(c, x, nullptr, first, count, seed, out, &lp_bad, pl))) return rc;
+    return eval_lp_result(lp_bad, *out, "evaluate_moments", pl.G);
 }
 
-extern "C" int twosd_evaluate_paired(twosd_ctx *c, const double *xa, const double *xb, int64_t first, int64_t count,
-                                     uint64_t seed, twosd_moments *a, twosd_moments *b, twosd_moments *diff) {
+extern "C" int twosd_evaluate_moments(twosd_ctx *c, const double *x, int64_t first, int64_t count, uint64_t seed,
+                                      twosd_moments *out) {
+    return evaluate_moments(c, x, first, count, seed, out, EvalPlan());
+}
+
+extern "C" int twosd_evaluate_moments_vr(twosd_ctx *c, const double *x, int64_t first, int64_t count, uint64_t seed,
+                                         twosd_moments *out, const twosd_sampling *plan) {
+    EvalPlan pl;
+    if (int rc = eval_plan(plan, "evaluate_moments", first, count, "count", &pl)) return rc;
+    return evaluate_moments(c, x, first, count, seed, out, pl);
+}
+
+static int evaluate_paired(twosd_ctx *c, const double *xa, const double *xb, int64_t first, int64_t count, uint64_t seed,
+                           twosd_moments *a, twosd_moments *b, twosd_moments *diff, const EvalPlan &pl) {
     int rc = eval_check_state(c, "evaluate_paired");
     if (rc) return rc;
     if (!a || !b || !diff || first < 0 || count < 0 || !xa || !xb) return fail(TWOSD_E_ARG, "evaluate_paired: bad arguments");
     HIPCHK(hipSetDevice(c->device));
     bool lp_bad = false;
     twosd_moments m[3];
-    if ((rc = eval_moments_range(c, xa, xb, first, count, seed, m, &lp_bad))) return rc;
+    if ((rc = eval_moments_range(c, xa, xb, first, count, seed, m, &lp_bad, pl))) return rc;
     *a = m[0]; *b = m[1]; *diff = m[2];
-    return eval_lp_result(lp_bad, m[0], "evaluate_paired");
+    return eval_lp_result(lp_bad, m[0], "evaluate_paired", pl.G);
 }
 
-extern "C" int twosd_evaluate_ci(twosd_ctx *c, const double *x, uint64_t seed, int64_t first, int64_t batch, int64_t n_max,
-                                 double z, double rel_tol, double abs_tol, double offset, twosd_moments *out,
-                                 double *half_width, int *converged) {
+extern "C" int twosd_evaluate_paired(twosd_ctx *c, const double *xa, const double *xb, int64_t first, int64_t count,
+                                     uint64_t seed, twosd_moments *a, twosd_moments *b, twosd_moments *diff) {
+    return evaluate_paired(c, xa, xb, first, count, seed, a, b, diff, EvalPlan());
+}
+
+extern "C" int twosd_evaluate_paired_vr(twosd_ctx *c, const double *xa, const double *xb, int64_t first, int64_t count,
+                                        uint64_t seed, twosd_moments *a, twosd_moments *b, twosd_moments *diff,
+                                        const twosd_sampling *plan) {
+    EvalPlan pl;
+    if (int rc = eval_plan(plan, "evaluate_paired", first, count, "count", &pl)) return rc;
+    return evaluate_paired(c, xa, xb, first, count, seed, a, b, diff, pl);
+}
+
+static int evaluate_ci(twosd_ctx *c, const double *x, uint64_t seed, int64_t first, int64_t batch, int64_t n_max, double z,
+                       double rel_tol, double abs_tol, double offset, twosd_moments *out, double *half_width, int *converged,
+                       const EvalPlan &pl) {
     if (!out || !half_width || !converged || first < 0) return fail(TWOSD_E_ARG, "evaluate_ci: bad arguments");
     if (batch < 2 || n_max < batch) return fail(TWOSD_E_ARG, "evaluate_ci: need 2 <= batch <= n_max (batch %lld, n_max %lld)", (long long)batch, (long long)n_max);
     if (!(z > 0.0) || !(rel_tol >= 0.0) || !(abs_tol >= 0.0) || !std::isfinite(offset))
@@ -2888,7 +3056,7 @@ extern "C" int twosd_evaluate_ci(twosd_ctx *c, const double *x, uint64_t seed, i
     for (int64_t done = 0; done < n_max && !conv; ) {
         const int64_t cnt = std::min(batch, n_max - done);
         twosd_moments m;
-        if ((rc = eval_moments_range(c, x, nullptr, first + done, cnt, seed, &m, &lp_bad))) return rc;
+        if ((rc = eval_moments_range(c, x, nullptr, first + done, cnt, seed, &m, &lp_bad, pl))) return rc;
         twosd_moments_merge(&acc, &m, &acc);
         done += cnt;
         if (acc.n >= 2) {
@@ -2899,7 +3067,28 @@ extern "C" int twosd_evaluate_ci(twosd_ctx *c, const double *x, uint64_t seed, i
     *out = acc;
     *half_width = hw;
     *converged = conv;
-    return eval_lp_result(lp_bad, acc, "evaluate_ci");
+    return eval_lp_result(lp_bad, acc, "evaluate_ci", pl.G);
+}
+
+extern "C" int twosd_evaluate_ci(twosd_ctx *c, const double *x, uint64_t seed, int64_t first, int64_t batch, int64_t n_max,
+                                 double z, double rel_tol, double abs_tol, double offset, twosd_moments *out,
+                                 double *half_width, int *converged) {
+    return evaluate_ci(c, x, seed, first, batch, n_max, z, rel_tol, abs_tol, offset, out, half_width, converged, EvalPlan());
+}
+
+// the rule of twosd_evaluate_ci on the group moments: its scenario counts (done, n_max, batch) stay
+// in scenarios, acc.n / acc.n_bad are groups
+extern "C" int twosd_evaluate_ci_vr(twosd_ctx *c, const double *x, uint64_t seed, int64_t first, int64_t batch, int64_t n_max,
+                                    double z, double rel_tol, double abs_tol, double offset, twosd_moments *out,
+                                    double *half_width, int *converged, const twosd_sampling *plan) {
+    EvalPlan pl;
+    if (int rc = eval_plan(plan, "evaluate_ci", first, batch, "batch", &pl)) return rc;
+    if (pl.G > 1) {
+        if (batch / pl.G < 2)
+            return fail(TWOSD_E_ARG, "evaluate_ci: batch = %lld holds fewer than 2 groups of %d", (long long)batch, pl.G);
+        n_max = n_max / pl.G * pl.G;
+    }
+    return evaluate_ci(c, x, seed, first, batch, n_max, z, rel_tol, abs_tol, offset, out, half_width, converged, pl);
 }
 
 extern "C" int twosd_training_cap(twosd_ctx *c, int64_t pivots_sum, int64_t scenarios, int *cap) {

@@ -53,4 +53,112 @@ hipError_t launch_sample(const SampleParams &S, hipStream_t st) {
     return hipGetLastError();
 }
 
+// ---- variance-reduced streams (twosd_sampling) -------------------------------
+// Both keep sample_kernel's words: u1, u2 of (index, element) come from the same Philox call, so
+// the streams differ from the i.i.d. one only in where each element's distribution is inverted.
+
+// DISCRETE (kind 0) or UNIFORM (kind 2) element e at the uniform u in [0, 1]: sample_kernel's
+// arithmetic.  u = 1.0 is legal: the DISCRETE walk stops at the last support point, UNIFORM gives
+// `right` (up to its two roundings).
+__device__ __forceinline__ double invert_at(const SampleParams &S, int e, int kind, double u) {
+    if (kind == 0) {
+        const int o = S.off[e], n = S.off[e + 1] - o;
+        int i = 0;
+        double cp = S.prob[o];
+        while (cp <= u && i < n - 1) cp = __dadd_rn(cp, S.prob[o + (++i)]);
+        return S.val[o + i];
+    }
+    return __dadd_rn(S.p0[e], __dmul_rn(__dadd_rn(S.p1[e], -S.p0[e]), u));
+}
+
+// ANTITHETIC: one thread per (scenario, element) like sample_kernel.  Pair p = g >> 1 draws the
+// words of index 2p; the even member is the i.i.d. draw of 2p, the odd member inverts DISCRETE /
+// UNIFORM at 1 - u1 (exact in fp64: u1 is a multiple of 2^-53 below 1) and negates NORMAL's z.
+__global__ void __launch_bounds__(256) sample_antithetic_kernel(SampleParams S) {
+    const long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    const long long total = (long long)S.N * S.k;
+    if (idx >= total) return;
+    const int s = (int)(idx / S.k), e = (int)(idx - (long long)s * S.k);
+    const unsigned long long g = S.first_index + (unsigned long long)s, g0 = g & ~1ull;
+    const bool odd = (g & 1ull) != 0;
+    const Philox4 r = philox4x32_10((uint32_t)g0, (uint32_t)(g0 >> 32), (uint32_t)e, 0u, (uint32_t)S.seed,
+                                    (uint32_t)(S.seed >> 32));
+    const double u1 = u01(r.v[0], r.v[1]);
+    const int kind = S.kind[e];
+    double v;
+    if (kind == 1) {
+        const double u2 = u01(r.v[2], r.v[3]);
+        const double z = sqrt(-2.0 * log(1.0 - u1)) * cos(6.283185307179586 * u2);
+        v = __dadd_rn(S.p0[e], __dmul_rn(S.p1[e], odd ? -z : z));
+    } else {
+        v = invert_at(S, e, kind, odd ? 1.0 - u1 : u1);
+    }
+    S.out[idx] = __dadd_rn(v, -S.tmpl[e]);
+}
+
+// LHS: one thread per (block of G scenarios, element), e fastest across the lanes, so at step j a
+// wave stores runs of consecutive doubles of the rows b G + j.  The thread first builds the
+// (block, element) permutation of 0..G-1 by the inside-out Fisher-Yates shuffle from Philox
+// counters (b_lo, b_hi, e, 2 + (i >> 2)) -- the fourth word keeps them apart from the scenario
+// words (0) and the bootstrap's (1) -- then walks the block: member j inverts at
+// u = min((perm[j] + u1(g, e)) / G, 1 - 2^-53), NORMAL through the inverse normal CDF (Box-Muller
+// cannot be stratified in one uniform).  G + ceil(G / 4) Philox calls for G outputs.
+// The permutation is bytes in LDS, [ceil(G / 4)][threads][4]: thread t owns dword column t of
+// every row, so whatever entries the lanes of a wave touch in one access (the shuffle's perm[t]
+// is a different row in every lane) lie in 32 distinct banks per half wave -- no conflicts, and no
+// two threads ever share a dword.  128 threads x 256 bytes = 32 KB at G = 256.
+constexpr int kLhsThreads = 128;
+__global__ void __launch_bounds__(kLhsThreads) sample_lhs_kernel(SampleParams S, int G, long long nblk) {
+    extern __shared__ unsigned char lhs_perm[];
+    const long long idx = (long long)blockIdx.x * kLhsThreads + threadIdx.x;
+    if (idx >= nblk * S.k) return;   // no barrier below: every thread works on its own column
+    const long long bl = idx / S.k;
+    const int e = (int)(idx - bl * S.k);
+    const unsigned long long gb = S.first_index / (unsigned long long)G + (unsigned long long)bl;
+    const uint32_t k0 = (uint32_t)S.seed, k1 = (uint32_t)(S.seed >> 32);
+    unsigned char *col = lhs_perm + 4 * threadIdx.x;
+    const auto at = [&](int i) -> unsigned char & { return col[(size_t)(i >> 2) * (4 * kLhsThreads) + (i & 3)]; };
+    at(0) = 0;
+    Philox4 w{};
+    for (int i = 1; i < G; ++i) {
+        if (i == 1 || (i & 3) == 0)
+            w = philox4x32_10((uint32_t)gb, (uint32_t)(gb >> 32), (uint32_t)e, 2u + (uint32_t)(i >> 2), k0, k1);
+        const int t = (int)__umulhi(w.v[i & 3], (uint32_t)(i + 1));   // uniform on 0..i
+        at(i) = at(t);
+        at(t) = (unsigned char)i;
+    }
+    const int kind = S.kind[e];
+    const double tm = S.tmpl[e], fG = (double)G;
+    for (int j = 0; j < G; ++j) {
+        const unsigned long long g = gb * (unsigned long long)G + (unsigned long long)j;
+        const Philox4 r = philox4x32_10((uint32_t)g, (uint32_t)(g >> 32), (uint32_t)e, 0u, k0, k1);
+        const double u1 = u01(r.v[0], r.v[1]);
+        double u = __ddiv_rn(__dadd_rn((double)at(j), u1), fG);
+        u = u < 0x1.fffffffffffffp-1 ? u : 0x1.fffffffffffffp-1;
+        double v;
+        if (kind == 1) {
+            const double z = normcdfinv(u > 0x1p-54 ? u : 0x1p-54);
+            v = __dadd_rn(S.p0[e], __dmul_rn(S.p1[e], z));
+        } else {
+            v = invert_at(S, e, kind, u);
+        }
+        S.out[(bl * G + j) * S.k + e] = __dadd_rn(v, -tm);
+    }
+}
+
+hipError_t launch_sample_plan(const SampleParams &S, int mode, int G, hipStream_t st) {
+    if (mode == TWOSD_SAMPLING_IID) return launch_sample(S, st);
+    const long long total = (long long)S.N * S.k;
+    if (total <= 0) return hipSuccess;
+    if (mode == TWOSD_SAMPLING_ANTITHETIC) {
+        hipLaunchKernelGGL(sample_antithetic_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, S);
+    } else {
+        const long long nblk = S.N / G, work = nblk * S.k;
+        const size_t lds = (size_t)((G + 3) / 4) * 4 * kLhsThreads;
+        hipLaunchKernelGGL(sample_lhs_kernel, dim3((unsigned)((work + kLhsThreads - 1) / kLhsThreads)), dim3(kLhsThreads), lds, st,
+                           S, G, nblk);
+    }
+    return hipGetLastError();
+}
+
 }  // namespace twosd

@@ -173,6 +173,10 @@ struct TemplateState {
     twosd::DevBuf<char> d_mompart;
     twosd::DevBuf<double> d_ev_obj;
     twosd::DevBuf<int> d_ev_st;
+    // group means and group statuses of a variance-reduced chunk (group_means_kernel; the paired
+    // form's second array behind the first)
+    twosd::DevBuf<double> d_gm_mean;
+    twosd::DevBuf<int> d_gm_st;
     // scenario distributions (on-device sampler)
     bool has_dist = false;
     twosd::DevBuf<int> d_dist_kind, d_dist_off;

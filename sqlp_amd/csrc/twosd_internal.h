@@ -191,6 +191,9 @@ struct SampleParams {
     double *out;                          // N x k deltas
 };
 hipError_t launch_sample(const SampleParams &S, hipStream_t st);
+// the stream of a sampling plan (twosd_sampling: mode, group G); S.first_index and S.N are
+// multiples of G (the caller checks).  IID launches sample_kernel itself.
+hipError_t launch_sample_plan(const SampleParams &S, int mode, int G, hipStream_t st);
 
 // ---- host-side setup (host_basis.cpp) --------------------------------------------
 struct HostLP {

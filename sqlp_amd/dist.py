@@ -34,6 +34,22 @@ def shard_range(N: int, rank: int, world_size: int):
     return (N * rank) // world_size, (N * (rank + 1)) // world_size
 
 
+def group_shard_ranges(lo: int, hi: int, world_size: int, group: int = 1):
+    """[lo, hi) -- a whole number of groups of `group` scenarios starting on a group boundary --
+    split over world_size ranks in whole groups: a list of world_size contiguous (lo_r, hi_r) in
+    rank order, disjoint, covering the range, every bound a multiple of `group` away from lo (the
+    groups shard as shard_range shards scenarios; a rank beyond the group count gets an empty
+    range).  Pure: no collective, no GPU."""
+    group, world_size = int(group), int(world_size)
+    if group < 1 or world_size < 1:
+        raise ValueError("group_shard_ranges: group and world_size must be >= 1")
+    if hi < lo or lo % group or (hi - lo) % group:
+        raise ValueError(f"group_shard_ranges: [{lo}, {hi}) is no whole number of groups of {group}")
+    ng = (hi - lo) // group
+    return [(lo + group * shard_range(ng, r, world_size)[0], lo + group * shard_range(ng, r, world_size)[1])
+            for r in range(world_size)]
+
+
 def allreduce_cut_partials(hist: torch.Tensor, sums: torch.Tensor):
     """Sum the per-rank cut partials in place: hist (int64 fixed point, exact) and sums
     (fp64).  No-op on a single rank."""
@@ -102,19 +118,28 @@ def merge_moments_in_rank_order(m):
     acc = None
     for p in parts:
         v = p.cpu().tolist()
-        q = Moments(int(v[0]), int(v[1]), v[2], v[3], v[4], v[5])
+        q = Moments(int(v[0]), int(v[1]), v[2], v[3], v[4], v[5], m.group)
         acc = q if acc is None else acc.merge(q)
     return acc
 
 
 def evaluate_ci_sharded(ctx, first_stage_cost, x, seed, batch=4096, n_max=1 << 20, confidence=0.95, rel_tol=1e-3,
-                        abs_tol=0.0, first=0, z=None):
+                        abs_tol=0.0, first=0, z=None, sampling=None):
     """twosd.evaluate_ci with every batch split over the ranks (shard_range): each rank evaluates
     its slice of the batch, the slices merge in rank order and the batches in stream order, so
     every rank holds the same moments and takes the same stop decision (the rule of
-    twosd_evaluate_ci).  A non-optimal LP counts in n_bad."""
+    twosd_evaluate_ci).  A non-optimal LP counts in n_bad.  sampling: a twosd.Sampling plan; every
+    batch is then split in whole groups (group_shard_ranges), first and batch are whole groups,
+    batch holds at least two, n_max is clipped down to whole groups and the moments are over
+    group means (the rule of twosd_evaluate_ci_vr)."""
     from . import twosd
     rank, G = world()
+    grp = 1 if sampling is None else int(sampling.group)
+    if grp > 1:
+        if first % grp or batch % grp or batch // grp < 2:
+            raise ValueError(f"evaluate_ci_sharded: first and batch must be multiples of the sampling group {grp}, "
+                             "batch at least two groups")
+        n_max = n_max // grp * grp
     if batch < 2 or n_max < batch:
         raise ValueError("evaluate_ci_sharded: need 2 <= batch <= n_max")
     if rel_tol < 0 or abs_tol < 0:
@@ -124,18 +149,21 @@ def evaluate_ci_sharded(ctx, first_stage_cost, x, seed, batch=4096, n_max=1 << 2
         raise ValueError("evaluate_ci_sharded: z <= 0")
     offset = float(np.dot(first_stage_cost, x))
     zero = np.zeros(len(x))
-    acc = twosd.Moments()
+    acc = twosd.Moments(group=grp)
     done, hw, conv = 0, float("inf"), False
     while done < n_max and not conv:
         cnt = min(batch, n_max - done)
-        lo, hi = shard_range(cnt, rank, G)
-        mine = twosd.evaluate_moments(ctx, zero, x, seed, first + done + lo, hi - lo, raise_on_status=False)
+        if sampling is None:
+            lo, hi = shard_range(cnt, rank, G)
+        else:
+            lo, hi = group_shard_ranges(0, cnt, G, grp)[rank]
+        mine = twosd.evaluate_moments(ctx, zero, x, seed, first + done + lo, hi - lo, raise_on_status=False, sampling=sampling)
         acc = acc.merge(merge_moments_in_rank_order(mine))
         done += cnt
         if acc.n >= 2:
             hw = z * acc.std_error
             conv = hw <= max(abs_tol, rel_tol * abs(offset + acc.mean))
-    return twosd.EvaluateCI(offset + acc.mean, hw, acc.n, acc.n_bad, bool(conv), acc)
+    return twosd.EvaluateCI(offset + acc.mean, hw, acc.n, acc.n_bad, bool(conv), acc, grp)
 
 
 class CutExchange:

@@ -573,12 +573,52 @@ def add_scenarios(epi: sdEpigraph, values, weights=None):
     epi.scenario_weight.extend([1.0] * N if w is None else list(w))
 
 
-def add_sampled_scenarios(epi: sdEpigraph, N, seed, first_index=0, weights=None):
+@dataclass(frozen=True)
+class Sampling:
+    """struct twosd_sampling: how a device-drawn stream is built.  Groups of `group` consecutive
+    global scenario indices are dependent (antithetic pairs, Latin hypercube blocks of S), so the
+    estimators that take a plan report moments over group means.  sampling=None means i.i.d."""
+    mode: int = _lib.SAMPLING_IID
+    group: int = 1
+
+    @classmethod
+    def iid(cls) -> "Sampling":
+        return cls(_lib.SAMPLING_IID, 1)
+
+    @classmethod
+    def antithetic(cls) -> "Sampling":
+        return cls(_lib.SAMPLING_ANTITHETIC, 2)
+
+    @classmethod
+    def lhs(cls, S) -> "Sampling":
+        """Latin hypercube blocks of S scenarios, 2 <= S <= 256 (the library checks)."""
+        return cls(_lib.SAMPLING_LHS, int(S))
+
+    def _c(self):
+        return _lib.SamplingPlan(int(self.mode), int(self.group))
+
+
+def _plan(sampling):
+    """(pointer or None, group) of a sampling= argument; the struct must outlive the call, so the
+    caller keeps the returned object."""
+    if sampling is None:
+        return None, 1
+    return sampling._c(), int(sampling.group)
+
+
+def add_sampled_scenarios(epi: sdEpigraph, N, seed, first_index=0, weights=None, sampling=None):
     """N scenarios drawn on the device (Philox4x32-10 stream (seed, first_index + s, e))
-    appended to epi -- add_scenario!(epi, rand(rng, sto)) N times without a host copy."""
+    appended to epi -- add_scenario!(epi, rand(rng, sto)) N times without a host copy.
+    sampling: a Sampling plan (twosd_add_sampled_scenarios_vr); first_index and N are then whole
+    groups."""
     w = None if weights is None else _f64(weights)
-    check(epi.ctx.lib.twosd_add_sampled_scenarios(epi.ctx.h, epi.index, int(N), C.c_uint64(seed),
-                                                   C.c_uint64(first_index), ptr(w)))
+    if sampling is None:
+        check(epi.ctx.lib.twosd_add_sampled_scenarios(epi.ctx.h, epi.index, int(N), C.c_uint64(seed),
+                                                       C.c_uint64(first_index), ptr(w)))
+    else:
+        plan, _ = _plan(sampling)
+        check(epi.ctx.lib.twosd_add_sampled_scenarios_vr(epi.ctx.h, epi.index, int(N), C.c_uint64(seed),
+                                                          C.c_uint64(first_index), ptr(w), C.byref(plan)))
     epi.scenario_weight.extend([1.0] * N if w is None else list(w))
 
 
@@ -643,6 +683,12 @@ class Moments:
     m2: float = 0.0
     min: float = float("inf")
     max: float = float("-inf")
+    group: int = 1      # > 1: the observations are means of groups of `group` scenarios (Sampling)
+
+    @property
+    def n_scenarios(self) -> int:
+        """Scenarios behind the n counted observations (n groups of `group`)."""
+        return self.n * self.group
 
     @property
     def variance(self) -> float:
@@ -660,16 +706,18 @@ class Moments:
 
     def merge(self, other: "Moments") -> "Moments":
         """twosd_moments_merge(self, other): the moments of both samples together."""
+        if self.group != other.group:
+            raise ValueError(f"merge: moments over groups of {self.group} and of {other.group}")
         a, b, out = self._c(), other._c(), _lib.Moments()
         check(_lib.load().twosd_moments_merge(C.byref(a), C.byref(b), C.byref(out)))
-        return Moments._of(out)
+        return Moments._of(out, self.group)
 
     def _c(self):
         return _lib.Moments(int(self.n), int(self.n_bad), float(self.mean), float(self.m2), float(self.min), float(self.max))
 
     @classmethod
-    def _of(cls, m) -> "Moments":
-        return cls(int(m.n), int(m.n_bad), float(m.mean), float(m.m2), float(m.min), float(m.max))
+    def _of(cls, m, group=1) -> "Moments":
+        return cls(int(m.n), int(m.n_bad), float(m.mean), float(m.m2), float(m.min), float(m.max), int(group))
 
 
 def _lp_status_ok(rc, raise_on_status):
@@ -678,57 +726,81 @@ def _lp_status_ok(rc, raise_on_status):
         check(rc)
 
 
-def moments_of_values(ctx: SDContext, obj, status=None) -> Moments:
+def moments_of_values(ctx: SDContext, obj, status=None, group=1) -> Moments:
     """Moments of the caller's own objectives on the device (twosd_moments_of_values): entries
-    whose status is not optimal are left out (n_bad) and never read into a sum."""
+    whose status is not optimal are left out (n_bad) and never read into a sum.  group = G > 1
+    (twosd_moments_of_values_grouped): the moments of the means of groups of G consecutive
+    entries; a group counts when all of its entries are optimal, n and n_bad count groups."""
     obj = _f64(np.ravel(obj))
     st = None if status is None else np.ascontiguousarray(np.ravel(status), dtype=np.int32)
     if st is not None and st.shape != obj.shape:
         raise ValueError("status and obj differ in length")
     out = _lib.Moments()
-    check(ctx.lib.twosd_moments_of_values(ctx.h, C.c_int64(obj.size), ptr(obj), ptr(st), C.byref(out)))
-    return Moments._of(out)
+    if int(group) == 1:
+        check(ctx.lib.twosd_moments_of_values(ctx.h, C.c_int64(obj.size), ptr(obj), ptr(st), C.byref(out)))
+    else:
+        check(ctx.lib.twosd_moments_of_values_grouped(ctx.h, C.c_int64(obj.size), int(group), ptr(obj), ptr(st), C.byref(out)))
+    return Moments._of(out, group)
 
 
-def evaluate_moments(ctx: SDContext, first_stage_cost, x, seed, first, count, raise_on_status=True) -> Moments:
+def evaluate_moments(ctx: SDContext, first_stage_cost, x, seed, first, count, raise_on_status=True, sampling=None) -> Moments:
     """Moments of c'x + obj_w over scenarios [first, first+count) of the device-drawn stream `seed`
     (twosd_evaluate_moments: no objective leaves the device).  mean, min and max include c'x.
     raise_on_status=False returns the moments of the optimal scenarios when some LP is not
-    optimal (their number is n_bad) instead of raising."""
+    optimal (their number is n_bad) instead of raising.  sampling: a Sampling plan
+    (twosd_evaluate_moments_vr): the moments are then of the group means, n and n_bad in groups."""
     out = _lib.Moments()
-    rc = ctx.lib.twosd_evaluate_moments(ctx.h, ptr(_f64(x)), C.c_int64(first), C.c_int64(count), C.c_uint64(seed),
-                                        C.byref(out))
+    plan, G = _plan(sampling)
+    if plan is None:
+        rc = ctx.lib.twosd_evaluate_moments(ctx.h, ptr(_f64(x)), C.c_int64(first), C.c_int64(count), C.c_uint64(seed),
+                                            C.byref(out))
+    else:
+        rc = ctx.lib.twosd_evaluate_moments_vr(ctx.h, ptr(_f64(x)), C.c_int64(first), C.c_int64(count), C.c_uint64(seed),
+                                               C.byref(out), C.byref(plan))
     _lp_status_ok(rc, raise_on_status)
-    return _shift(Moments._of(out), float(np.dot(first_stage_cost, x)))
+    return _shift(Moments._of(out, G), float(np.dot(first_stage_cost, x)))
 
 
 def _shift(m: Moments, c: float) -> Moments:
     if m.n == 0 or c == 0.0:
         return m
-    return Moments(m.n, m.n_bad, m.mean + c, m.m2, m.min + c, m.max + c)
+    return Moments(m.n, m.n_bad, m.mean + c, m.m2, m.min + c, m.max + c, m.group)
 
 
-def evaluate_paired(ctx: SDContext, first_stage_cost, xa, xb, seed, first, count, raise_on_status=True):
+def evaluate_paired(ctx: SDContext, first_stage_cost, xa, xb, seed, first, count, raise_on_status=True, sampling=None):
     """Two first-stage points on common random numbers (twosd_evaluate_paired): the same
     scenarios solved at xa and at xb -> (a, b, diff), diff the moments of the per-scenario
-    difference of c'x + obj.  diff.half_width() is the error bar of "xa is better than xb"."""
+    difference of c'x + obj.  diff.half_width() is the error bar of "xa is better than xb".
+    sampling: a Sampling plan (twosd_evaluate_paired_vr): all three over group means."""
     a, b, d = _lib.Moments(), _lib.Moments(), _lib.Moments()
-    rc = ctx.lib.twosd_evaluate_paired(ctx.h, ptr(_f64(xa)), ptr(_f64(xb)), C.c_int64(first), C.c_int64(count),
-                                       C.c_uint64(seed), C.byref(a), C.byref(b), C.byref(d))
+    plan, G = _plan(sampling)
+    if plan is None:
+        rc = ctx.lib.twosd_evaluate_paired(ctx.h, ptr(_f64(xa)), ptr(_f64(xb)), C.c_int64(first), C.c_int64(count),
+                                           C.c_uint64(seed), C.byref(a), C.byref(b), C.byref(d))
+    else:
+        rc = ctx.lib.twosd_evaluate_paired_vr(ctx.h, ptr(_f64(xa)), ptr(_f64(xb)), C.c_int64(first), C.c_int64(count),
+                                              C.c_uint64(seed), C.byref(a), C.byref(b), C.byref(d), C.byref(plan))
     _lp_status_ok(rc, raise_on_status)
     ca, cb = float(np.dot(first_stage_cost, xa)), float(np.dot(first_stage_cost, xb))
-    return _shift(Moments._of(a), ca), _shift(Moments._of(b), cb), _shift(Moments._of(d), ca - cb)
+    return _shift(Moments._of(a, G), ca), _shift(Moments._of(b, G), cb), _shift(Moments._of(d, G), ca - cb)
 
 
 @dataclass(frozen=True)
 class EvaluateCI:
-    """Result of evaluate_ci: mean (c'x included) +- half_width over n scenarios."""
+    """Result of evaluate_ci: mean (c'x included) +- half_width over n observations: scenarios,
+    or under a Sampling plan groups of `group` scenarios (n_bad likewise)."""
     mean: float
     half_width: float
     n: int
     n_bad: int
     converged: bool
     moments: Moments    # stage-2 part alone (without c'x)
+    group: int = 1
+
+    @property
+    def n_scenarios(self) -> int:
+        """Scenarios behind the n counted observations."""
+        return self.n * self.group
 
 
 def normal_quantile(confidence: float) -> float:
@@ -740,20 +812,29 @@ def normal_quantile(confidence: float) -> float:
 
 
 def evaluate_ci(ctx: SDContext, first_stage_cost, x, seed, batch=4096, n_max=1 << 20, confidence=0.95, rel_tol=1e-3,
-                abs_tol=0.0, first=0, raise_on_status=True, z=None) -> EvaluateCI:
+                abs_tol=0.0, first=0, raise_on_status=True, z=None, sampling=None) -> EvaluateCI:
     """Sample the stream `seed` in batches until the confidence interval of c'x + E[obj] is tight
     (twosd_evaluate_ci): half-width <= max(abs_tol, rel_tol |mean|), or n_max scenarios.  z (a
-    quantile of the caller's own, e.g. Student's t) overrides `confidence`."""
+    quantile of the caller's own, e.g. Student's t) overrides `confidence`.  sampling: a Sampling
+    plan (twosd_evaluate_ci_vr): batch holds at least two whole groups, the rule runs on the
+    moments of the group means and n counts groups (n_scenarios: scenarios)."""
     out = _lib.Moments()
     hw = C.c_double()
     conv = C.c_int()
     offset = float(np.dot(first_stage_cost, x))
-    rc = ctx.lib.twosd_evaluate_ci(ctx.h, ptr(_f64(x)), C.c_uint64(seed), C.c_int64(first), C.c_int64(batch),
-                                   C.c_int64(n_max), normal_quantile(confidence) if z is None else float(z), float(rel_tol), float(abs_tol), offset,
-                                   C.byref(out), C.byref(hw), C.byref(conv))
+    zq = normal_quantile(confidence) if z is None else float(z)
+    plan, G = _plan(sampling)
+    if plan is None:
+        rc = ctx.lib.twosd_evaluate_ci(ctx.h, ptr(_f64(x)), C.c_uint64(seed), C.c_int64(first), C.c_int64(batch),
+                                       C.c_int64(n_max), zq, float(rel_tol), float(abs_tol), offset,
+                                       C.byref(out), C.byref(hw), C.byref(conv))
+    else:
+        rc = ctx.lib.twosd_evaluate_ci_vr(ctx.h, ptr(_f64(x)), C.c_uint64(seed), C.c_int64(first), C.c_int64(batch),
+                                          C.c_int64(n_max), zq, float(rel_tol), float(abs_tol), offset,
+                                          C.byref(out), C.byref(hw), C.byref(conv), C.byref(plan))
     _lp_status_ok(rc, raise_on_status)
-    m = Moments._of(out)
-    return EvaluateCI(offset + m.mean, hw.value, m.n, m.n_bad, bool(conv.value), m)
+    m = Moments._of(out, G)
+    return EvaluateCI(offset + m.mean, hw.value, m.n, m.n_bad, bool(conv.value), m, G)
 
 
 def evaluate_epigraph(cuts, incumbent_cut, x, total_scenario_weight, lower_bound, sense=MIN_SENSE):
