@@ -81,6 +81,15 @@ def hash_dual_vector(vec) -> int:
     return struct.unpack("<Q", struct.pack("<d", round16(s)))[0]
 
 
+def hash_dual_rows(P) -> np.ndarray:
+    """hash_dual_vector of every row of P (uint64), vectorised: np.cumsum adds sequentially, so
+    its last column is the reference's sum in index order (inf where that sum overflows)."""
+    P = np.atleast_2d(np.asarray(P, dtype=np.float64))
+    with np.errstate(over="ignore"):
+        sums = np.cumsum(np.abs(P), axis=1)[:, -1] if P.shape[1] else np.zeros(P.shape[0])
+    return round16_vec(sums).view(np.uint64)
+
+
 def dual_isequal(h1, d1, h2, d2) -> bool:
     if len(d1) != len(d2) or h1 != h2:
         return False
@@ -124,8 +133,7 @@ class DualVertexSet:
             for i, (h, d) in enumerate(zip(self.hashes, self.data)):
                 self._by_hash.setdefault(h, []).append(i)
                 self._r16.append(round16_vec(d))
-        sums = np.cumsum(np.abs(P), axis=1)[:, -1] if P.shape[1] else np.zeros(P.shape[0])
-        hb = round16_vec(sums).view(np.uint64)
+        hb = hash_dual_rows(P)
         R = round16_vec(P)
         out = np.empty(P.shape[0], dtype=np.int64)
         for s in range(P.shape[0]):

@@ -24,14 +24,11 @@
 
 namespace twosd {
 
-// Phase 1: one LANE per candidate -> hash (reference, sequential L1 order), fingerprint,
-// has-NaN flag.  The sequential sum is a dependent chain per vector, so each lane walks
-// its own vector; the block's 256 vectors are staged through LDS 16 columns at a time
-// (coalesced 128-byte row segments in, conflict-free stride-17 reads out).
+// Phase 1: hash (reference, sequential L1 order), fingerprint and has-NaN flag of every candidate,
 // one wavefront per vector: the lanes load the row coalesced and fold the order-independent
 // parts (fingerprint sum, NaN flag); |pi_i| goes through LDS and lane 0 adds it in index order
-// (the reference's sequential sum, dual_set.jl:47-50, so the same bits).  Round 3 used one
-// thread per vector: a push of ~4k vectors occupied 16 CUs for ~0.26 ms.
+// (the reference's sequential sum, dual_set.jl:47-50, so the same bits).  One thread per vector
+// was tried first: a push of ~4k vectors occupied 16 CUs for ~0.26 ms.
 constexpr int kKeyWaves = 4;
 __global__ void __launch_bounds__(64 * kKeyWaves) dvs_key_kernel(int count, int m, const double *__restrict__ pis,
                                                                uint64_t *__restrict__ hash, uint64_t *__restrict__ fp,
@@ -258,8 +255,7 @@ static int ensure_capacity(twosd_ctx *c, int need) {
 
 // Push `count` candidates already on the device (row-major count x m).  d_out_index
 // (nullable, device) receives the vertex index of every candidate.
-int dvs_push_device(twosd_ctx *c, int count, const double *d_pis, int *d_out_index, const uint64_t *d_hash,
-                    const uint64_t *d_fp, const int *d_nan) {
+int dvs_push_device(twosd_ctx *c, int count, const double *d_pis, int *d_out_index) {
     if (count <= 0) return TWOSD_OK;
     DvsDevice &D = c->dvs;
     DvsWs *w = ws_of(c);
@@ -281,14 +277,8 @@ int dvs_push_device(twosd_ctx *c, int count, const double *d_pis, int *d_out_ind
     const int ttmask = (int)w->tt.cap - 1;
     const int nb = nblocks_for(count);
     hipLaunchKernelGGL(dvs_fill_kernel, dim3((w->tt.cap + 255) / 256), dim3(256), 0, c->stream, w->tt, (int)w->tt.cap, -1);
-    if (d_hash) {   // keys computed by the producer (LP kernel epilogue)
-        HIPCHK(hipMemcpyAsync(w->chash, d_hash, sizeof(uint64_t) * count, hipMemcpyDeviceToDevice, c->stream));
-        HIPCHK(hipMemcpyAsync(w->cfp, d_fp, sizeof(uint64_t) * count, hipMemcpyDeviceToDevice, c->stream));
-        HIPCHK(hipMemcpyAsync(w->nanflag, d_nan, sizeof(int) * count, hipMemcpyDeviceToDevice, c->stream));
-    } else {
-        hipLaunchKernelGGL(dvs_key_kernel, dim3((count + kKeyWaves - 1) / kKeyWaves), dim3(64 * kKeyWaves),
-                           sizeof(double) * kKeyWaves * m, c->stream, count, m, d_pis, w->chash, w->cfp, w->nanflag);
-    }
+    hipLaunchKernelGGL(dvs_key_kernel, dim3((count + kKeyWaves - 1) / kKeyWaves), dim3(64 * kKeyWaves),
+                       sizeof(double) * kKeyWaves * m, c->stream, count, m, d_pis, w->chash, w->cfp, w->nanflag);
     hipLaunchKernelGGL(dvs_lookup_kernel, dim3(nb), dim3(256), 0, c->stream, count, m, d_pis, w->chash, w->cfp,
                        w->nanflag, D.V, D.hash, D.fp, D.table, D.tcap - 1, w->out);
     hipLaunchKernelGGL(dvs_batch_kernel, dim3(nb), dim3(256), 0, c->stream, count, m, d_pis, w->chash, w->cfp,
@@ -325,7 +315,7 @@ extern "C" int twosd_dvs_push(twosd_ctx *c, int count, const double *pis, int *o
         HIPCHK(hipMemcpy(w->pis, pis, sizeof(double) * need, hipMemcpyHostToDevice));
         hipEvent_t e0 = c->ev[2], e1 = c->ev[3];
         HIPCHK(hipEventRecord(e0, c->stream));
-        int rc = dvs_push_device(c, count, w->pis, nullptr, nullptr, nullptr, nullptr);
+        int rc = dvs_push_device(c, count, w->pis, nullptr);
         if (rc) return rc;
         HIPCHK(hipEventRecord(e1, c->stream));
         HIPCHK(hipEventSynchronize(e1));

@@ -1,5 +1,4 @@
-// dvs_keys.h -- the reference dedup key of a dual vector (src/sd_algorithm/dual_set.jl),
-// shared by the vertex-set kernels and the LP kernel epilogue (which keys its own duals).
+// dvs_keys.h -- the reference dedup key of a dual vector (src/sd_algorithm/dual_set.jl).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <math.h>
@@ -37,12 +36,6 @@ __device__ __forceinline__ uint64_t comp_bits(double x) {
     double r = round16(x);
     if (r == 0.0) r = 0.0;
     return (uint64_t)__double_as_longlong(r);
-}
-
-__device__ __forceinline__ uint64_t wave_sum_u64(uint64_t v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += (uint64_t)__shfl_xor((unsigned long long)v, o);
-    return v;
 }
 
 }  // namespace twosd

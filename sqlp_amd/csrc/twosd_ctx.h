@@ -279,9 +279,7 @@ int vkey_first_occurrences(twosd_ctx *c, int N, const unsigned long long *d_vkey
                            int *U, const int **d_counts = nullptr);
 // dual vertex set (dvs_kernel.hip)
 int dvs_init(twosd_ctx *c);
-// d_hash / d_fp / d_nan: keys precomputed by the producer (nullable: computed here)
-int dvs_push_device(twosd_ctx *c, int count, const double *d_pis, int *d_out_index, const uint64_t *d_hash = nullptr,
-                    const uint64_t *d_fp = nullptr, const int *d_nan = nullptr);
+int dvs_push_device(twosd_ctx *c, int count, const double *d_pis, int *d_out_index);
 // cut (cut_kernel.hip)
 void cut_invalidate_pk(twosd_ctx *c);
 void cut_truncate_pk(twosd_ctx *c, int size);   // V truncated to size: PK rows past it are stale
