@@ -460,6 +460,27 @@ int twosd_cut_stats(twosd_ctx *ctx, int64_t *out);
 int twosd_cut_pass(twosd_ctx *ctx, int *fp32, double *band);
 
 /*
+ * Which pass that was: *kind = 0 the fp64 MFMA pass, 1 the fp32 one, 2 the integer one
+ * (v_mfma_i32_16x16x64_i8 over int8 limbs of fixed-point operands: exact int32 sums, the only error
+ * the bounded operand quantisation; sqlp_amd/csrc/cut_i8.h).  twosd_cut_pass reports *fp32 = 1 for
+ * kinds 1 and 2 and the band of the pass that ran.  *limbs / *pairs (may be NULL): the integer
+ * pass's build-time limb count and number of kept limb pairs.  The integer pass is the default
+ * reduced-precision pass; TWOSD_CUT_I8=0 selects the fp32 one, TWOSD_CUT_F32=0 the fp64 one, and
+ * the device falls back by itself (fp32 envelope failed: 0; a NaN or infinite delta seen: 1).
+ */
+int twosd_cut_pass_kind(twosd_ctx *ctx, int *kind, int *limbs, int *pairs);
+
+/*
+ * Diagnostics for tests: runs one cut of epigraph epi at x (tie_rel 0) and writes the integer
+ * pass's score term t (fp32; the score is base[v] + t) of every scenario s and compacted vertex
+ * position c to out[s * nvc + c], computed by the pass's own device functions.  *nvc_out = the
+ * number of compacted vertices, vmap_out (may be NULL, |V| entries) their vertex indices.  Limited to
+ * N |V| <= 2^20; cap = the floats out holds.  TWOSD_E_STATE when the integer pass is switched off.
+ */
+int twosd_cut_debug_scores(twosd_ctx *ctx, int epi, const double *x, float *out, int64_t cap, int *nvc_out,
+                           int *vmap_out);
+
+/*
  * Multi-GPU split of twosd_build_cut: each rank computes partial sums over its own
  * scenarios into a caller-provided DEVICE buffer (layout in twosd_cut_partial_len),
  * the caller all-reduces it (sum; e.g. torch.distributed / RCCL), then finalize.

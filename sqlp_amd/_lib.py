@@ -85,6 +85,8 @@ SIGNATURES = [
     ("twosd_training_cap", I, [P, C.c_int64, C.c_int64, P]),
     ("twosd_cut_stats", I, [P, P]),
     ("twosd_cut_pass", I, [P, P, P]),
+    ("twosd_cut_pass_kind", I, [P, P, P, P]),
+    ("twosd_cut_debug_scores", I, [P, I, P, P, C.c_int64, P, P]),
     ("twosd_select_refresh_bases", I, [P, P, P, P, I, I, P, P, P]),
     ("twosd_last_objective", I, [P, P, P]),
     ("twosd_refresh_train_bases", I, [P, P, P, P]),

@@ -36,6 +36,9 @@
 //                      per scenario in registers; per-wave partial sums; h via uint64
 //                      fixed-point atomics (exact and order independent -> identical on any
 //                      rank count); the last round's tiles split by vertex range
+//   cut_argmax3_kernel the same pass with fp32 operands (v_mfma_f32_16x16x4f32), the base added in fp64
+//   cut_pkq_kernel / cut_argmax4_kernel  the same pass with fixed-point int8-limb operands
+//                      (v_mfma_i32_16x16x64_i8, cut_i8.h): exact integer sums, the default
 //   cut_tail_merge_kernel  per-range results of the split tiles merged in vertex order
 //   cut_fixup_kernel   scenarios with several vertices in the decision band: their logged
 //                      candidates re-scored in the restatement's order and decided by its rule
@@ -50,6 +53,7 @@
 #include <cstring>
 #include <vector>
 #include "twosd_ctx.h"
+#include "cut_i8.h"
 
 namespace twosd {
 
@@ -78,8 +82,11 @@ struct CutParams {
     const double *base;    // nv: pi_v . bvec in index order (the restatement's base dot)
     const int *eord;       // k: elements by ascending row (the restated score's order)
     const unsigned long long *band_bits;   // the ACTIVE band of this cut, as bits (cut_band_select_kernel)
-    const unsigned long long *mode;        // 1: this cut's MFMA pass runs in fp32 (cut_argmax3_kernel), 0: fp64 (cut_argmax2_kernel)
+    const unsigned long long *mode;        // this cut's MFMA pass: 2 integer limbs (cut_argmax4_kernel), 1 fp32 (cut_argmax3_kernel), 0 fp64 (cut_argmax2_kernel)
     const float *basec32;  // vcap32: basec rounded up to fp32 (-inf past nvc): the fp32 pass's prefilter
+    const int8_t *PKq;     // the integer pass's chunk source: per 32-vertex chunk, limb, 64-wide k-step the int8 limb plane (cut_pkq_kernel)
+    const float *scq;      // vcap32: the integer pass's output scale 2^(S_v + kOutShift) per compacted vertex (0 past nvc)
+    const double *dsc;     // 128: the deltas' quantisation factors 2^(kQ - E_e) (0 past k)
     const float *PKTc32;   // KR32 x vcap32: PKTc's element rows rounded to fp32, no base row (cut_argmax3_kernel's LDS-DMA source)
     double band_scale;     // 4 gamma_{k+4}: twice the 2 gamma bound
     int *arg; double *val; int *flag;   // N; flag != 0: re-decide (main rows: 4-bit log counts per lane group)
@@ -292,19 +299,31 @@ __global__ void __launch_bounds__(256) cut_vbase_kernel(int nv, int m, int k, in
             __syncthreads();
         }
         if (!act) continue;
-        double a = 0.0, pm = 0.0, dm = 0.0;
+        double a = 0.0, pm = 0.0, dm = 0.0, um = 0.0;
         for (int e = lane; e < k; e += 64) {
             const double pc = fabs(PK[(size_t)v * k4 + e] * coef[e]), de = __longlong_as_double((long long)dmax[e]);
             a += pc * de;
             pm = fmax(pm, pc);
             dm = fmax(dm, de);
+            um = fmax(um, ldexp(pc, ci8::scale_exp(de)));   // |u_e| = |pc_e| 2^E_e (cut_i8.h)
         }
 #pragma unroll
         for (int o = 32; o > 0; o >>= 1) {
             a += __shfl_xor(a, o);
             pm = fmax(pm, __shfl_xor(pm, o));
             dm = fmax(dm, __shfl_xor(dm, o));
+            um = fmax(um, __shfl_xor(um, o));
         }
+        // the integer pass's vertex scale (the value cut_pkq_kernel forms) and normalised operand sum
+        const int Sv = ci8::scale_exp(um);
+        double ns = 0.0;
+        for (int e = lane; e < k; e += 64) {
+            const double pc = fabs(PK[(size_t)v * k4 + e] * coef[e]), de = __longlong_as_double((long long)dmax[e]);
+            const int Ee = ci8::scale_exp(de);
+            ns += ldexp(de, -Ee) + ldexp(pc, Ee - Sv);
+        }
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) ns += __shfl_xor(ns, o);
         if (lane == 0) {
             base[v] = s;
             const double t = fabs(s) + a;
@@ -321,28 +340,44 @@ __global__ void __launch_bounds__(256) cut_vbase_kernel(int nv, int m, int k, in
             // operands and sums well inside the fp32 range, or the cut runs the fp64 pass
             const double lim = ldexp(1.0, 100);
             if (!(a < lim && pm < lim && dm < lim)) atomicOr(band_bits + 2, 1ull);
+            // the integer pass: ci8::band_term bounds |t - sum_e pc_e dv_e| for its score term t
+            // (operand quantisation, dropped limb pairs, the level combination's fp32 roundings);
+            // doubled as the others, and the base and the final add stay fp64: the fp64 band is added
+            const double bi8 = b64 + 2.0 * ci8::band_term(k, Sv, ns);
+            atomicMax(band_bits + 5, (unsigned long long)__double_as_longlong(isfinite(bi8) ? bi8 : INFINITY));
         }
     }
 }
 
-// the cut's pass: fp32 when asked and every vertex's operands fit (band_bits[2] == 0), else
-// fp64; band_bits[3] = that pass's band (what every later kernel of the cut reads), [4] = the pass
-__global__ void cut_band_select_kernel(unsigned long long *band_bits, int want32) {
+// the cut's pass: a reduced-precision pass when asked and every vertex's operands fit
+// (band_bits[2] == 0), else fp64; band_bits[3] = that pass's band (what every later kernel of the
+// cut reads), [4] = the pass.
+// The integer pass (2) replaces the fp32 one when asked (wanti8), no delta seen so far was NaN
+// or infinite (*nonfinite == 0, folded with dmax) and its band is finite.
+__global__ void cut_band_select_kernel(unsigned long long *band_bits, int want32, int wanti8,
+                                       const unsigned long long *__restrict__ nonfinite) {
     if (threadIdx.x != 0 || blockIdx.x != 0) return;
-    const unsigned long long m = (want32 && band_bits[2] == 0) ? 1ull : 0ull;
-    band_bits[3] = m ? band_bits[1] : band_bits[0];
+    unsigned long long m = (want32 && band_bits[2] == 0) ? 1ull : 0ull;
+    if (m && wanti8 && *nonfinite == 0 && isfinite(__longlong_as_double((long long)band_bits[5]))) m = 2ull;
+    band_bits[3] = m == 2 ? band_bits[5] : m ? band_bits[1] : band_bits[0];
     band_bits[4] = m;
 }
 
 // dmax[e] = max |dv[s][e]| over scenarios [from, to) folded into the epigraph's running maximum
-// (non-negative doubles order as their bit patterns)
+// (non-negative doubles order as their bit patterns); dmax[k] != 0: some delta was NaN or infinite
 __global__ void __launch_bounds__(256) cut_dmax_kernel(int from, int to, int k, const double *__restrict__ dv,
                                                        unsigned long long *__restrict__ dmax) {
     if ((int)threadIdx.x >= k) return;
     const int e = threadIdx.x;
     double mx = 0.0;
-    for (int s = from + blockIdx.x; s < to; s += gridDim.x) mx = fmax(mx, fabs(dv[(size_t)s * k + e]));   // NaN ignored: its scores never win
+    bool bad = false;
+    for (int s = from + blockIdx.x; s < to; s += gridDim.x) {
+        const double d = dv[(size_t)s * k + e];
+        mx = fmax(mx, fabs(d));   // NaN ignored: its scores never win
+        bad |= !isfinite(d);
+    }
     atomicMax(&dmax[e], (unsigned long long)__double_as_longlong(mx));
+    if (bad) atomicOr(&dmax[k], 1ull);   // a non-finite delta seen: the integer pass is not used (cut_band_select_kernel)
 }
 
 // the decision band of this cut (written by cut_vbase_kernel) through the scalar cache: a
@@ -958,6 +993,381 @@ __global__ void __launch_bounds__(256, TWOSD_CUT3_BPC) cut_argmax3_kernel(CutPar
     }
 }
 
+// ---- v4: the integer MFMA pass (v_mfma_i32_16x16x64_i8).  Both operands are fixed-point numbers
+// of ci8::kL signed limbs (cut_i8.h): the vertex side pc_e = PK[v,e] coef_e at the scale
+// 2^(S_v - E_e), the scenario deltas at 2^E_e, E_e from the epigraph's dmax cache.  The dot product
+// is the sum of the limb-pair products; the pairs with l1 + l2 <= kL - 1 are kept, one exact int32
+// accumulator per level l1 + l2, and ci8::combine folds the levels into the fp32 term t.  The
+// score is base[v] + t in fp64 as in v3, within the integer band of the restated score
+// (cut_vbase_kernel, band_bits[5]); everything after t -- prefilter, exact steps, logs, tail
+// ranges, the fp64 re-read at the tile end -- is v3's.  The i32 C/D layout is the f32 one: register
+// r of a tile is vertex row 4g + r, scenario column j.  An integer sum does not depend on the order
+// of its terms, so the result is the same bits on any hardware and in the numpy model.
+typedef int i4 __attribute__((ext_vector_type(4)));
+
+// The image of one 32-vertex chunk, in global memory and (copied lane-linearly by the LDS-DMA) in
+// LDS: [limb][k-step][g][vertex 0..31][16 bytes]; byte b of (k-step ks, g) is element
+// e = 64 ks + 16 g + b, the 16 k-values lane (g, j) feeds one MFMA.  A wave's ds_read_b128 of a
+// fragment reads 16 consecutive bytes per lane, 256 contiguous bytes per 16 lanes of a g:
+// conflict-free.
+__host__ __device__ constexpr int i8_chunk_bytes(int KS) { return ci8::kL * KS * 2048; }
+__host__ __device__ constexpr int i8_frag_off(int KS, int l, int ks, int g, int vv) { return ((l * KS + ks) * 4 + g) * 512 + vv * 16; }
+
+// the limb planes of the compacted vertices at x, their output scales, and (block 0) the deltas'
+// quantisation factors.  One block per chunk: thread (q, vv) = (t >> 5, t & 31) owns the 16
+// elements e = 16 q + b of vertex position c = 32 chunk + vv.
+__global__ void __launch_bounds__(256) cut_pkq_kernel(int k, int KS, int vcap, const double *__restrict__ PKT,
+                                                      const double *__restrict__ coef, const unsigned long long *__restrict__ dmax,
+                                                      const int *__restrict__ vmap, const int *__restrict__ nvc_p,
+                                                      int8_t *__restrict__ PKq, float *__restrict__ scq, double *__restrict__ dsc) {
+    __shared__ double smax[8][32];
+    const int t = threadIdx.x, vv = t & 31, q = t >> 5;
+    const int c = blockIdx.x * 32 + vv;
+    const bool act = q < 4 * KS, in = c < *nvc_p;
+    const int v = in ? vmap[c] : 0;
+    if (blockIdx.x == 0 && t < 128)
+        dsc[t] = t < k ? ldexp(1.0, ci8::kQ - ci8::scale_exp(__longlong_as_double((long long)dmax[t]))) : 0.0;
+    double pc[16];
+    int Ee[16];
+    double mx = 0.0;
+#pragma unroll
+    for (int b = 0; b < 16; ++b) {
+        const int e = 16 * q + b;
+        pc[b] = 0.0;
+        Ee[b] = 0;
+        if (act && in && e < k) {
+            pc[b] = coef[e] * PKT[(size_t)e * vcap + v];
+            Ee[b] = ci8::scale_exp(__longlong_as_double((long long)dmax[e]));
+            mx = fmax(mx, fabs(ldexp(pc[b], Ee[b])));
+        }
+    }
+    smax[q][vv] = mx;
+    __syncthreads();
+#pragma unroll
+    for (int qq = 0; qq < 8; ++qq) mx = fmax(mx, smax[qq][vv]);
+    const int S = ci8::scale_exp(mx);
+    if (q == 0) scq[c] = in ? ldexpf(1.0f, S + ci8::kOutShift) : 0.0f;
+    if (!act) return;
+    unsigned wd[ci8::kL][4] = {};
+#pragma unroll
+    for (int b = 0; b < 16; ++b) {
+        int8_t lb[ci8::kL];
+        ci8::limbs(ci8::quantise(pc[b], S - Ee[b]), lb);   // u_e = pc_e 2^E_e at scale S: one exact scaling
+#pragma unroll
+        for (int l = 0; l < ci8::kL; ++l) wd[l][b >> 2] |= (unsigned)(uint8_t)lb[l] << (8 * (b & 3));
+    }
+    int8_t *img = PKq + (size_t)blockIdx.x * i8_chunk_bytes(KS);
+#pragma unroll
+    for (int l = 0; l < ci8::kL; ++l) {
+        i4 o = {(int)wd[l][0], (int)wd[l][1], (int)wd[l][2], (int)wd[l][3]};
+        *reinterpret_cast<i4 *>(img + i8_frag_off(KS, l, q >> 2, q & 3, vv)) = o;
+    }
+}
+
+// lane (g, .)'s quantised deltas of scenario s: per k-step and limb the 16 bytes e = 64 ks + 16 g + b
+// (the MFMA's B operand), from the fp64 deltas
+template <int KS>
+__device__ __forceinline__ void i8_quant_deltas(const CutParams &P, int s, int g, i4 (&d)[KS][ci8::kL]) {
+#pragma unroll
+    for (int ks = 0; ks < KS; ++ks) {
+        unsigned wd[ci8::kL][4] = {};
+#pragma unroll
+        for (int b = 0; b < 16; ++b) {
+            const int e = 64 * ks + 16 * g + b;
+            const double x = (s < P.N && e < P.k) ? P.dv[(size_t)s * P.k + e] : 0.0;
+            int8_t lb[ci8::kL];
+            ci8::limbs(ci8::quantise_by(x, P.dsc[e]), lb);
+#pragma unroll
+            for (int l = 0; l < ci8::kL; ++l) wd[l][b >> 2] |= (unsigned)(uint8_t)lb[l] << (8 * (b & 3));
+        }
+#pragma unroll
+        for (int l = 0; l < ci8::kL; ++l) d[ks][l] = i4{(int)wd[l][0], (int)wd[l][1], (int)wd[l][2], (int)wd[l][3]};
+    }
+}
+
+// the level sums of one chunk image (LDS or global) against one scenario tile: acc[level][vertex
+// tile].  One scenario tile at a time halves the live accumulators (24 registers for kL = 3); the
+// second tile reads the fragments from LDS again.
+template <int KS>
+__device__ __forceinline__ void i8_chunk_mma(const int8_t *img, int g, int j, const i4 (&d)[KS][ci8::kL], i4 (&acc)[ci8::kL][2]) {
+#pragma unroll
+    for (int ks = 0; ks < KS; ++ks) {
+#pragma unroll
+        for (int l1 = 0; l1 < ci8::kL; ++l1) {
+            const i4 x0 = *reinterpret_cast<const i4 *>(img + i8_frag_off(KS, l1, ks, g, j));
+            const i4 x1 = *reinterpret_cast<const i4 *>(img + i8_frag_off(KS, l1, ks, g, 16 + j));
+#pragma unroll
+            for (int l2 = 0; l1 + l2 < ci8::kL; ++l2) {
+                i4 *a = acc[l1 + l2];
+                a[0] = __builtin_amdgcn_mfma_i32_16x16x64_i8(x0, d[ks][l2], a[0], 0, 0, 0);
+                a[1] = __builtin_amdgcn_mfma_i32_16x16x64_i8(x1, d[ks][l2], a[1], 0, 0, 0);
+            }
+        }
+    }
+}
+
+// t of this lane's 8 scores of a chunk and scenario tile: sc[r] / sc[4 + r] the output scales of
+// its vertices 4g + r / 16 + 4g + r
+__device__ __forceinline__ void i8_chunk_scores(const i4 (&acc)[ci8::kL][2], const float (&sc)[8], f4 &tlo, f4 &thi) {
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+        int lo[ci8::kL], hi[ci8::kL];
+#pragma unroll
+        for (int l = 0; l < ci8::kL; ++l) { lo[l] = acc[l][0][r]; hi[l] = acc[l][1][r]; }
+        tlo[r] = ci8::combine(lo, sc[r]);
+        thi[r] = ci8::combine(hi, sc[4 + r]);
+    }
+}
+
+#ifndef TWOSD_CUT4_BPC
+#define TWOSD_CUT4_BPC 3                 // blocks per CU the integer pass is compiled for
+#endif
+
+template <int KB>
+__global__ void __launch_bounds__(256, TWOSD_CUT4_BPC) cut_argmax4_kernel(CutParams P) {
+    if (*P.mode != 2) return;                       // another pass runs this cut
+    constexpr int KS = KB <= 16 ? 1 : 2;            // k-steps of 64 (k <= 64: KB <= 16)
+    constexpr int CB = i8_chunk_bytes(KS);
+    __shared__ __attribute__((aligned(16))) int8_t Bs[2][CB];   // double-buffered chunk image
+    __shared__ double Bb[3][kVT2];                  // the chunks' fp64 bases (ring of 3: finish reads chunk ch - 1)
+    extern __shared__ unsigned long long hl[];      // nv entries when P.hist_lds
+    const int lane = threadIdx.x & 63;
+    const int wid = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    if (P.hist_lds)
+        for (int v = threadIdx.x; v < P.nv; v += 256) hl[v] = 0ull;
+    const int g = lane >> 4, j = lane & 15;
+    const int ntiles = (P.N + kCutTile2 - 1) / kCutTile2;
+    const int nvc = *P.nvc;
+    const int nchunks = (nvc + kVT2 - 1) / kVT2;
+    const int nunits = P.full_units + (ntiles - P.full_units) * P.tail_S;
+    const double band = cut_band_scalar(P);
+    const double rel = P.tie_rel;
+    double pv_sum = 0.0;
+    double Sacc[2] = {0.0, 0.0};   // lane (g, j): e = 4 kb + g for kb = j, j + 16
+
+    for (int unit = blockIdx.x; unit < nunits; unit += gridDim.x) {
+        const bool tail = unit >= P.full_units;
+        const int tile = tail ? P.full_units + (unit - P.full_units) / P.tail_S : unit;
+        const int range = tail ? (unit - P.full_units) % P.tail_S : 0;
+        const int c_lo = tail ? (int)((long long)nchunks * range / P.tail_S) : 0;
+        const int c_hi = tail ? (int)((long long)nchunks * (range + 1) / P.tail_S) : nchunks;
+        const int s0 = tile * kCutTile2 + wid * 32;
+        const int sa = s0 + j, sb = s0 + 16 + j;
+        i4 d0[KS][ci8::kL], d1[KS][ci8::kL];
+        i8_quant_deltas<KS>(P, sa, g, d0);
+        i8_quant_deltas<KS>(P, sb, g, d1);
+        RowEx rb0, rb1;
+        rb0.M = -INFINITY; rb0.thr = -INFINITY; rb0.I = -1; rb0.n = 0; rb0.f = 0; rb0.thr32 = -INFINITY;
+        rb1 = rb0;
+        int *const lbase = tail ? P.tcand : P.cand;
+        const unsigned log0 = tail ? (unsigned)(((((size_t)(s0 + j - P.full_units * kCutTile2)) * P.tail_S + range) * 4 + g) * kCandC)
+                                      : (unsigned)((((size_t)(s0 + j)) * 4 + g) * kCandC);
+        const unsigned lstep = 16u * (tail ? P.tail_S : 1) * 4 * kCandC;
+
+        // LDS-DMA staging: the chunk image is copied as it lies, 1 KiB (64 lanes x 16 bytes) per instruction
+        auto stage = [&](int buf, int bslot, int v0) {
+            const int8_t *src = P.PKq + (size_t)(v0 / kVT2) * CB;
+            for (int i = wid; i < CB / 1024; i += 4)
+                __builtin_amdgcn_global_load_lds((const void *)(src + i * 1024 + lane * 16),
+                                                 (__attribute__((address_space(3))) void *)&Bs[buf][i * 1024], 16, 0, 0);
+            if (wid == 3 && lane < 16)
+                __builtin_amdgcn_global_load_lds((const void *)(P.basec + v0 + 2 * lane),
+                                                 (__attribute__((address_space(3))) void *)&Bb[bslot][0], 16, 0, 0);
+        };
+        // this lane's 8 vertices of a chunk: prefilter bases (as v3) and output scales
+        auto load_bases = [&](float (&bq)[8], float (&sq)[8], int v0) {
+            const f4 lo = *reinterpret_cast<const f4 *>(P.basec32 + v0 + 4 * g);
+            const f4 hi = *reinterpret_cast<const f4 *>(P.basec32 + v0 + 16 + 4 * g);
+            const f4 slo = *reinterpret_cast<const f4 *>(P.scq + v0 + 4 * g);
+            const f4 shi = *reinterpret_cast<const f4 *>(P.scq + v0 + 16 + 4 * g);
+#pragma unroll
+            for (int r = 0; r < 4; ++r) { bq[r] = lo[r]; bq[4 + r] = hi[r]; sq[r] = slo[r]; sq[4 + r] = shi[r]; }
+        };
+        // v3's finish: prefilter in fp32, exact steps in vertex order for the lanes past it
+        auto finish = [&](const f4 &q00, const f4 &q01, const f4 &q10, const f4 &q11, const float (&bb)[8], int vb, int bslot) {
+            unsigned m0 = 0, m1 = 0;
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                m0 |= (unsigned)(bb[r] + q00[r] >= rb0.thr32) << r;
+                m1 |= (unsigned)(bb[r] + q01[r] >= rb1.thr32) << r;
+                m0 |= (unsigned)(bb[4 + r] + q10[r] >= rb0.thr32) << (4 + r);
+                m1 |= (unsigned)(bb[4 + r] + q11[r] >= rb1.thr32) << (4 + r);
+            }
+            while (__builtin_amdgcn_ballot_w64((m0 | m1) != 0) != 0) {
+                const int r0 = m0 ? __builtin_ctz(m0) : 0, r1 = m1 ? __builtin_ctz(m1) : 0;
+                const int o0 = (r0 >> 2) * 16 + 4 * g + (r0 & 3), o1 = (r1 >> 2) * 16 + 4 * g + (r1 & 3);
+                const double b0 = Bb[bslot][o0], b1 = Bb[bslot][o1];
+                const float t0 = r0 < 4 ? q00[r0 & 3] : q10[r0 & 3];
+                const float t1 = r1 < 4 ? q01[r1 & 3] : q11[r1 & 3];
+                const double s0 = (vb + o0 < nvc ? b0 : -INFINITY) + (double)t0;
+                const double s1 = (vb + o1 < nvc ? b1 : -INFINITY) + (double)t1;
+                if (m0) row_fast<true>(rb0, s0, vb + o0, rel, band, lbase, log0);
+                if (m1) row_fast<true>(rb1, s1, vb + o1, rel, band, lbase, log0 + lstep);
+                m0 &= m0 - 1;
+                m1 &= m1 - 1;
+            }
+        };
+        f4 p[4] = {};
+        float bp[8];
+        int pv0 = 0;
+        stage(0, 0, c_lo * kVT2);
+        __syncthreads();
+        int bs = 0, bsp = 0;   // base ring slots of chunks ch and ch - 1
+        for (int ch = c_lo; ch < c_hi; ++ch) {
+            const int buf = (ch - c_lo) & 1;
+            const int v0 = ch * kVT2;
+            float bq[8], sq[8];
+            load_bases(bq, sq, v0);                 // in flight under the MFMAs
+            if (ch + 1 < c_hi) stage(buf ^ 1, bs == 2 ? 0 : bs + 1, v0 + kVT2);
+            {
+                i4 acc[ci8::kL][2] = {};
+                i8_chunk_mma<KS>(&Bs[buf][0], g, j, d0, acc);
+                if (ch > c_lo) finish(p[0], p[1], p[2], p[3], bp, pv0, bsp);   // the previous chunk, under these MFMAs
+                i8_chunk_scores(acc, sq, p[0], p[2]);
+            }
+            __builtin_amdgcn_sched_barrier(0);
+            {
+                i4 acc[ci8::kL][2] = {};
+                i8_chunk_mma<KS>(&Bs[buf][0], g, j, d1, acc);
+                i8_chunk_scores(acc, sq, p[1], p[3]);
+            }
+#pragma unroll
+            for (int r = 0; r < 8; ++r) bp[r] = bq[r];
+            pv0 = v0;
+            bsp = bs;
+            bs = bs == 2 ? 0 : bs + 1;
+            __syncthreads();
+        }
+        if (c_hi > c_lo) finish(p[0], p[1], p[2], p[3], bp, pv0, bsp);
+        int pk0, pk1, nt0, nt1;
+        combine_ex(rb0, rel, band, g, pk0, nt0);
+        combine_ex(rb1, rel, band, g, pk1, nt1);
+        if (rb0.n > 0 && (tail || nt0 >= 2)) lbase[log0] = rb0.f;
+        if (rb1.n > 0 && (tail || nt1 >= 2)) lbase[log0 + lstep] = rb1.f;
+        rb0.I = rb0.I >= 0 ? P.vmap[rb0.I] : -1;
+        rb1.I = rb1.I >= 0 ? P.vmap[rb1.I] : -1;
+        if (tail) {
+            if (g == 0) {
+                const int t0 = P.full_units * kCutTile2;
+                if (sa < P.N) {
+                    const size_t o = (size_t)(sa - t0) * P.tail_S + range;
+                    P.tp_m[o] = rb0.M; P.tp_i[o] = rb0.I; P.tp_f[o] = pk0;
+                }
+                if (sb < P.N) {
+                    const size_t o = (size_t)(sb - t0) * P.tail_S + range;
+                    P.tp_m[o] = rb1.M; P.tp_i[o] = rb1.I; P.tp_f[o] = pk1;
+                }
+            }
+            continue;
+        }
+        if (nt0 < 2) pk0 = 0;
+        if (nt1 < 2) pk1 = 0;
+        const bool ok0 = sa < P.N && !pk0 && rb0.I >= 0, ok1 = sb < P.N && !pk1 && rb1.I >= 0;
+        const double p0 = ok0 ? P.w[sa] * P.inv_total : 0.0, p1 = ok1 ? P.w[sb] * P.inv_total : 0.0;
+        // v3's tile end: the fp64 deltas again for the S_e terms and the decided rows' values
+        auto fin = [&](int sx, bool ok, int ai, double pp) -> double {
+            const double *pk = P.PK + (size_t)(ai >= 0 ? ai : 0) * P.k4;
+            const double pu = ok ? pp : 0.0;
+            constexpr int FG = 6;
+            double cg = 0.0;
+#pragma unroll
+            for (int k0 = 0; k0 < KB; k0 += FG) {
+                double d64[FG], pke[FG];
+#pragma unroll
+                for (int u = 0; u < FG; ++u) {
+                    const int e = 4 * (k0 + u) + g;
+                    const bool in = k0 + u < KB && e < P.k;
+                    d64[u] = (in && sx < P.N) ? P.dv[(size_t)sx * P.k + e] : 0.0;
+                    pke[u] = in ? pk[e] : 0.0;
+                }
+#pragma unroll
+                for (int u = 0; u < FG; ++u) {
+                    const int kb = k0 + u, e = 4 * kb + g;
+                    if (kb >= KB) break;
+                    if (e < P.k) cg = fma(pke[u] * P.coef[e], d64[u], cg);
+                    double v = (e < P.k) ? pu * pke[u] * d64[u] : 0.0;
+#pragma unroll
+                    for (int o = 8; o > 0; o >>= 1) v += __shfl_xor(v, o);
+                    if (j == (kb & 15)) {
+                        if (kb < 16) Sacc[0] += v;
+                        else Sacc[1] += v;
+                    }
+                }
+            }
+            return dec_combine(cg);
+        };
+        const double tv0 = fin(sa, ok0, rb0.I, p0);
+        const double tv1 = fin(sb, ok1, rb1.I, p1);
+        const double vl0 = ok0 ? P.base[rb0.I] + tv0 : rb0.M, vl1 = ok1 ? P.base[rb1.I] + tv1 : rb1.M;
+        if (g == 0) {
+            if (sa < P.N) { P.arg[sa] = rb0.I; P.val[sa] = vl0; P.flag[sa] = pk0; }
+            if (sb < P.N) { P.arg[sb] = rb1.I; P.val[sb] = vl1; P.flag[sb] = pk1; }
+        }
+#pragma unroll
+        for (int t = 0; t < 2; ++t) {
+#pragma unroll
+            for (int jj = 0; jj < 16; ++jj) {
+                const int ok = __shfl(t == 0 ? (int)ok0 : (int)ok1, jj);
+                const int ai = __shfl(t == 0 ? rb0.I : rb1.I, jj);
+                const double pp = __shfl(t == 0 ? p0 : p1, jj);
+                const double vl = __shfl(t == 0 ? vl0 : vl1, jj);
+                if (lane == 0 && ok) {
+                    pv_sum = fma(pp, vl, pv_sum);
+                    const unsigned long long hq = (unsigned long long)__double2ull_rn(pp * kFix);
+                    if (P.hist_lds) __hip_atomic_fetch_add(&hl[ai], hq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                    else atomicAdd(&P.hist[ai], hq);
+                }
+            }
+        }
+    }
+    if (P.hist_lds) {
+        __syncthreads();
+        for (int v = threadIdx.x; v < P.nv; v += 256) P.hist_part[(size_t)blockIdx.x * P.nv + v] = hl[v];
+    }
+    const int slot = blockIdx.x * 4 + wid;
+    double *out = P.partial + (size_t)slot * (P.k + 1);
+    if (lane == 0) out[0] = pv_sum;
+#pragma unroll
+    for (int t = 0; t < 2; ++t) {
+        const int e = 4 * (j + 16 * t) + g;
+        if (e < P.k) out[1 + e] = Sacc[t];
+    }
+}
+
+// diagnostics: the integer pass's t of every (scenario, compacted vertex), out[s * nvc + c], by the
+// device functions of cut_argmax4_kernel (the chunk images read from global memory)
+template <int KS>
+__global__ void __launch_bounds__(256) cut_scores4_kernel(CutParams P, float *__restrict__ out) {
+    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+    const int g = lane >> 4, j = lane & 15;
+    const int nvc = *P.nvc;
+    const int nchunks = (nvc + kVT2 - 1) / kVT2;
+    const int s0 = blockIdx.x * kCutTile2 + wid * 32;
+    const int sa = s0 + j, sb = s0 + 16 + j;
+    i4 d0[KS][ci8::kL], d1[KS][ci8::kL];
+    i8_quant_deltas<KS>(P, sa, g, d0);
+    i8_quant_deltas<KS>(P, sb, g, d1);
+    for (int ch = 0; ch < nchunks; ++ch) {
+        const int v0 = ch * kVT2;
+        float sq[8];
+#pragma unroll
+        for (int r = 0; r < 4; ++r) { sq[r] = P.scq[v0 + 4 * g + r]; sq[4 + r] = P.scq[v0 + 16 + 4 * g + r]; }
+        f4 t[4];
+        for (int st = 0; st < 2; ++st) {
+            i4 acc[ci8::kL][2] = {};
+            i8_chunk_mma<KS>(P.PKq + (size_t)ch * i8_chunk_bytes(KS), g, j, st ? d1 : d0, acc);
+            i8_chunk_scores(acc, sq, t[st], t[2 + st]);
+        }
+#pragma unroll
+        for (int tile = 0; tile < 4; ++tile)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const int c = v0 + (tile >> 1) * 16 + 4 * g + r, s = (tile & 1) ? sb : sa;
+                if (c < nvc && s < P.N) out[(size_t)s * nvc + c] = t[tile][r];
+            }
+    }
+}
+
 // hist[v] += sum over blocks of the block histograms (integers: exact in any order)
 __global__ void __launch_bounds__(256) cut_hist_reduce_kernel(int nb, int nv, const unsigned long long *__restrict__ part,
                                                               unsigned long long *__restrict__ hist) {
@@ -1524,7 +1934,11 @@ struct CutWs {
     CutBuf<double> PK, PKT, PKO;
     CutBuf<double> PKTc;
     CutBuf<float> PKTc32;               // the fp32 pass's chunk source
-    CutBuf<float> basec32;              // the fp32 pass's prefilter bases
+    CutBuf<float> basec32;              // the fp32 and integer passes' prefilter bases
+    CutBuf<int8_t> PKq;                 // the integer pass's chunk images (limb planes), per x
+    CutBuf<float> scq;                  // its output scales per compacted vertex, per x
+    CutBuf<double> dsc;                 // its delta quantisation factors (128)
+    int i8_ks = 0;                      // k-steps of the images the last cut wrote (0: none)
     // PK rows up to date, the vertices PK / PKT / PKO / phash / tprev hold, and their row length
     int pk_count = 0, pk_vcap = 0, pk_k4 = 0;
     CutBuf<int> rows;
@@ -1666,6 +2080,23 @@ static int argmax3_occupancy(int KB, size_t dyn_lds) {
 static void launch_argmax3(int KB, const CutParams &P, int nblocks, hipStream_t s) {
     CUT_KB_SWITCH(launch_argmax3_t, P, nblocks, s)
 }
+template <int KB>
+static void launch_argmax4_t(const CutParams &P, int nblocks, hipStream_t s) {
+    hipLaunchKernelGGL(cut_argmax4_kernel<KB>, dim3(nblocks), dim3(256), P.hist_lds ? sizeof(unsigned long long) * P.nv : 0, s, P);
+}
+template <int KB>
+static int argmax4_occupancy_t(size_t dyn_lds) {
+    int nb = 0;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, cut_argmax4_kernel<KB>, 256, dyn_lds) != hipSuccess) nb = 0;
+    return nb;
+}
+static int argmax4_occupancy(int KB, size_t dyn_lds) {
+    CUT_KB_SWITCH(argmax4_occupancy_t, dyn_lds)
+    return 0;
+}
+static void launch_argmax4(int KB, const CutParams &P, int nblocks, hipStream_t s) {
+    CUT_KB_SWITCH(launch_argmax4_t, P, nblocks, s)
+}
 
 static void launch_argmax(int KB, const CutParams &P, int nblocks, hipStream_t s) {
     switch (KB) {
@@ -1756,6 +2187,11 @@ static int cut_partial_impl(twosd_ctx *c, int epi, const double *x, double tie_r
     // runs the fp64 pass anyway (decided on the device, cut_band_select_kernel)
     const int KB32 = kb_for(k4);
     const bool want32 = KB32 > 0 && (!getenv("TWOSD_CUT_F32") || atoi(getenv("TWOSD_CUT_F32")) != 0);
+    // the integer (int8-limb) MFMA pass in place of the fp32 one (cut_argmax4_kernel; k <= 128 holds
+    // for every k the envelope admits) unless TWOSD_CUT_I8=0; the device falls back to the fp32 or
+    // fp64 pass for a cut it does not fit (cut_band_select_kernel)
+    const bool wanti8 = want32 && (!getenv("TWOSD_CUT_I8") || atoi(getenv("TWOSD_CUT_I8")) != 0);
+    const int KS8 = KB32 <= 16 ? 1 : 2;
     int rc;
     if ((rc = update_pk(c))) return rc;
     // host: bvec = r - (T x) as the reference writes it (`coef.rhs - coef.transfer * x`,
@@ -1786,7 +2222,9 @@ static int cut_partial_impl(twosd_ctx *c, int epi, const double *x, double tie_r
     static const int bpc_env = getenv("TWOSD_CUT_BPC") ? atoi(getenv("TWOSD_CUT_BPC")) : 0;
     int bpc = bpc_env;
     if (bpc <= 0)
-        bpc = want32 ? argmax3_occupancy(KB32, sizeof(unsigned long long) * kHistLds) : argmax_occupancy(KB, sizeof(unsigned long long) * kHistLds);
+        bpc = wanti8   ? argmax4_occupancy(KB32, sizeof(unsigned long long) * kHistLds)
+              : want32 ? argmax3_occupancy(KB32, sizeof(unsigned long long) * kHistLds)
+                       : argmax_occupancy(KB, sizeof(unsigned long long) * kHistLds);
     if (bpc <= 0) bpc = 2;
     const int nchunks = (nv + kVT2 - 1) / kVT2;
     // The persistent grid runs whole tiles round after round; the tiles past the last full
@@ -1836,7 +2274,8 @@ static int cut_partial_impl(twosd_ctx *c, int epi, const double *x, double tie_r
     }
     if ((rc = w->cand.fit(cand_need))) return rc;
     if ((rc = w->tcand.fit(tcand_need))) return rc;
-    // band_bits: [0] fp64 band, [1] fp32 band, [2] fp32 operands out of range, [3] the active band, [4] the pass
+    // band_bits: [0] fp64 band, [1] fp32 band, [2] fp32 operands out of range, [3] the active band, [4] the pass,
+    // [5] the integer pass's band
     if (!w->band_bits && (rc = w->band_bits.alloc(8))) return rc;
     if (!w->fstats && (rc = w->fstats.alloc(16))) return rc;
     HIPCHK(hipMemsetAsync(w->fstats, 0, sizeof(unsigned long long) * 16, c->stream));
@@ -1852,8 +2291,9 @@ static int cut_partial_impl(twosd_ctx *c, int epi, const double *x, double tie_r
     // mean the rows were replaced: fold everything in again (a too-small dmax would narrow the
     // decision band and mark near-tied rows decided without a fixup).
     if (w->dmax_k[epi] != k || w->dmax_rows[epi] > N) {
-        if ((rc = w->dmax[epi].alloc(std::max(k, 1)))) return rc;
-        HIPCHK(hipMemsetAsync(w->dmax[epi], 0, sizeof(unsigned long long) * std::max(k, 1), c->stream));
+        // k maxima and the non-finite flag (entry k)
+        if ((rc = w->dmax[epi].alloc(std::max(k, 1) + 1))) return rc;
+        HIPCHK(hipMemsetAsync(w->dmax[epi], 0, sizeof(unsigned long long) * (std::max(k, 1) + 1), c->stream));
         w->dmax_k[epi] = k;
         w->dmax_rows[epi] = 0;
     }
@@ -1877,7 +2317,8 @@ static int cut_partial_impl(twosd_ctx *c, int epi, const double *x, double tie_r
     }
     hipLaunchKernelGGL(cut_vbase_kernel, dim3(std::max(1, std::min((nv + 3) / 4, 4096))), dim3(256), 0, c->stream, nv, m, k, k4,
                        c->dvs.V, w->bvec, w->PK, w->coef, w->dmax[epi], w->base, w->band_bits, band_scale, band_scale32);
-    hipLaunchKernelGGL(cut_band_select_kernel, dim3(1), dim3(64), 0, c->stream, w->band_bits, want32 ? 1 : 0);
+    hipLaunchKernelGGL(cut_band_select_kernel, dim3(1), dim3(64), 0, c->stream, w->band_bits, want32 ? 1 : 0, wanti8 ? 1 : 0,
+                       w->dmax[epi] + k);
     CutParams P{};
     P.band_scale = band_scale;
     P.N = N; P.k = k; P.k4 = k4; P.nv = nv; P.vcap = w->pk_vcap; P.m = m;
@@ -1913,6 +2354,15 @@ static int cut_partial_impl(twosd_ctx *c, int epi, const double *x, double tie_r
                            c->stream, nv, k4, w->vmap, w->nvc, w->PKO, w->base, w->PKOc, w->basec, vcap32,
                            want32 ? w->basec32 : nullptr);
         P.basec32 = w->basec32;
+        w->i8_ks = 0;
+        if (wanti8) {
+            if ((rc = w->PKq.fit((size_t)(vcap32 / 32) * i8_chunk_bytes(KS8))) || (rc = w->scq.fit((size_t)vcap32))) return rc;
+            if (!w->dsc && (rc = w->dsc.alloc(128))) return rc;
+            hipLaunchKernelGGL(cut_pkq_kernel, dim3(vcap32 / 32), dim3(256), 0, c->stream, k, KS8, w->pk_vcap, w->PKT, w->coef,
+                               w->dmax[epi], w->vmap, w->nvc, w->PKq, w->scq, w->dsc);
+            w->i8_ks = KS8;
+        }
+        P.PKq = w->PKq; P.scq = w->scq; P.dsc = w->dsc;
         P.PKTc = w->PKTc;
         P.vcap32 = vcap32;
         P.vmap = w->vmap;
@@ -1923,7 +2373,8 @@ static int cut_partial_impl(twosd_ctx *c, int epi, const double *x, double tie_r
     P.arg = w->arg; P.val = w->val; P.flag = w->flag; P.hist = d_hist; P.partial = w->partial;
     P.full_units = full; P.tail_S = S; P.fx_gs = fx_gs;
     P.tp_m = w->tp_m; P.tp_i = w->tp_i; P.tp_f = w->tp_f;
-    if (want32) launch_argmax3(KB32, P, nblocks, c->stream);   // each of the two returns at once unless its pass runs
+    if (wanti8) launch_argmax4(KB32, P, nblocks, c->stream);   // each of the three returns at once unless its pass runs
+    if (want32) launch_argmax3(KB32, P, nblocks, c->stream);
     launch_argmax(KB, P, nblocks, c->stream);
     if (P.hist_lds)
         hipLaunchKernelGGL(cut_hist_reduce_kernel, dim3((nv + 255) / 256), dim3(256), 0, c->stream, nblocks, nv, w->hist_part,
@@ -2068,8 +2519,58 @@ extern "C" int twosd_cut_pass(twosd_ctx *c, int *fp32, double *band) {
     HIPCHK(hipSetDevice(c->device));
     HIPCHK(hipStreamSynchronize(c->stream));
     HIPCHK(hipMemcpy(h, w->band_bits, sizeof(h), hipMemcpyDeviceToHost));
-    *fp32 = (int)h[4];
+    *fp32 = h[4] != 0;   // a reduced-precision pass ran: fp32 or integer (twosd_cut_pass_kind tells which)
     if (band) memcpy(band, &h[3], sizeof(double));
+    return TWOSD_OK;
+}
+
+extern "C" int twosd_cut_pass_kind(twosd_ctx *c, int *kind, int *limbs, int *pairs) {
+    if (!c || !kind) return fail(TWOSD_E_ARG, "cut_pass_kind: NULL");
+    *kind = 0;
+    if (limbs) *limbs = ci8::kL;
+    if (pairs) *pairs = ci8::kPairs;
+    CutWs *w = c->cut_ws.get();
+    if (!w || !w->band_bits) return TWOSD_OK;
+    unsigned long long h[8] = {};
+    HIPCHK(hipSetDevice(c->device));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    HIPCHK(hipMemcpy(h, w->band_bits, sizeof(h), hipMemcpyDeviceToHost));
+    *kind = (int)h[4];
+    return TWOSD_OK;
+}
+
+extern "C" int twosd_cut_debug_scores(twosd_ctx *c, int epi, const double *x, float *out, int64_t cap, int *nvc_out,
+                                      int *vmap_out) {
+    int rc = check_cut_args(c, epi, x);
+    if (rc) return rc;
+    if (!out || !nvc_out) return fail(TWOSD_E_ARG, "cut_debug_scores: NULL");
+    HIPCHK(hipSetDevice(c->device));
+    const EpiDevice &E = c->epis[epi];
+    CutWs *w = cws(c);
+    const int nv = c->dvs.size, N = E.count;
+    if (N <= 0 || !(E.total_weight > 0.0)) return fail(TWOSD_E_STATE, "cut_debug_scores: the epigraph has no scenarios");
+    if ((long long)N * nv > (1ll << 20)) return fail(TWOSD_E_UNSUPPORTED, "cut_debug_scores: N |V| = %lld exceeds 2^20", (long long)N * nv);
+    if ((rc = w->hist.fit(nv)) || (rc = w->sums.fit(c->k + 1))) return rc;
+    // one cut at x prepares every operand of the pass (and runs whichever pass applies)
+    c->last_cut_epi = -1;
+    if ((rc = cut_partial_impl(c, epi, x, 0.0, E.total_weight, w->hist, w->sums))) return rc;
+    if (!w->i8_ks) return fail(TWOSD_E_STATE, "cut_debug_scores: the integer pass is switched off (TWOSD_CUT_F32 / TWOSD_CUT_I8)");
+    int nvc = 0;
+    HIPCHK(hipStreamSynchronize(c->stream));
+    HIPCHK(hipMemcpy(&nvc, w->nvc, sizeof(int), hipMemcpyDeviceToHost));
+    if ((int64_t)N * nvc > cap) return fail(TWOSD_E_ARG, "cut_debug_scores: out holds %lld floats, %lld needed", (long long)cap, (long long)N * nvc);
+    DevBuf<float, 4> d_out;
+    if ((rc = d_out.alloc((size_t)N * nvc))) return rc;
+    CutParams P{};
+    P.N = N; P.k = c->k; P.nvc = w->nvc; P.dv = E.d_dv; P.PKq = w->PKq; P.scq = w->scq; P.dsc = w->dsc;
+    const int nb = (N + kCutTile2 - 1) / kCutTile2;
+    if (w->i8_ks == 1) hipLaunchKernelGGL(cut_scores4_kernel<1>, dim3(nb), dim3(256), 0, c->stream, P, d_out.p);
+    else hipLaunchKernelGGL(cut_scores4_kernel<2>, dim3(nb), dim3(256), 0, c->stream, P, d_out.p);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(c->stream));
+    HIPCHK(hipMemcpy(out, d_out.p, sizeof(float) * (size_t)N * nvc, hipMemcpyDeviceToHost));
+    if (vmap_out) HIPCHK(hipMemcpy(vmap_out, w->vmap, sizeof(int) * nvc, hipMemcpyDeviceToHost));
+    *nvc_out = nvc;
     return TWOSD_OK;
 }
 

@@ -293,6 +293,24 @@ class SDContext:
         check(self.lib.twosd_cut_pass(self.h, C.byref(f), C.byref(b)))
         return f.value, b.value
 
+    def cut_pass_kind(self):
+        """(kind, limbs, pairs) of the last cut: kind 0 the fp64 MFMA pass, 1 the fp32 one, 2 the
+        integer (int8-limb) one; the integer pass's limb count and kept limb pairs
+        (twosd_cut_pass_kind)."""
+        kind, limbs, pairs = C.c_int(), C.c_int(), C.c_int()
+        check(self.lib.twosd_cut_pass_kind(self.h, C.byref(kind), C.byref(limbs), C.byref(pairs)))
+        return kind.value, limbs.value, pairs.value
+
+    def cut_debug_scores(self, epi, x, n, nv):
+        """The integer pass's fp32 score terms of one cut of epigraph `epi` (n scenarios, nv
+        vertices) at x: (t[n, nvc], vmap[nvc]) over the compacted vertices (twosd_cut_debug_scores)."""
+        x = np.ascontiguousarray(x, dtype=np.float64)
+        out = np.zeros(n * nv, dtype=np.float32)
+        vmap = np.zeros(nv, dtype=np.int32)
+        nvc = C.c_int()
+        check(self.lib.twosd_cut_debug_scores(self.h, int(epi), ptr(x), ptr(out), out.size, C.byref(nvc), ptr(vmap)))
+        return out[:n * nvc.value].reshape(n, nvc.value).copy(), vmap[:nvc.value].copy()
+
     def training_cap(self, pivots_sum, scenarios) -> int:
         """The refresh's training pivot cap for a last large batch of `scenarios` solves with
         `pivots_sum` pivots (twosd_training_cap: the native rule, this context's setting)."""

@@ -28,7 +28,7 @@ from collections import defaultdict
 
 import numpy as np
 
-KERNELS = ["lp_hyper_kernel", "pool_refine_kernel", "pool_select_kernel", "cut_argmax3_kernel", "cut_argmax2_kernel",
+KERNELS = ["lp_hyper_kernel", "pool_refine_kernel", "pool_select_kernel", "cut_argmax4_kernel", "cut_argmax3_kernel", "cut_argmax2_kernel",
            "cut_fixup_kernel", "pg_ftran_kernel", "pg_fill_kernel"]
 
 
