@@ -51,6 +51,7 @@
 #include <algorithm>
 #include <cstdlib>
 #include <cstring>
+#include <utility>
 #include <vector>
 #include "twosd_ctx.h"
 #include "cut_i8.h"
@@ -461,18 +462,8 @@ __device__ __forceinline__ int lds2(int kk, int vv) { return kk * kLdsRow2 + (vv
 
 // The value of a decided row in fp64, the same bits in every pass, split and kernel: base[I] + t,
 // t = (c_0 + c_1) + (c_2 + c_3), c_g the fma chain over e = g, g + 4, g + 8, ... < k of
-// (PK[I,e] coef_e) dv_e from 0.  dec_lane_chain is lane (g, .)'s c_g from its register deltas
-// d[kb] (e = 4 kb + g); dec_combine the xor-16 / xor-32 sum that forms t on every lane of the column.
-template <int KB, typename D>
-__device__ __forceinline__ double dec_lane_chain(const CutParams &P, const double *pk, const D (&d)[KB], int g) {
-    double c = 0.0;
-#pragma unroll
-    for (int kb = 0; kb < KB; ++kb) {
-        const int e = 4 * kb + g;
-        if (e < P.k) c = fma(pk[e] * P.coef[e], (double)d[kb], c);
-    }
-    return c;
-}
+// (PK[I,e] coef_e) dv_e from 0.  cut_tile_end's pick_terms forms lane (g, .)'s c_g from its deltas of
+// k-block kb (e = 4 kb + g); dec_combine the xor-16 / xor-32 sum that forms t on every lane of the column.
 __device__ __forceinline__ double dec_combine(double c) {
     c += __shfl_xor(c, 16);
     return c + __shfl_xor(c, 32);
@@ -503,6 +494,140 @@ __device__ __forceinline__ void combine_ex(RowEx &rb, double rel, double band, i
     pack = pk;
 }
 
+// ---- The steps the MFMA passes (cut_argmax2 / 3 / 4_kernel) share.  A pass keeps its operand load
+// and quantisation, its LDS, `stage`, the chunk product and where the candidate steps run relative
+// to the MFMAs.  These kernels sit on their register caps, and the compiler's allocation follows how
+// the source is cut: what is a function below is what left every instantiation's occupancy, LDS and
+// chunk-loop scratch traffic as they were (profiles/r11).
+
+// One work unit of the persistent grid as a wave sees it, for cut_tile_end: a whole scenario tile or
+// vertex range `range` of a tail tile; the wave's scenarios are s0 + j (row 0) and s0 + 16 + j
+// (row 1); lane (g, j)'s candidate logs of the two are lbase[log0 ...] and lbase[log0 + lstep ...].
+struct CutUnit {
+    bool tail;
+    int range, s0;
+    int *lbase;
+    unsigned log0, lstep;
+};
+
+__device__ __forceinline__ int cut_num_units(const CutParams &P) {
+    const int ntiles = (P.N + kCutTile2 - 1) / kCutTile2;
+    return P.full_units + (ntiles - P.full_units) * P.tail_S;
+}
+
+__device__ __forceinline__ RowEx row_ex_init() {
+    RowEx b;
+    b.M = -INFINITY; b.thr = -INFINITY; b.I = -1; b.n = 0; b.f = 0; b.thr32 = -INFINITY;
+    return b;
+}
+
+// The fp64 delta of k-block kb (element e = 4 kb + g < k) of a finished tile's scenario, from one of
+// two sources: the fp64 pass's delta registers, or (an int: the scenario) the deltas read again.
+template <int KB>
+__device__ __forceinline__ double tile_delta(const CutParams &, const double (&a)[KB], int kb, int) { return a[kb < KB ? kb : KB - 1]; }
+template <int KB>
+__device__ __forceinline__ double tile_delta(const CutParams &P, int sx, int, int e) { return sx < P.N ? P.dv[(size_t)sx * P.k + e] : 0.0; }
+
+// The end of a unit: the 4 lanes of each row combined; the held first log entries stored for the
+// rows the fixup reads (every tail row: the merge decides); the picks translated to vertex indices
+// (the logs keep vmap positions: the fixup translates them).  A tail range leaves its result in
+// tp_* for cut_tail_merge_kernel: the log lengths of the range's band, since the merge decides with
+// the band of the row's maximum over all ranges (a range below it contributes nothing).  A whole
+// tile writes arg / val / flag -- a decided row's value is the pick's fp64 value (pick_terms), a
+// flagged row keeps the pass's maximum and the fixup writes its restated value -- and adds p * val
+// and the vertex histogram with its scenarios in order (lane 0 reads them from lanes 0-15).
+// d0 / d1: the two rows' delta sources (tile_delta); the arithmetic and its order are the same for both.
+template <int KB, bool HOLD, typename Src>
+__device__ __forceinline__ void cut_tile_end(const CutParams &P, const CutUnit &u, RowEx &rb0, RowEx &rb1, const Src &d0, const Src &d1,
+                                             double rel, double band, int lane, double &pv_sum, double (&Sacc)[2]) {
+    extern __shared__ unsigned long long hl[];   // the block's LDS histogram (P.hist_lds)
+    const int g = lane >> 4, j = lane & 15;
+    int pk0, pk1, nt0, nt1;
+    combine_ex(rb0, rel, band, g, pk0, nt0);
+    combine_ex(rb1, rel, band, g, pk1, nt1);
+    if (HOLD && rb0.n > 0 && (u.tail || nt0 >= 2)) u.lbase[u.log0] = rb0.f;
+    if (HOLD && rb1.n > 0 && (u.tail || nt1 >= 2)) u.lbase[u.log0 + u.lstep] = rb1.f;
+    rb0.I = rb0.I >= 0 ? P.vmap[rb0.I] : -1;
+    rb1.I = rb1.I >= 0 ? P.vmap[rb1.I] : -1;
+    const int sa = u.s0 + j, sb = u.s0 + 16 + j;
+    if (u.tail) {
+        if (g == 0) {
+            const int t0 = P.full_units * kCutTile2;
+            if (sa < P.N) {
+                const size_t o = (size_t)(sa - t0) * P.tail_S + u.range;
+                P.tp_m[o] = rb0.M; P.tp_i[o] = rb0.I; P.tp_f[o] = pk0;
+            }
+            if (sb < P.N) {
+                const size_t o = (size_t)(sb - t0) * P.tail_S + u.range;
+                P.tp_m[o] = rb1.M; P.tp_i[o] = rb1.I; P.tp_f[o] = pk1;
+            }
+        }
+        return;
+    }
+    if (nt0 < 2) pk0 = 0;   // decided
+    if (nt1 < 2) pk1 = 0;
+    const bool ok0 = sa < P.N && !pk0 && rb0.I >= 0, ok1 = sb < P.N && !pk1 && rb1.I >= 0;
+    const double p0 = ok0 ? P.w[sa] * P.inv_total : 0.0, p1 = ok1 ? P.w[sb] * P.inv_total : 0.0;
+    // one scenario and its pick ai (weight pp; ok: decided): the S_e terms p_w PK[a(w), e] dv[w, e] --
+    // lane (g, j) holds scenario j's e = 4 kb + g, the 16 scenarios of a tile are summed by a fixed xor
+    // tree, lane (g, kb mod 16) keeps the sum in Sacc -- and the lane's chain c_g of the decided value
+    // (dec_combine); returns t.  The k-blocks go in groups of 6, their loads in flight together
+    auto pick_terms = [&](const Src &d, bool ok, int ai, double pp) -> double {
+        const double *pk = P.PK + (size_t)(ai >= 0 ? ai : 0) * P.k4;
+        const double pu = ok ? pp : 0.0;
+        constexpr int FG = 6;
+        double cg = 0.0;
+#pragma unroll
+        for (int k0 = 0; k0 < KB; k0 += FG) {
+            double d64[FG], pke[FG];
+#pragma unroll
+            for (int q = 0; q < FG; ++q) {
+                const int e = 4 * (k0 + q) + g;
+                const bool in = k0 + q < KB && e < P.k;
+                d64[q] = in ? tile_delta<KB>(P, d, k0 + q, e) : 0.0;
+                pke[q] = in ? pk[e] : 0.0;
+            }
+#pragma unroll
+            for (int q = 0; q < FG; ++q) {
+                const int kb = k0 + q, e = 4 * kb + g;
+                if (kb >= KB) break;
+                if (e < P.k) cg = fma(pke[q] * P.coef[e], d64[q], cg);
+                double v = (e < P.k) ? pu * pke[q] * d64[q] : 0.0;
+#pragma unroll
+                for (int o = 8; o > 0; o >>= 1) v += __shfl_xor(v, o);
+                if (j == (kb & 15)) {
+                    if (kb < 16) Sacc[0] += v;
+                    else Sacc[1] += v;
+                }
+            }
+        }
+        return dec_combine(cg);
+    };
+    const double tv0 = pick_terms(d0, ok0, rb0.I, p0);
+    const double tv1 = pick_terms(d1, ok1, rb1.I, p1);
+    const double vl0 = ok0 ? P.base[rb0.I] + tv0 : rb0.M, vl1 = ok1 ? P.base[rb1.I] + tv1 : rb1.M;
+    if (g == 0) {
+        if (sa < P.N) { P.arg[sa] = rb0.I; P.val[sa] = vl0; P.flag[sa] = pk0; }
+        if (sb < P.N) { P.arg[sb] = rb1.I; P.val[sb] = vl1; P.flag[sb] = pk1; }
+    }
+#pragma unroll
+    for (int t = 0; t < 2; ++t) {
+#pragma unroll
+        for (int jj = 0; jj < 16; ++jj) {
+            const int ok = __shfl(t == 0 ? (int)ok0 : (int)ok1, jj);
+            const int ai = __shfl(t == 0 ? rb0.I : rb1.I, jj);
+            const double pp = __shfl(t == 0 ? p0 : p1, jj);
+            const double vl = __shfl(t == 0 ? vl0 : vl1, jj);
+            if (lane == 0 && ok) {
+                pv_sum = fma(pp, vl, pv_sum);
+                const unsigned long long hq = (unsigned long long)__double2ull_rn(pp * kFix);
+                if (P.hist_lds) __hip_atomic_fetch_add(&hl[ai], hq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                else atomicAdd(&P.hist[ai], hq);
+            }
+        }
+    }
+}
+
 #ifndef TWOSD_CUT_LB3
 #define TWOSD_CUT_LB3 1                  // 3 blocks per CU for KB <= 22 (168 VGPRs; ssn: 62 -> 76 % of the roofline)
 #endif
@@ -517,16 +642,17 @@ __global__ void __launch_bounds__(256, (TWOSD_CUT_LB3 && KB <= 22) ? 3 : 2) cut_
     if (P.hist_lds)
         for (int v = threadIdx.x; v < P.nv; v += 256) hl[v] = 0ull;
     const int g = lane >> 4, j = lane & 15;
-    const int ntiles = (P.N + kCutTile2 - 1) / kCutTile2;
     const int nchunks = (*P.nvc + kVT2 - 1) / kVT2;   // the argmax's vertices (vmap)
-    const int nunits = P.full_units + (ntiles - P.full_units) * P.tail_S;
+    const int nunits = cut_num_units(P);
     const double band = kHold ? __longlong_as_double((long long)*P.band_bits) : cut_band_scalar(P);
     const double rel = P.tie_rel;
     double pv_sum = 0.0;
     double Sacc[2] = {0.0, 0.0};   // lane (g, j): e = 4 kb + g for kb = j, j + 16
 
     for (int unit = blockIdx.x; unit < nunits; unit += gridDim.x) {
-        // a whole tile (all vertex chunks), or vertex range `range` of a tail tile
+        // a whole tile (all vertex chunks), or vertex range `range` of a tail tile.  (This unit arithmetic
+        // stays written in each pass: as one function next to cut_tile_end it took the fp32 pass from
+        // 0 / 1 / 2 scratch loads per chunk step to 1 / 2 / 3 at KB 12-16 / 22-24 / 32.)
         const bool tail = unit >= P.full_units;
         const int tile = tail ? P.full_units + (unit - P.full_units) / P.tail_S : unit;
         const int range = tail ? (unit - P.full_units) % P.tail_S : 0;
@@ -544,9 +670,7 @@ __global__ void __launch_bounds__(256, (TWOSD_CUT_LB3 && KB <= 22) ? 3 : 2) cut_
             a1[kb] = (sb < P.N && e < P.k) ? P.dv[(size_t)sb * P.k + e] : 0.0;
             if (e == P.k) a0[kb] = a1[kb] = 1.0;   // x the base row of the chunk
         }
-        RowEx rb0, rb1;   // scenario s0 + j / s0 + 16 + j over this lane's vertices v0 + g + 4r (+16)
-        rb0.M = -INFINITY; rb0.thr = -INFINITY; rb0.I = -1; rb0.n = 0; rb0.f = 0; rb0.thr32 = -INFINITY;
-        rb1 = rb0;
+        RowEx rb0 = row_ex_init(), rb1 = rb0;   // scenario s0 + j / s0 + 16 + j over this lane's vertices v0 + g + 4r (+16)
         // this lane's candidate logs of the two scenarios (rows padded to whole tiles)
         // (a wave-uniform base and a 32-bit element offset: one VGPR per lane instead of a pointer pair)
         int *const lbase = tail ? P.tcand : P.cand;
@@ -614,83 +738,11 @@ __global__ void __launch_bounds__(256, (TWOSD_CUT_LB3 && KB <= 22) ? 3 : 2) cut_
             }
             __syncthreads();
         }
-        int pk0, pk1, nt0, nt1;
-        combine_ex(rb0, rel, band, g, pk0, nt0);
-        combine_ex(rb1, rel, band, g, pk1, nt1);
-        // the logs' first entries, for the rows the fixup reads (every tail row: the merge decides)
-        if (kHold && rb0.n > 0 && (tail || nt0 >= 2)) lbase[log0] = rb0.f;
-        if (kHold && rb1.n > 0 && (tail || nt1 >= 2)) lbase[log0 + lstep] = rb1.f;
-        // the picks as vertex indices (the logs keep vmap positions: the fixup translates them)
-        rb0.I = rb0.I >= 0 ? P.vmap[rb0.I] : -1;
-        rb1.I = rb1.I >= 0 ? P.vmap[rb1.I] : -1;
-        const int sa = s0 + j, sb = s0 + 16 + j;
-        if (tail) {   // this vertex range's result; cut_tail_merge_kernel decides and sums
-            if (g == 0) {
-                const int t0 = P.full_units * kCutTile2;
-                // the log lengths of the range's band: the merge decides with the band of the row's
-                // maximum over all ranges (a range below it contributes nothing)
-                if (sa < P.N) {
-                    const size_t o = (size_t)(sa - t0) * P.tail_S + range;
-                    P.tp_m[o] = rb0.M; P.tp_i[o] = rb0.I; P.tp_f[o] = pk0;
-                }
-                if (sb < P.N) {
-                    const size_t o = (size_t)(sb - t0) * P.tail_S + range;
-                    P.tp_m[o] = rb1.M; P.tp_i[o] = rb1.I; P.tp_f[o] = pk1;
-                }
-            }
-            continue;
-        }
-        if (nt0 < 2) pk0 = 0;   // decided
-        if (nt1 < 2) pk1 = 0;
-        const bool ok0 = sa < P.N && !pk0 && rb0.I >= 0, ok1 = sb < P.N && !pk1 && rb1.I >= 0;
-        const double p0 = ok0 ? P.w[sa] * P.inv_total : 0.0, p1 = ok1 ? P.w[sb] * P.inv_total : 0.0;
-        // decided rows: the pick's fp64 value (dec_lane_chain; flagged rows keep the pass's maximum,
-        // the fixup writes their restated value)
-        const double tv0 = dec_combine(dec_lane_chain<KB>(P, P.PK + (size_t)(rb0.I >= 0 ? rb0.I : 0) * P.k4, a0, g));
-        const double tv1 = dec_combine(dec_lane_chain<KB>(P, P.PK + (size_t)(rb1.I >= 0 ? rb1.I : 0) * P.k4, a1, g));
-        const double vl0 = ok0 ? P.base[rb0.I] + tv0 : rb0.M, vl1 = ok1 ? P.base[rb1.I] + tv1 : rb1.M;
-        if (g == 0) {
-            if (sa < P.N) { P.arg[sa] = rb0.I; P.val[sa] = vl0; P.flag[sa] = pk0; }
-            if (sb < P.N) { P.arg[sb] = rb1.I; P.val[sb] = vl1; P.flag[sb] = pk1; }
-        }
-        // sum p * val and the vertex histogram, scenarios in order (lane 0 reads them from lanes 0-15)
-#pragma unroll
-        for (int t = 0; t < 2; ++t) {
-#pragma unroll
-            for (int jj = 0; jj < 16; ++jj) {
-                const int ok = __shfl(t == 0 ? (int)ok0 : (int)ok1, jj);
-                const int ai = __shfl(t == 0 ? rb0.I : rb1.I, jj);
-                const double pp = __shfl(t == 0 ? p0 : p1, jj);
-                const double vl = __shfl(t == 0 ? vl0 : vl1, jj);
-                if (lane == 0 && ok) {
-                    pv_sum = fma(pp, vl, pv_sum);
-                    const unsigned long long hq = (unsigned long long)__double2ull_rn(pp * kFix);
-                    if (P.hist_lds) __hip_atomic_fetch_add(&hl[ai], hq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-                    else atomicAdd(&P.hist[ai], hq);
-                }
-            }
-        }
-        // S_e = sum_w p_w PK[a(w), e] dv[w, e] from the delta registers: lane (g, j) holds
-        // scenario j's e = 4 kb + g and its pick; the 16 scenarios of a tile are summed by a
-        // fixed xor tree, lane (g, kb mod 16) keeps the sum
-        auto s_pass = [&](const double (&a)[KB], bool ok, int ai, double pp) {
-            const double *pk = P.PK + (size_t)(ok ? ai : 0) * P.k4;
-            const double pu = ok ? pp : 0.0;
-#pragma unroll
-            for (int kb = 0; kb < KB; ++kb) {
-                const int e = 4 * kb + g;
-                double v = (e < P.k) ? pu * pk[e] * a[kb] : 0.0;
-#pragma unroll
-                for (int o = 8; o > 0; o >>= 1) v += __shfl_xor(v, o);
-                if (j == (kb & 15)) {
-                    if (kb < 16) Sacc[0] += v;
-                    else Sacc[1] += v;
-                }
-            }
-        };
-        s_pass(a0, ok0, rb0.I, p0);
-        s_pass(a1, ok1, rb1.I, p1);
+        const CutUnit un = {tail, range, s0, lbase, log0, lstep};
+        cut_tile_end<KB, kHold>(P, un, rb0, rb1, a0, a1, rel, band, lane, pv_sum, Sacc);   // from the delta registers
     }
+    // (the block end stays written in each pass: as one function it raised this pass's scratch from 32 to
+    // 172 bytes per lane at KB 22, from 0 to 24-268 at KB 24-32, and the fp32 pass's from 72 to 628 at KB 30)
     if (P.hist_lds) {
         __syncthreads();
         for (int v = threadIdx.x; v < P.nv; v += 256) P.hist_part[(size_t)blockIdx.x * P.nv + v] = hl[v];
@@ -746,10 +798,9 @@ __global__ void __launch_bounds__(256, TWOSD_CUT3_BPC) cut_argmax3_kernel(CutPar
     if (P.hist_lds)
         for (int v = threadIdx.x; v < P.nv; v += 256) hl[v] = 0ull;
     const int g = lane >> 4, j = lane & 15;
-    const int ntiles = (P.N + kCutTile2 - 1) / kCutTile2;
     const int nvc = *P.nvc;
     const int nchunks = (nvc + kVT2 - 1) / kVT2;
-    const int nunits = P.full_units + (ntiles - P.full_units) * P.tail_S;
+    const int nunits = cut_num_units(P);
     const double band = cut_band_scalar(P);
     const double rel = P.tie_rel;
     double pv_sum = 0.0;
@@ -773,9 +824,7 @@ __global__ void __launch_bounds__(256, TWOSD_CUT3_BPC) cut_argmax3_kernel(CutPar
             a0[kb] = (sa < P.N && e < P.k) ? (float)P.dv[(size_t)sa * P.k + e] : 0.0f;
             a1[kb] = (sb < P.N && e < P.k) ? (float)P.dv[(size_t)sb * P.k + e] : 0.0f;
         }
-        RowEx rb0, rb1;
-        rb0.M = -INFINITY; rb0.thr = -INFINITY; rb0.I = -1; rb0.n = 0; rb0.f = 0; rb0.thr32 = -INFINITY;
-        rb1 = rb0;
+        RowEx rb0 = row_ex_init(), rb1 = rb0;
         int *const lbase = tail ? P.tcand : P.cand;
         const unsigned log0 = tail ? (unsigned)(((((size_t)(s0 + j - P.full_units * kCutTile2)) * P.tail_S + range) * 4 + g) * kCandC)
                                       : (unsigned)((((size_t)(s0 + j)) * 4 + g) * kCandC);
@@ -886,92 +935,8 @@ __global__ void __launch_bounds__(256, TWOSD_CUT3_BPC) cut_argmax3_kernel(CutPar
             __syncthreads();
         }
         if (c_hi > c_lo) finish(p00, p01, p10, p11, bp, pv0, bsp);
-        int pk0, pk1, nt0, nt1;
-        combine_ex(rb0, rel, band, g, pk0, nt0);
-        combine_ex(rb1, rel, band, g, pk1, nt1);
-        if (kHold3 && rb0.n > 0 && (tail || nt0 >= 2)) lbase[log0] = rb0.f;
-        if (kHold3 && rb1.n > 0 && (tail || nt1 >= 2)) lbase[log0 + lstep] = rb1.f;
-        rb0.I = rb0.I >= 0 ? P.vmap[rb0.I] : -1;
-        rb1.I = rb1.I >= 0 ? P.vmap[rb1.I] : -1;
-        if (tail) {
-            if (g == 0) {
-                const int t0 = P.full_units * kCutTile2;
-                if (sa < P.N) {
-                    const size_t o = (size_t)(sa - t0) * P.tail_S + range;
-                    P.tp_m[o] = rb0.M; P.tp_i[o] = rb0.I; P.tp_f[o] = pk0;
-                }
-                if (sb < P.N) {
-                    const size_t o = (size_t)(sb - t0) * P.tail_S + range;
-                    P.tp_m[o] = rb1.M; P.tp_i[o] = rb1.I; P.tp_f[o] = pk1;
-                }
-            }
-            continue;
-        }
-        if (nt0 < 2) pk0 = 0;
-        if (nt1 < 2) pk1 = 0;
-        const bool ok0 = sa < P.N && !pk0 && rb0.I >= 0, ok1 = sb < P.N && !pk1 && rb1.I >= 0;
-        const double p0 = ok0 ? P.w[sa] * P.inv_total : 0.0, p1 = ok1 ? P.w[sb] * P.inv_total : 0.0;
-        // per scenario of the tile: its fp64 deltas again (this lane's e = 4 kb + g), the S_e terms
-        // of its pick (the xor tree of v2's s_pass) and its value base[a] + sum_e PK[a,e] coef_e dv_e
-        // in fp64 (the lanes' partial sums combined over g in a fixed order)
-        auto fin = [&](int sx, bool ok, int ai, double pp) -> double {
-            const double *pk = P.PK + (size_t)(ai >= 0 ? ai : 0) * P.k4;
-            const double pu = ok ? pp : 0.0;
-            // k-blocks in groups of 6 (their loads in flight together): the S_e terms (v2's xor
-            // tree) and dec_lane_chain's chain c_g, in the same order and arithmetic
-            constexpr int FG = 6;
-            double cg = 0.0;
-#pragma unroll
-            for (int k0 = 0; k0 < KB; k0 += FG) {
-                double d64[FG], pke[FG];
-#pragma unroll
-                for (int u = 0; u < FG; ++u) {
-                    const int e = 4 * (k0 + u) + g;
-                    const bool in = k0 + u < KB && e < P.k;
-                    d64[u] = (in && sx < P.N) ? P.dv[(size_t)sx * P.k + e] : 0.0;
-                    pke[u] = in ? pk[e] : 0.0;
-                }
-#pragma unroll
-                for (int u = 0; u < FG; ++u) {
-                    const int kb = k0 + u, e = 4 * kb + g;
-                    if (kb >= KB) break;
-                    if (e < P.k) cg = fma(pke[u] * P.coef[e], d64[u], cg);
-                    double v = (e < P.k) ? pu * pke[u] * d64[u] : 0.0;
-#pragma unroll
-                    for (int o = 8; o > 0; o >>= 1) v += __shfl_xor(v, o);
-                    if (j == (kb & 15)) {
-                        if (kb < 16) Sacc[0] += v;
-                        else Sacc[1] += v;
-                    }
-                }
-            }
-            return dec_combine(cg);
-        };
-        const double tv0 = fin(sa, ok0, rb0.I, p0);
-        const double tv1 = fin(sb, ok1, rb1.I, p1);
-        // decided rows: the fp64 value of the pick; flagged rows keep the MFMA maximum (the fixup
-        // re-scores them and writes the restated value)
-        const double vl0 = ok0 ? P.base[rb0.I] + tv0 : rb0.M, vl1 = ok1 ? P.base[rb1.I] + tv1 : rb1.M;
-        if (g == 0) {
-            if (sa < P.N) { P.arg[sa] = rb0.I; P.val[sa] = vl0; P.flag[sa] = pk0; }
-            if (sb < P.N) { P.arg[sb] = rb1.I; P.val[sb] = vl1; P.flag[sb] = pk1; }
-        }
-#pragma unroll
-        for (int t = 0; t < 2; ++t) {
-#pragma unroll
-            for (int jj = 0; jj < 16; ++jj) {
-                const int ok = __shfl(t == 0 ? (int)ok0 : (int)ok1, jj);
-                const int ai = __shfl(t == 0 ? rb0.I : rb1.I, jj);
-                const double pp = __shfl(t == 0 ? p0 : p1, jj);
-                const double vl = __shfl(t == 0 ? vl0 : vl1, jj);
-                if (lane == 0 && ok) {
-                    pv_sum = fma(pp, vl, pv_sum);
-                    const unsigned long long hq = (unsigned long long)__double2ull_rn(pp * kFix);
-                    if (P.hist_lds) __hip_atomic_fetch_add(&hl[ai], hq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-                    else atomicAdd(&P.hist[ai], hq);
-                }
-            }
-        }
+        const CutUnit un = {tail, range, s0, lbase, log0, lstep};
+        cut_tile_end<KB, kHold3>(P, un, rb0, rb1, sa, sb, rel, band, lane, pv_sum, Sacc);   // the fp64 deltas read again
     }
     if (P.hist_lds) {
         __syncthreads();
@@ -1000,7 +965,8 @@ __global__ void __launch_bounds__(256, TWOSD_CUT3_BPC) cut_argmax3_kernel(CutPar
 // accumulator per level l1 + l2, and ci8::combine folds the levels into the fp32 term t.  The
 // score is base[v] + t in fp64 as in v3, within the integer band of the restated score
 // (cut_vbase_kernel, band_bits[5]); everything after t -- prefilter, exact steps, logs, tail
-// ranges, the fp64 re-read at the tile end -- is v3's.  The i32 C/D layout is the f32 one: register
+// ranges, the fp64 re-read at the tile end -- is v3's (a second copy of it: see the notes in the
+// kernel).  The i32 C/D layout is the f32 one: register
 // r of a tile is vertex row 4g + r, scenario column j.  An integer sum does not depend on the order
 // of its terms, so the result is the same bits on any hardware and in the numpy model.
 typedef int i4 __attribute__((ext_vector_type(4)));
@@ -1136,10 +1102,9 @@ __global__ void __launch_bounds__(256, TWOSD_CUT4_BPC) cut_argmax4_kernel(CutPar
     if (P.hist_lds)
         for (int v = threadIdx.x; v < P.nv; v += 256) hl[v] = 0ull;
     const int g = lane >> 4, j = lane & 15;
-    const int ntiles = (P.N + kCutTile2 - 1) / kCutTile2;
     const int nvc = *P.nvc;
     const int nchunks = (nvc + kVT2 - 1) / kVT2;
-    const int nunits = P.full_units + (ntiles - P.full_units) * P.tail_S;
+    const int nunits = cut_num_units(P);
     const double band = cut_band_scalar(P);
     const double rel = P.tie_rel;
     double pv_sum = 0.0;
@@ -1156,9 +1121,7 @@ __global__ void __launch_bounds__(256, TWOSD_CUT4_BPC) cut_argmax4_kernel(CutPar
         i4 d0[KS][ci8::kL], d1[KS][ci8::kL];
         i8_quant_deltas<KS>(P, sa, g, d0);
         i8_quant_deltas<KS>(P, sb, g, d1);
-        RowEx rb0, rb1;
-        rb0.M = -INFINITY; rb0.thr = -INFINITY; rb0.I = -1; rb0.n = 0; rb0.f = 0; rb0.thr32 = -INFINITY;
-        rb1 = rb0;
+        RowEx rb0 = row_ex_init(), rb1 = rb0;
         int *const lbase = tail ? P.tcand : P.cand;
         const unsigned log0 = tail ? (unsigned)(((((size_t)(s0 + j - P.full_units * kCutTile2)) * P.tail_S + range) * 4 + g) * kCandC)
                                       : (unsigned)((((size_t)(s0 + j)) * 4 + g) * kCandC);
@@ -1183,7 +1146,9 @@ __global__ void __launch_bounds__(256, TWOSD_CUT4_BPC) cut_argmax4_kernel(CutPar
 #pragma unroll
             for (int r = 0; r < 4; ++r) { bq[r] = lo[r]; bq[4 + r] = hi[r]; sq[r] = slo[r]; sq[4 + r] = shi[r]; }
         };
-        // v3's finish: prefilter in fp32, exact steps in vertex order for the lanes past it
+        // v3's finish, a second copy: prefilter in fp32, exact steps in vertex order for the lanes past it.  (As
+        // one function -- RowEx &, the four tiles, the base slot -- the chunk loop went from 0 scratch loads
+        // / 0 stores to 6 / 4 in the fp32 pass at KB 8 and from 7 / 1 to 8 / 4 here at KB 30.)
         auto finish = [&](const f4 &q00, const f4 &q01, const f4 &q10, const f4 &q11, const float (&bb)[8], int vb, int bslot) {
             unsigned m0 = 0, m1 = 0;
 #pragma unroll
@@ -1239,6 +1204,9 @@ __global__ void __launch_bounds__(256, TWOSD_CUT4_BPC) cut_argmax4_kernel(CutPar
             __syncthreads();
         }
         if (c_hi > c_lo) finish(p[0], p[1], p[2], p[3], bp, pv0, bsp);
+        // cut_tile_end<KB, true> (int sources), a second copy: calling it instead -- whole, in halves, or
+        // only its pick_terms -- took this chunk loop from 6 scratch accesses per step to 8-15 at KB 24 and
+        // 32, and from 1 to 2 at KB 8; only KB 22 and 30 can be timed (ssn, storm)
         int pk0, pk1, nt0, nt1;
         combine_ex(rb0, rel, band, g, pk0, nt0);
         combine_ex(rb1, rel, band, g, pk1, nt1);
@@ -1264,7 +1232,7 @@ __global__ void __launch_bounds__(256, TWOSD_CUT4_BPC) cut_argmax4_kernel(CutPar
         if (nt1 < 2) pk1 = 0;
         const bool ok0 = sa < P.N && !pk0 && rb0.I >= 0, ok1 = sb < P.N && !pk1 && rb1.I >= 0;
         const double p0 = ok0 ? P.w[sa] * P.inv_total : 0.0, p1 = ok1 ? P.w[sb] * P.inv_total : 0.0;
-        // v3's tile end: the fp64 deltas again for the S_e terms and the decided rows' values
+        // the fp64 deltas again for the S_e terms and the decided rows' values
         auto fin = [&](int sx, bool ok, int ai, double pp) -> double {
             const double *pk = P.PK + (size_t)(ai >= 0 ? ai : 0) * P.k4;
             const double pu = ok ? pp : 0.0;
@@ -1425,7 +1393,7 @@ __global__ void __launch_bounds__(256) cut_tail_merge_kernel(CutParams P, int sl
             const int e = lane + 64 * t;
             if (e < P.k) Sacc[t] = fma(p * P.PK[(size_t)I * P.k4 + e], P.dv[(size_t)s * P.k + e], Sacc[t]);
         }
-        // lane g < 4: the chain c_g of dec_lane_chain, then (c_0 + c_1) + (c_2 + c_3) as dec_combine
+        // lane g < 4: the chain c_g of cut_tile_end's pick_terms, then (c_0 + c_1) + (c_2 + c_3) as dec_combine
         double cg = 0.0;
         if (lane < 4) {
             const double *pk = P.PK + (size_t)I * P.k4, *dr = P.dv + (size_t)s * P.k;
@@ -2010,108 +1978,41 @@ static int clear_cut_stats(twosd_ctx *c) {
     return TWOSD_OK;
 }
 
+// the k-block counts the three argmax kernels are instantiated for, ascending (22: ssn, k = 86, + base row)
+constexpr int kCutKBs[] = {1, 2, 4, 6, 8, 12, 16, 22, 24, 30, 32};
+constexpr int kNumKB = sizeof(kCutKBs) / sizeof(kCutKBs[0]);
+static_assert(4 * kCutKBs[kNumKB - 1] == 128, "the envelope: at most 128 chunk rows (k <= 127 plus the base row)");
+
 static int kb_for(int k4) {
-    static const int KBs[] = {1, 2, 4, 6, 8, 12, 16, 22, 24, 30, 32};   // 22: ssn (k = 86, + base row)
-    for (int kb : KBs)
+    for (int kb : kCutKBs)
         if (4 * kb >= k4) return kb;
     return -1;
 }
 
-template <int KB>
-static void launch_argmax_t(const CutParams &P, int nblocks, hipStream_t s) {
-    hipLaunchKernelGGL(cut_argmax2_kernel<KB>, dim3(nblocks), dim3(256), P.hist_lds ? sizeof(unsigned long long) * P.nv : 0, s, P);
+// the argmax kernel of (pass, KB); pass as band_bits[4] has it: 0 fp64, 1 fp32, 2 integer
+typedef void (*cut_argmax_fn)(CutParams);
+template <size_t... I>
+static cut_argmax_fn argmax_kernel_of(int pass, int KB, std::index_sequence<I...>) {
+    static const cut_argmax_fn tab[3][kNumKB] = {{cut_argmax2_kernel<kCutKBs[I]>...},
+                                                 {cut_argmax3_kernel<kCutKBs[I]>...},
+                                                 {cut_argmax4_kernel<kCutKBs[I]>...}};
+    for (int i = 0; i < kNumKB; ++i)
+        if (kCutKBs[i] == KB) return tab[pass][i];
+    return nullptr;
 }
+static cut_argmax_fn argmax_kernel(int pass, int KB) { return argmax_kernel_of(pass, KB, std::make_index_sequence<kNumKB>{}); }
 
 // resident blocks per CU of one instantiation (registers and LDS): the persistent grid is
 // sized to exactly what is resident, so no block starts after the first ones drain (a grid
 // of 3 blocks per CU at 2 resident ran its last third with half of every CU idle)
-template <int KB>
-static int argmax_occupancy_t(size_t dyn_lds) {
+static int argmax_occupancy(cut_argmax_fn fn, size_t dyn_lds) {
     int nb = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, cut_argmax2_kernel<KB>, 256, dyn_lds) != hipSuccess) nb = 0;
+    if (!fn || hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, fn, 256, dyn_lds) != hipSuccess) nb = 0;
     return nb;
 }
 
-static int argmax_occupancy(int KB, size_t dyn_lds) {
-    switch (KB) {
-        case 1: return argmax_occupancy_t<1>(dyn_lds);
-        case 2: return argmax_occupancy_t<2>(dyn_lds);
-        case 4: return argmax_occupancy_t<4>(dyn_lds);
-        case 6: return argmax_occupancy_t<6>(dyn_lds);
-        case 8: return argmax_occupancy_t<8>(dyn_lds);
-        case 12: return argmax_occupancy_t<12>(dyn_lds);
-        case 16: return argmax_occupancy_t<16>(dyn_lds);
-        case 22: return argmax_occupancy_t<22>(dyn_lds);
-        case 24: return argmax_occupancy_t<24>(dyn_lds);
-        case 30: return argmax_occupancy_t<30>(dyn_lds);
-        case 32: return argmax_occupancy_t<32>(dyn_lds);
-    }
-    return 0;
-}
-
-template <int KB>
-static void launch_argmax3_t(const CutParams &P, int nblocks, hipStream_t s) {
-    hipLaunchKernelGGL(cut_argmax3_kernel<KB>, dim3(nblocks), dim3(256), P.hist_lds ? sizeof(unsigned long long) * P.nv : 0, s, P);
-}
-template <int KB>
-static int argmax3_occupancy_t(size_t dyn_lds) {
-    int nb = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, cut_argmax3_kernel<KB>, 256, dyn_lds) != hipSuccess) nb = 0;
-    return nb;
-}
-#define CUT_KB_SWITCH(FN, ...)                          \
-    switch (KB) {                                       \
-        case 1: return FN<1>(__VA_ARGS__);              \
-        case 2: return FN<2>(__VA_ARGS__);              \
-        case 4: return FN<4>(__VA_ARGS__);              \
-        case 6: return FN<6>(__VA_ARGS__);              \
-        case 8: return FN<8>(__VA_ARGS__);              \
-        case 12: return FN<12>(__VA_ARGS__);            \
-        case 16: return FN<16>(__VA_ARGS__);            \
-        case 22: return FN<22>(__VA_ARGS__);            \
-        case 24: return FN<24>(__VA_ARGS__);            \
-        case 30: return FN<30>(__VA_ARGS__);            \
-        case 32: return FN<32>(__VA_ARGS__);            \
-    }
-static int argmax3_occupancy(int KB, size_t dyn_lds) {
-    CUT_KB_SWITCH(argmax3_occupancy_t, dyn_lds)
-    return 0;
-}
-static void launch_argmax3(int KB, const CutParams &P, int nblocks, hipStream_t s) {
-    CUT_KB_SWITCH(launch_argmax3_t, P, nblocks, s)
-}
-template <int KB>
-static void launch_argmax4_t(const CutParams &P, int nblocks, hipStream_t s) {
-    hipLaunchKernelGGL(cut_argmax4_kernel<KB>, dim3(nblocks), dim3(256), P.hist_lds ? sizeof(unsigned long long) * P.nv : 0, s, P);
-}
-template <int KB>
-static int argmax4_occupancy_t(size_t dyn_lds) {
-    int nb = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, cut_argmax4_kernel<KB>, 256, dyn_lds) != hipSuccess) nb = 0;
-    return nb;
-}
-static int argmax4_occupancy(int KB, size_t dyn_lds) {
-    CUT_KB_SWITCH(argmax4_occupancy_t, dyn_lds)
-    return 0;
-}
-static void launch_argmax4(int KB, const CutParams &P, int nblocks, hipStream_t s) {
-    CUT_KB_SWITCH(launch_argmax4_t, P, nblocks, s)
-}
-
-static void launch_argmax(int KB, const CutParams &P, int nblocks, hipStream_t s) {
-    switch (KB) {
-        case 1: launch_argmax_t<1>(P, nblocks, s); break;
-        case 2: launch_argmax_t<2>(P, nblocks, s); break;
-        case 4: launch_argmax_t<4>(P, nblocks, s); break;
-        case 6: launch_argmax_t<6>(P, nblocks, s); break;
-        case 8: launch_argmax_t<8>(P, nblocks, s); break;
-        case 12: launch_argmax_t<12>(P, nblocks, s); break;
-        case 16: launch_argmax_t<16>(P, nblocks, s); break;
-        case 22: launch_argmax_t<22>(P, nblocks, s); break;
-        case 24: launch_argmax_t<24>(P, nblocks, s); break;
-        case 30: launch_argmax_t<30>(P, nblocks, s); break;
-        case 32: launch_argmax_t<32>(P, nblocks, s); break;
-    }
+static void launch_argmax(cut_argmax_fn fn, const CutParams &P, int nblocks, hipStream_t s) {
+    hipLaunchKernelGGL(fn, dim3(nblocks), dim3(256), P.hist_lds ? sizeof(unsigned long long) * P.nv : 0, s, P);
 }
 
 // bring PK/PKT up to date with the vertex set
@@ -2222,9 +2123,8 @@ static int cut_partial_impl(twosd_ctx *c, int epi, const double *x, double tie_r
     static const int bpc_env = getenv("TWOSD_CUT_BPC") ? atoi(getenv("TWOSD_CUT_BPC")) : 0;
     int bpc = bpc_env;
     if (bpc <= 0)
-        bpc = wanti8   ? argmax4_occupancy(KB32, sizeof(unsigned long long) * kHistLds)
-              : want32 ? argmax3_occupancy(KB32, sizeof(unsigned long long) * kHistLds)
-                       : argmax_occupancy(KB, sizeof(unsigned long long) * kHistLds);
+        bpc = argmax_occupancy(wanti8 ? argmax_kernel(2, KB32) : want32 ? argmax_kernel(1, KB32) : argmax_kernel(0, KB),
+                               sizeof(unsigned long long) * kHistLds);
     if (bpc <= 0) bpc = 2;
     const int nchunks = (nv + kVT2 - 1) / kVT2;
     // The persistent grid runs whole tiles round after round; the tiles past the last full
@@ -2373,9 +2273,9 @@ static int cut_partial_impl(twosd_ctx *c, int epi, const double *x, double tie_r
     P.arg = w->arg; P.val = w->val; P.flag = w->flag; P.hist = d_hist; P.partial = w->partial;
     P.full_units = full; P.tail_S = S; P.fx_gs = fx_gs;
     P.tp_m = w->tp_m; P.tp_i = w->tp_i; P.tp_f = w->tp_f;
-    if (wanti8) launch_argmax4(KB32, P, nblocks, c->stream);   // each of the three returns at once unless its pass runs
-    if (want32) launch_argmax3(KB32, P, nblocks, c->stream);
-    launch_argmax(KB, P, nblocks, c->stream);
+    if (wanti8) launch_argmax(argmax_kernel(2, KB32), P, nblocks, c->stream);   // each of the three returns at once unless its pass runs
+    if (want32) launch_argmax(argmax_kernel(1, KB32), P, nblocks, c->stream);
+    launch_argmax(argmax_kernel(0, KB), P, nblocks, c->stream);
     if (P.hist_lds)
         hipLaunchKernelGGL(cut_hist_reduce_kernel, dim3((nv + 255) / 256), dim3(256), 0, c->stream, nblocks, nv, w->hist_part,
                            d_hist);
@@ -2509,16 +2409,23 @@ extern "C" int twosd_cut_stats(twosd_ctx *c, int64_t *out) {
     return TWOSD_OK;
 }
 
+// the last cut's band_bits (zeros before the first cut): [3] the active band, [4] the pass
+static int read_band_bits(twosd_ctx *c, unsigned long long (&h)[8]) {
+    memset(h, 0, sizeof(h));
+    CutWs *w = c->cut_ws.get();
+    if (!w || !w->band_bits) return TWOSD_OK;
+    HIPCHK(hipSetDevice(c->device));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    HIPCHK(hipMemcpy(h, w->band_bits, sizeof(h), hipMemcpyDeviceToHost));
+    return TWOSD_OK;
+}
+
 extern "C" int twosd_cut_pass(twosd_ctx *c, int *fp32, double *band) {
     if (!c || !fp32) return fail(TWOSD_E_ARG, "cut_pass: NULL");
     *fp32 = 0;
     if (band) *band = 0.0;
-    CutWs *w = c->cut_ws.get();
-    if (!w || !w->band_bits) return TWOSD_OK;
-    unsigned long long h[8] = {};
-    HIPCHK(hipSetDevice(c->device));
-    HIPCHK(hipStreamSynchronize(c->stream));
-    HIPCHK(hipMemcpy(h, w->band_bits, sizeof(h), hipMemcpyDeviceToHost));
+    unsigned long long h[8];
+    if (int rc = read_band_bits(c, h)) return rc;
     *fp32 = h[4] != 0;   // a reduced-precision pass ran: fp32 or integer (twosd_cut_pass_kind tells which)
     if (band) memcpy(band, &h[3], sizeof(double));
     return TWOSD_OK;
@@ -2529,12 +2436,8 @@ extern "C" int twosd_cut_pass_kind(twosd_ctx *c, int *kind, int *limbs, int *pai
     *kind = 0;
     if (limbs) *limbs = ci8::kL;
     if (pairs) *pairs = ci8::kPairs;
-    CutWs *w = c->cut_ws.get();
-    if (!w || !w->band_bits) return TWOSD_OK;
-    unsigned long long h[8] = {};
-    HIPCHK(hipSetDevice(c->device));
-    HIPCHK(hipStreamSynchronize(c->stream));
-    HIPCHK(hipMemcpy(h, w->band_bits, sizeof(h), hipMemcpyDeviceToHost));
+    unsigned long long h[8];
+    if (int rc = read_band_bits(c, h)) return rc;
     *kind = (int)h[4];
     return TWOSD_OK;
 }

@@ -23,6 +23,10 @@ SEED_VALUES, SEED_TRAIN = 1, 2
 X_FAR = np.array([0.9, 0.4, 0.6, 0.1])
 X = [np.array([0.5, 1.0, 0.2, 0.7]), np.array([0.54, 0.94, 0.24, 0.64])]
 PENALTY = 50.0
+# the environment that requests each of the cut's MFMA passes (the pass values of cut_pass_kind):
+# 2 integer limbs, 1 fp32, 0 fp64; the device may still fall back (fp32 range, non-finite deltas)
+PASS_ENV = {2: dict(TWOSD_CUT_F32="1", TWOSD_CUT_I8="1"), 1: dict(TWOSD_CUT_F32="1", TWOSD_CUT_I8="0"),
+            0: dict(TWOSD_CUT_F32="0", TWOSD_CUT_I8="1")}
 
 
 def synth_template(m2, ncols, k, seed, senses="EGL", neg_costs=True, amp=1.0):

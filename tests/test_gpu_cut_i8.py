@@ -29,8 +29,7 @@ class _env:
                 os.environ[k] = v
 
 
-PASS_ENV = {2: dict(TWOSD_CUT_F32="1", TWOSD_CUT_I8="1"), 1: dict(TWOSD_CUT_F32="1", TWOSD_CUT_I8="0"),
-            0: dict(TWOSD_CUT_F32="0", TWOSD_CUT_I8="1")}
+PASS_ENV = SC.PASS_ENV
 
 
 # ---- bit-exact scores ---------------------------------------------------------------------------------
@@ -175,6 +174,38 @@ def test_three_passes_importance_weighted_transship():
     for tie_rel in (0.0, 1e-12):
         a, b, omv, oma = cpu.build_cut(sp.r, sp.T, x, Vm, ctx.rows, vals - sp.r[ctx.rows], w, tie_rel=tie_rel)
         _check_against_oracle(_three_passes(ctx, epi, x, tie_rel), a, b, omv, oma)
+
+
+@pytest.mark.parametrize("name,nsrc", [("ssn", 4096), ("storm", 8192)])
+def test_three_passes_at_the_small_shapes(name, nsrc):
+    """The steps the three passes share (unit arithmetic, tile end, block end) at the smallest shapes
+    where they can go wrong: N in {1, 127, 129, 300} scenarios (the bounds of both scenario rows on
+    either side of a tile) x |V| in {260, 33, 31, 1}.  |V| = 260 is 9 chunks: every tile runs as tail
+    units of S = 2 vertex ranges into the tail logs and the merge, with the global histogram; |V| <= 33
+    runs whole-tile units with the LDS histogram.  ssn is KB = 22: the fp64 pass at 3 blocks per CU
+    without the held log entry, two integer k-steps; storm's fp64 pass runs at 2 blocks per CU with
+    the held entry.  Every pass gives the C oracle's picks and cut under both tie rules."""
+    from oracle import cpu
+    from sqlp_amd import twosd
+    inst, ctx, x, V = _built_at_x(name, nsrc)
+    assert len(V) >= 260, len(V)
+    sp = inst["osp2"]
+    rng = np.random.default_rng(11)
+    epis = {}
+    for N in (1, 127, 129, 300):
+        vals, w = I.sample(name, N, 50 + N), rng.uniform(0.5, 1.5, size=N)
+        epi = twosd.sdEpigraph(ctx, 1.0, 0.0)
+        twosd.add_scenarios(epi, vals, w)
+        epis[N] = (epi, vals, w)
+    for nv in (260, 33, 31, 1):
+        V.truncate(nv)
+        Vm = V.matrix()
+        for N, (epi, vals, w) in epis.items():
+            for tie_rel in (0.0, 1e-12):
+                a, b, omv, oma = cpu.build_cut(sp.r, sp.T, x, Vm, ctx.rows, vals - sp.r[ctx.rows], w, tie_rel=tie_rel)
+                got = _three_passes(ctx, epi, x, tie_rel)
+                _check_against_oracle(got, a, b, omv, oma)
+        print(f"I8 small shapes {name} |V| {nv}: passes run {[got[k][4] for k in (2, 1, 0)]}, twins dropped {got[2][5][3]}")
 
 
 # ---- full units and tail ranges -----------------------------------------------------------------------

@@ -255,17 +255,24 @@ def test_cut_matches_oracle(tid):
     ra = np.tile(S.r, (N, 1))
     ra[:, S.rows] = vals
     worst = 0.0
+    kinds = set()
     for x in SC.X:                                          # where V was built, and elsewhere
         scores = SC.cut_scores(S, Vm, x, vals)
         best = scores.max(1)
         for tie_rel in (0.0, 1e-12):
             a, b, omv, oma = cpu.build_cut(S.r, S.T, x, Vm, S.rows, vals - S.r[S.rows], w, tie_rel=tie_rel, nthreads=4)
             got = {}
-            for f32 in ("1", "0"):
-                with _env("TWOSD_CUT_F32", f32):
+            for kind in (2, 1, 0):                          # the integer, fp32 and fp64 passes requested
+                f32, i8 = SC.PASS_ENV[kind]["TWOSD_CUT_F32"], SC.PASS_ENV[kind]["TWOSD_CUT_I8"]
+                with _env("TWOSD_CUT_F32", f32), _env("TWOSD_CUT_I8", i8):
                     cut, mv, ma = twosd._build_cut(epi, x, tie_rel, want_argmax=True)
                     got[f32] = ctx.cut_pass()
+                    ran = ctx.cut_pass_kind()[0]
                 assert got[f32][0] == int(f32)
+                # the fp64 and fp32 requests run those passes; the integer request runs the integer pass,
+                # or the fp32 one where the integer band is not finite (recorded per template below)
+                assert ran == kind or (kind == 2 and ran == 1), (kind, ran)
+                kinds.add((kind, ran))
                 assert cut.weight_mark == pytest.approx(w.sum(), rel=1e-15)
                 assert (ma == oma).all(), (f32, tie_rel, SC.near_ties(scores), int((ma != oma).sum()))
                 np.testing.assert_allclose(mv, omv, rtol=1e-10, atol=1e-9)
@@ -279,7 +286,8 @@ def test_cut_matches_oracle(tid):
                 assert cut.alpha == pytest.approx(a_ref, rel=1e-9, abs=1e-9)
                 np.testing.assert_allclose(cut.beta, b_ref, rtol=1e-9, atol=1e-9 * (1 + np.abs(b_ref).max()))
             assert got["1"][1] > got["0"][1] > 0.0         # the fp32 band is the wider one
-    print(f"SHAPES cut {tid} (R, C, KB) = {S.dispatch}: |V| {len(Vm)}, worst alpha error {worst:.3e} relative")
+    print(f"SHAPES cut {tid} (R, C, KB) = {S.dispatch}: |V| {len(Vm)}, worst alpha error {worst:.3e} relative, "
+          f"passes run for the integer request {sorted(r for q, r in kinds if q == 2)}")
 
 
 # ---- 5. envelope --------------------------------------------------------------------------------------

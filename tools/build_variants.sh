@@ -6,8 +6,8 @@ set -e
 cd "$(dirname "$0")/../sqlp_amd/csrc"
 SRC=lp_hyper.hip
 if [ "$1" = "-f" ]; then SRC=$2; shift 2; fi
-ALL="api.hip lp_hyper.hip pool_sort.hip sampler.hip dvs_kernel.hip cut_kernel.hip vkey.hip pool_gpu.hip"
-OTHERS="build/host_basis.cpp.o"
+ALL=$(sed -n 's/^SRCS *= *//p' Makefile)   # the Makefile's source list: a variant links every other object of the default build
+OTHERS=""
 for f in $ALL; do [ "$f" = "$SRC" ] || OTHERS="$OTHERS build/$f.o"; done
 make -s $OTHERS
 FL="-O3 -std=c++17 -fPIC --offload-arch=gfx950 -I../../include -Wall -Wno-unused-function -Wno-unused-value -Wno-unused-result"
