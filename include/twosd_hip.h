@@ -127,7 +127,10 @@ int twosd_canonical_form(int m2, int n2, const int64_t *W_colptr, const int64_t 
  * Random element positions of a scenario (spSmpsScenario entries, smps_sto.jl:135):
  * element e sits at stage-2 row row[e] (a row of the caller's template: < m2, never a bound
  * row); col[e] = -1 for an RHS entry, else the first-stage column of a T entry
- * (delta_coefficients, subprob.jl:104-121).
+ * (delta_coefficients, subprob.jl:104-121).  The listing fixes the columns of the value arrays
+ * only: every decision uses the canonical element order (ascending row, RHS first, then T columns
+ * ascending).  An element listed twice is refused with TWOSD_E_ARG (the reference keeps the last
+ * write, subprob.jl:114-117); a refused call leaves k and the positions as they were.
  */
 int twosd_set_random_positions(twosd_ctx *ctx, int k, const int *row, const int *col, int index_base);
 

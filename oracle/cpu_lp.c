@@ -452,7 +452,9 @@ void oracle_build_cut(int m, int n1, int nv, int N, int k, const int *rows, cons
     for (int i = 0; i < m; ++i) { double tx = 0.0; for (int j = 0; j < n1; ++j) tx += T[(size_t)i * n1 + j] * x[j]; base[i] = r[i] - tx; }
     double *vb = (double *)malloc(sizeof(double) * (nv ? nv : 1));
     for (int v = 0; v < nv; ++v) { double s = 0; for (int i = 0; i < m; ++i) s += V[(size_t)v * m + i] * base[i]; vb[v] = s; }
-    /* elements by ascending row (element order within a row): insertion sort, k is small */
+    /* elements by ascending row, a row's elements in the order given (stable): RHS-only scenarios have one
+     * element per row; a caller that folds T elements into DR lists a row's elements in the canonical
+     * order (RHS first, then T columns ascending).  Insertion sort, k is small */
     int *ord = (int *)malloc(sizeof(int) * (k ? k : 1));
     for (int j = 0; j < k; ++j) {
         int q = j;

@@ -219,11 +219,20 @@ def _seq_rowdot(A, b):
     return np.cumsum(A * b[None, :], axis=1)[:, -1]
 
 
-def _element_terms(dr, dT, x):
+def _element_terms(dr, dT, x, order=None):
     """(row, coef_e * dv_e) of every nonzero random element of a scenario, by ascending row (RHS
-    element first, then T columns ascending): the terms restated_score adds one at a time."""
+    element first, then T columns ascending): the terms restated_score adds one at a time.
+    order (tests only): a listing [(row, col)] of every random element, col < 0 for RHS; the terms
+    then come by ascending row and, within a row, in that listing's order."""
     rows, fac = [], []
     dT = np.asarray(dT)
+    if order is not None:
+        for i, j in sorted(order, key=lambda p: p[0]):          # stable: the listing's order within a row
+            v = float(dr[i]) if j < 0 else float(dT[i, j])
+            if v != 0:
+                rows.append(i)
+                fac.append(v if j < 0 else float(-x[j]) * v)
+        return np.array(rows, dtype=np.int64), np.array(fac, dtype=np.float64)
     for i in np.flatnonzero((np.asarray(dr) != 0) | (dT != 0).any(axis=1)):
         if dr[i] != 0:
             rows.append(i)
@@ -234,7 +243,7 @@ def _element_terms(dr, dT, x):
     return np.array(rows, dtype=np.int64), np.array(fac, dtype=np.float64)
 
 
-def argmax_procedure(coef: Coefficients, deltas, x, V, tie_rel: float = 0.0):
+def argmax_procedure(coef: Coefficients, deltas, x, V, tie_rel: float = 0.0, order=None):
     """subprob.jl:141-169 (MIN_SENSE).  tie_rel == 0 is the reference rule exactly (strict
     '>' so the first maximum in insertion order wins).  tie_rel > 0 is the build's
     documented near-tie rule: the lowest vertex index whose score is within
@@ -246,7 +255,8 @@ def argmax_procedure(coef: Coefficients, deltas, x, V, tie_rel: float = 0.0):
     element; within a row the RHS element first, then T columns ascending).  With one random
     element per row this is the dense dot(pi, dvec) with its zero rows dropped (adding an exact
     0 changes nothing).  The reference's OpenBLAS ddot adds in a CPU-dependent blocked order, so
-    at rounding-level ties its pick is not reproducible by any restatement."""
+    at rounding-level ties its pick is not reproducible by any restatement.
+    order (tests only) replaces the canonical within-row order by a listing's, see _element_terms."""
     x = np.asarray(x, dtype=np.float64)
     base = _seq_base(coef, x)
     Vl = list(V)
@@ -254,7 +264,7 @@ def argmax_procedure(coef: Coefficients, deltas, x, V, tie_rel: float = 0.0):
     Vm = np.array(Vl, dtype=np.float64).reshape(len(Vl), -1)
     vb = _seq_rowdot(Vm, base)
     for dr, dT in deltas:
-        rows, fac = _element_terms(dr, dT, x)
+        rows, fac = _element_terms(dr, dT, x, order)
         t = _seq_rowdot(Vm[:, rows], fac) if len(rows) else np.zeros(len(Vl))
         scores = [float(s) for s in (vb + t)]
         if tie_rel == 0.0:
@@ -272,9 +282,10 @@ def argmax_procedure(coef: Coefficients, deltas, x, V, tie_rel: float = 0.0):
     return np.array(vals), np.array(args, dtype=np.int64)
 
 
-def build_sasa_cut(coef: Coefficients, deltas, weights, x, V, tie_rel: float = 0.0):
-    """epigraph.jl:125-146.  Returns (alpha, beta, weight_mark, max_val, max_arg)."""
-    max_val, max_arg = argmax_procedure(coef, deltas, x, V, tie_rel)
+def build_sasa_cut(coef: Coefficients, deltas, weights, x, V, tie_rel: float = 0.0, order=None):
+    """epigraph.jl:125-146.  Returns (alpha, beta, weight_mark, max_val, max_arg).  order: tests only,
+    see _element_terms."""
+    max_val, max_arg = argmax_procedure(coef, deltas, x, V, tie_rel, order)
     Vl = list(V)
     total = float(sum(weights))           # epi.total_scenario_weight (epigraph.jl:89)
     alpha = 0.0

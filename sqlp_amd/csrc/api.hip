@@ -436,14 +436,22 @@ extern "C" int twosd_set_random_positions(twosd_ctx *c, int k, const int *row, c
     if (k < 0 || (k > 0 && (!row || !col))) return fail(TWOSD_E_ARG, "set_random_positions: bad arguments");
     for (auto &e : c->epis)
         if (e.count) return fail(TWOSD_E_STATE, "set_random_positions: epigraphs already hold scenarios");
-    c->pos_row.resize(k); c->pos_col.resize(k);
+    // checked into a copy first: a refused call leaves k and the positions as they were
+    std::vector<int> pr(k), pc(k);
     for (int e = 0; e < k; ++e) {
         const int rr = row[e] - base;
         const int cc = col[e] < 0 ? -1 : col[e] - base;
         if (rr < 0 || rr >= c->m2_user) return fail(TWOSD_E_ARG, "position %d: row %d out of range", e, row[e]);   // not a bound row
         if (cc >= c->n1) return fail(TWOSD_E_ARG, "position %d: column %d is not a first-stage column (KeyError in delta_coefficients, subprob.jl:116)", e, col[e]);
-        c->pos_row[e] = rr; c->pos_col[e] = cc;
+        // a position listed twice: the reference keeps the last write (delta_rhs[row] = ..., subprob.jl:114-117),
+        // every kernel here would add both deltas; refused (k <= 127 for the cut, so the scan is short)
+        for (int d = 0; d < e; ++d)
+            if (pr[d] == rr && pc[d] == cc)
+                return fail(TWOSD_E_ARG, "positions %d and %d are the same element (row %d, %s %d)", d, e, row[e],
+                            cc < 0 ? "RHS, column" : "column", col[e]);
+        pr[e] = rr; pc[e] = cc;
     }
+    c->pos_row.swap(pr); c->pos_col.swap(pc);
     c->k = k;
     c->prep_valid = false;
     c->k_valid = false;

@@ -2023,11 +2023,15 @@ static int update_pk(twosd_ctx *c) {
     if (!w->rows || w->pk_k4 != k4 || w->m != m) {
         if ((rc = w->rows.alloc(std::max(k, 1))) || (rc = w->eord.alloc(std::max(k, 1)))) return rc;
         if (k) HIPCHK(hipMemcpy(w->rows, c->pos_row.data(), sizeof(int) * k, hipMemcpyHostToDevice));
-        // the restated score's element order: ascending row (the dense dot over the m rows), element
-        // order within a row
+        // the restated score's element order: ascending row (the dense dot over the m rows); within a
+        // row the RHS element (column -1) first, then the T columns ascending -- the canonical order of
+        // twosd_ref._element_terms, whatever order the caller listed the positions in (no position
+        // is listed twice, twosd_set_random_positions, so this is a total order)
         std::vector<int> ord(k);
         for (int e = 0; e < k; ++e) ord[e] = e;
-        std::stable_sort(ord.begin(), ord.end(), [&](int a, int b) { return c->pos_row[a] < c->pos_row[b]; });
+        std::sort(ord.begin(), ord.end(), [&](int a, int b) {
+            return c->pos_row[a] != c->pos_row[b] ? c->pos_row[a] < c->pos_row[b] : c->pos_col[a] < c->pos_col[b];
+        });
         if (k) HIPCHK(hipMemcpy(w->eord, ord.data(), sizeof(int) * k, hipMemcpyHostToDevice));
         w->pk_count = 0;
         w->pk_k4 = k4;

@@ -152,12 +152,22 @@ class SDContext:
 
     def set_positions(self, positions):
         """Random-element layout; KeyError for an unknown row/column like
-        delta_coefficients (subprob.jl:112,116)."""
-        self.positions = [spSmpsPosition(*p) for p in positions]
-        self.pos_index = {p: e for e, p in enumerate(self.positions)}
-        rows = np.array([self.row_lookup[p.row_name] for p in self.positions], dtype=np.int32)
+        delta_coefficients (subprob.jl:112,116); ValueError, before any device call, for an element
+        listed twice (the reference keeps the last write, subprob.jl:114-117; the kernels would add
+        both deltas, so twosd_set_random_positions refuses it too).  The order of the listing fixes
+        the columns of the value arrays only: every decision uses the canonical element order
+        (ascending row, RHS first, then T columns ascending)."""
+        new = [spSmpsPosition(*p) for p in positions]
+        rows = np.array([self.row_lookup[p.row_name] for p in new], dtype=np.int32)
         cols = np.array([-1 if p.col_name in ("RHS", "rhs") else self.col_lookup[p.col_name]
-                         for p in self.positions], dtype=np.int32)
+                         for p in new], dtype=np.int32)
+        seen = {}
+        for e, rc in enumerate(zip(rows.tolist(), cols.tolist())):
+            if rc in seen:
+                raise ValueError(f"positions {seen[rc]} and {e} are the same element {tuple(new[e])}")
+            seen[rc] = e
+        self.positions = new
+        self.pos_index = {p: e for e, p in enumerate(self.positions)}
         self.k = len(self.positions)
         self.rows, self.cols = rows, cols
         ib = self.index_base

@@ -237,3 +237,200 @@ def near_ties(scores):
 
 def cut_scores(S, Vm, x, vals):
     return (Vm @ (S.r - S.T @ x))[None, :] + (vals - S.r[S.rows]) @ Vm[:, S.rows].T
+
+
+# ---- random technology-matrix (T) elements on the generated templates ---------------------------------
+# The templates above have coef_e == 1 on every element (RHS rows only).  t_variant keeps a template's
+# W, q, senses and k -- and with k its (R, C, KB) slots -- and re-lays the k random elements so that about
+# half are T entries (coef_e = -x[col]), several of them share a row, and one row is a directed tie.
+T_AMP = 0.3               # a T element's value: the template's entry + U(-T_AMP, T_AMP)
+T_LP_IDS = ["c", "e", "g"]            # LP + pool + cut
+T_CUT_IDS = ["k95", "k96"]            # the cut only: KB 24 top / 30 bottom, two int8 slices
+T_LAYOUTS = ["distinct", "shared"]
+TIE_COL = 0               # X[0][TIE_COL] == 0.5, a power of two: a / x is exact
+TIE_OFFSETS = tuple(round((-1) ** i * 4.37 * 1.35 ** i, 2) for i in range(16))   # component i0 of the appended copies: 4.37 ... -394
+TIE_TOP = 128              # the most-picked vertices that get copies
+# (template, layout): (seed, amp of the RHS elements, scale of TIE_OFFSETS).  With half of the elements
+# on T entries (whose effect on the rhs, |dT x[col]| <= 0.3, is small) and several on one row, fewer
+# rows of b vary than in the RHS-only template, so amp is picked again from the ladder, and the seed
+# and the scale with it, as values at which the oracle and twosd_ref alone meet every condition that
+# tests/test_telement_cases.py asserts.  The scale matters because a copy's rounding residue is seen
+# only if it survives the last addition base[v] + t, and depends on the order of the two terms only
+# while |offset a| is not far above the partial sum it is added to: larger offsets win the argmax
+# the same way in either order and hide the smaller ones.
+T_VARIANTS = {
+    ("c", "distinct"): (0, 3.0, 1.0), ("c", "shared"): (1, 50.0, 1.0),
+    ("e", "distinct"): (0, 1.0, 1.0), ("e", "shared"): (1, 4.0, 1.0),
+    ("g", "distinct"): (0, 0.3, 1.0), ("g", "shared"): (0, 0.4, 1.0),
+    ("k95", "distinct"): (0, 0.2, 1.0), ("k95", "shared"): (0, 1.0, 16.0),
+    ("k96", "distinct"): (0, 0.2, 1.0), ("k96", "shared"): (0, 1.0, 16.0),
+}
+
+
+def t_variant(tid, layout, seed=None, amp=None, tie_scale=None):
+    """template(tid) with random T elements.  Returns a namespace like template()'s (same W, q, sense,
+    m2, n2, k, dispatch) plus: elems = [(row, col)] in listing order (col -1: RHS), rows / cols (int32, per
+    element), positions (names), tmpl (template value per element), xz (the X_Z point), canon (the listing
+    indices in the canonical order: ascending row, RHS first, T columns ascending), and for "shared"
+    i0 / j0, the directed tie row and its T column.
+
+    "distinct": k elements on the template's k rows, RHS and T alternating, listed by descending row (so
+    the restated order is not the listing); the first T element sits on a structural zero of T.
+    "shared" (k >= 4): the tie row holds (RHS, T); for k >= 7 one row holds (RHS, T, T) and one (T, T)
+    (those three rows take 7 elements: template c, k = 4, has the tie row only); the other elements sit
+    on rows of their own, RHS and T alternating; the listing is a seeded shuffle.  The tie row i0 is the
+    highest random row (so every other element's term is added before its two), with r[i0] = 0 and
+    T[i0, :] = 0 on the variant's copy of the template.
+    xz = X[0] with one T element's column at 0.0 (coef = -0.0) and another at -0.3 (coef > 0).
+    seed, amp (the RHS elements' amplitude) and tie_scale default to T_VARIANTS[(tid, layout)]."""
+    B = template(tid)
+    assert layout in T_LAYOUTS and (layout == "distinct" or B.k >= 4)
+    cfg = T_VARIANTS[(tid, layout)]
+    seed, amp, tie_scale = [c if v is None else v for v, c in zip((seed, amp, tie_scale), cfg)]
+    rng = np.random.default_rng(100003 * B.seed + 17 * seed + T_LAYOUTS.index(layout))
+    k, n1 = B.k, B.T.shape[1]
+    r, T = B.r.copy(), B.T.copy()
+    i0 = j0 = None
+    if layout == "distinct":
+        elems, t = [], 0
+        for e, i in enumerate(int(v) for v in B.rows):
+            if e % 2 == 0 and k > 1:
+                elems.append((i, -1))
+                continue
+            if t == 0:
+                c0 = int(np.flatnonzero(T[i] == 0.0)[0])          # a structural zero of T
+            elems.append((i, (c0 + t) % n1))
+            t += 1
+        elems = elems[::-1]
+    else:
+        groups, left = [[-1, TIE_COL]], k - 2
+        if k >= 7:
+            groups += [[-1] + sorted(rng.choice(n1, 2, replace=False).tolist()), sorted(rng.choice(n1, 2, replace=False).tolist())]
+            left -= 5
+        groups += [[int(1 + rng.integers(n1 - 1))] if e % 2 else [-1] for e in range(left)]
+        used = [int(v) for v in B.rows[:len(groups)]]
+        i0, j0 = used[-1], TIE_COL
+        r[i0] = 0.0
+        T[i0, :] = 0.0
+        order = [used[-1]] + used[:-1]                            # the tie row, then the shared rows from the lowest row up
+        elems = [(i, j) for i, g in zip(order, groups) for j in g]
+        elems = [elems[p] for p in rng.permutation(len(elems))]
+    assert len(elems) == k == len(set(elems))
+    rows = np.array([i for i, _ in elems], dtype=np.int32)
+    cols = np.array([j for _, j in elems], dtype=np.int32)
+    tmpl = np.array([r[i] if j < 0 else T[i, j] for i, j in elems])
+    tcols = [int(j) for j in dict.fromkeys(cols[cols >= 0].tolist())]
+    pick = [j for j in tcols if j != j0] + [j for j in tcols if j == j0]
+    xz = X[0].copy()
+    xz[pick[0]] = 0.0
+    if len(pick) > 1:
+        xz[pick[1]] = -0.3
+    S = SimpleNamespace(m2=B.m2, n2=B.n2, k=k, seed=B.seed, amp=amp, tie_scale=tie_scale, W=B.W, T=T, q=B.q, r=r, sense=B.sense, lb=B.lb, ub=B.ub,
+                        id=f"{tid}-{layout}", base_id=tid, layout=layout, dispatch=B.dispatch, elems=elems, rows=rows, cols=cols,
+                        tmpl=tmpl, xz=xz, i0=i0, j0=j0, vseed=seed,
+                        positions=[("RHS" if j < 0 else f"x{j}", f"r{i}") for i, j in elems],
+                        canon=sorted(range(k), key=lambda e: elems[e]),
+                        sp2=BC.stage_problem(B.W, T, B.q, r, B.sense, B.lb, B.ub), hp=B.hp)
+    # what oracle/twosd_ref.Coefficients reads
+    S.osp = SimpleNamespace(r=r, T=T, W=B.W, last_names=[f"x{j}" for j in range(n1)], row_names=[f"r{i}" for i in range(B.m2)])
+    return S
+
+
+def t_relisted(S, perm):
+    """S with its elements listed in the order perm (listing indices); t_values(S)[:, perm] are its values."""
+    R = SimpleNamespace(**vars(S))
+    R.elems = [S.elems[e] for e in perm]
+    R.rows, R.cols, R.tmpl = S.rows[perm], S.cols[perm], S.tmpl[perm]
+    R.positions = [S.positions[e] for e in perm]
+    R.canon = sorted(range(S.k), key=lambda e: R.elems[e])
+    return R
+
+
+def t_xs(S):
+    """The x points of the T variants: where V is built, elsewhere, and X_Z."""
+    return [("X0", X[0]), ("X1", X[1]), ("XZ", S.xz)]
+
+
+def t_values(S, N=N_SCEN, seed=SEED_VALUES):
+    """N scenario values of the k elements in listing order: r[row] + U(-amp, amp) for an RHS element,
+    T[row, col] + U(-T_AMP, T_AMP) for a T element; on the tie row a ~ U(-1, 1) for the RHS element and
+    a / X[0][j0] (exact: a power of two) for the T element, so that coef * dv == -a at X[0]."""
+    rng = np.random.default_rng(1000 * S.seed + 31 * S.vseed + seed)
+    u = rng.uniform(-1.0, 1.0, size=(N, S.k))
+    a = rng.uniform(-1.0, 1.0, size=N)
+    vals = np.empty((N, S.k))
+    for e, (i, j) in enumerate(S.elems):
+        if i == S.i0:
+            vals[:, e] = a if j < 0 else a / X[0][S.j0]
+        else:
+            vals[:, e] = S.tmpl[e] + (S.amp if j < 0 else T_AMP) * u[:, S.canon.index(e)]
+    return vals
+
+
+def t_coef(S, x):
+    """coef_e(x): 1 for an RHS element, -x[col] for a T element."""
+    return np.array([1.0 if j < 0 else -x[j] for _, j in S.elems])
+
+
+def t_rhs_deltas(S, x, vals):
+    """(rows, base, DR) of the oracle LP: b = base + sum_e DR[:, e] e_row(e), base = r - T x, DR = dr for an
+    RHS element and -(dT) x[col] for a T element (b = (r + dr) - (T + dT) x)."""
+    return S.rows, S.r - S.T @ x, (vals - S.tmpl) * t_coef(S, x)[None, :]
+
+
+def t_rhs(S, x, vals):
+    rows, base, DR = t_rhs_deltas(S, x, vals)
+    B = np.tile(base, (len(vals), 1))
+    for e, i in enumerate(rows):
+        B[:, i] += DR[:, e]
+    return B
+
+
+def t_start_head(S, x, v0):
+    """start_head for a T variant: the unique optimal basis of scenario v0 at x (HiGHS)."""
+    from oracle import lp_highs
+    b = t_rhs(S, x, v0[None, :])[0]
+    st, _, y, _ = lp_highs.solve_rhs(S.hp, b)
+    assert st == 0
+    slack = S.W @ y - b
+    head = [j for j in range(S.n2) if y[j] > 1e-7]
+    head += [S.n2 + i for i in range(S.m2) if S.sense[i] != "E" and abs(slack[i]) > 1e-7]
+    assert len(head) == S.m2, (S.id, len(head), S.m2)
+    return np.array(head, dtype=np.int32)
+
+
+def t_oracle_solve(S, lp, x, vals, nthreads=4):
+    rows, base, DR = t_rhs_deltas(S, x, vals)
+    return lp.solve_batch(rows, base, DR, want_y=True, nthreads=nthreads)
+
+
+def t_scores(S, Vm, x, vals):
+    """Scores of every (scenario, vertex) to rounding (the near-tie count, not a decision)."""
+    _, base, DR = t_rhs_deltas(S, x, vals)
+    return (Vm @ base)[None, :] + DR @ Vm[:, S.rows].T
+
+
+def t_ref_deltas(S, vals):
+    """(Coefficients, [delta_coefficients of every scenario]) of oracle/twosd_ref.py."""
+    from oracle import twosd_ref
+    coef = twosd_ref.Coefficients(S.osp)
+    return coef, [twosd_ref.delta_coefficients(coef, list(zip(S.positions, v))) for v in vals]
+
+
+def t_with_tie_copies(S, Vm, picks):
+    """Vm with copies of the TIE_TOP most-picked vertices appended, each changed only in component i0 by
+    one of TIE_OFFSETS: at X[0] a copy ties its original exactly in real arithmetic (row i0's base is 0
+    and its two terms cancel), so rounding and the order of the two terms decide the pick."""
+    top = np.argsort(-np.bincount(picks, minlength=len(Vm)), kind="stable")[:TIE_TOP]
+    copies = []
+    for off in TIE_OFFSETS:
+        off = S.tie_scale * off
+        c = Vm[top].copy()
+        c[:, S.i0] += off
+        copies.append(c)
+    return np.vstack([Vm] + copies)
+
+
+def t_reversed_within_rows(S):
+    """The element listing [(row, col)] in the canonical order with every row's elements reversed."""
+    return sorted(S.elems, key=lambda p: (p[0], -p[1]))
