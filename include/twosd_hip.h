@@ -534,6 +534,24 @@ int twosd_bootstrap_count_of_word(uint32_t u);
 int twosd_bootstrap_counts(twosd_ctx *ctx, int M, uint64_t seed, uint64_t first_index, int64_t count, uint8_t *out);
 
 /*
+ * The bootstrap on a variance-reduced epigraph (twosd_sampling, group G): the observations of such
+ * a stream are its groups, so the bootstrap resamples whole groups.  The count of the scenario with
+ * global index g in replicate b is c_b(g / G): the count function above, indexed by the GLOBAL GROUP
+ * INDEX.  Every member of a group carries its group's count and keeps its own weight w_s; integer
+ * weights, the normalisation by the replicate's own W_jb, the identity row 0 and the zero cut at
+ * W_jb = 0 are those of twosd_reform_cuts.  G = 1 (a NULL plan or mode IID) is the namesake call
+ * itself, bit for bit.  Sharding on group boundaries reproduces the draws.
+ *   bootstrap_counts_vr: first_index and count multiples of G; out[s * M + b] = c_b((first_index + s) / G).
+ *   reform_cuts_vr / reform_partial_vr: index_offset, the epigraph's current scenario count and every
+ *     handle's N_j multiples of G.  twosd_reform_partial_len and twosd_reform_finalize do not depend
+ *     on the plan.
+ * TWOSD_E_ARG with the offending value in the message for an invalid plan (as every _vr call) and
+ * for each quantity above that is not in whole groups (a handle is named).
+ */
+int twosd_bootstrap_counts_vr(twosd_ctx *ctx, int M, uint64_t seed, uint64_t first_index, int64_t count, uint8_t *out,
+                              const twosd_sampling *plan);
+
+/*
  * Re-formed cuts under bootstrap weights (the device part of the in-sample stopping rule; no
  * reference counterpart: plugin/stopping_rule.jl is empty).  For each of the H handles (all of
  * epigraph epi) and each row b of M + 1 -- row 0 the identity replicate (all counts 1), row 1 + b
@@ -569,6 +587,11 @@ int twosd_reform_partial(twosd_ctx *ctx, int epi, int H, const int *handles, int
                          double total_weight, uint64_t *d_u64, double *d_f64);
 int twosd_reform_finalize(twosd_ctx *ctx, int H, const int *handles, int M, double total_weight, const uint64_t *d_u64,
                           const double *d_f64, double *alpha, double *beta, double *weight_mark, double *total_weight_out);
+/* The same under a sampling plan: whole groups are resampled (see twosd_bootstrap_counts_vr). */
+int twosd_reform_cuts_vr(twosd_ctx *ctx, int epi, int H, const int *handles, int M, uint64_t seed, uint64_t index_offset,
+                         double *alpha, double *beta, double *weight_mark, double *total_weight, const twosd_sampling *plan);
+int twosd_reform_partial_vr(twosd_ctx *ctx, int epi, int H, const int *handles, int M, uint64_t seed, uint64_t index_offset,
+                            double total_weight, uint64_t *d_u64, double *d_f64, const twosd_sampling *plan);
 /* Device time of the last twosd_reform_cuts on the context's stream (HIP events), milliseconds:
  * [0] the partial sums (histograms, delta streaming, reductions), [1] the finalize with its copies. */
 int twosd_reform_last_ms(twosd_ctx *ctx, double *ms2);

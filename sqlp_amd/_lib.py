@@ -112,6 +112,9 @@ SIGNATURES = [
     ("twosd_evaluate_moments_vr", I, [P, P, C.c_int64, C.c_int64, C.c_uint64, P, P]),
     ("twosd_evaluate_paired_vr", I, [P, P, P, C.c_int64, C.c_int64, C.c_uint64, P, P, P, P]),
     ("twosd_evaluate_ci_vr", I, [P, P, C.c_uint64, C.c_int64, C.c_int64, C.c_int64, D, D, D, D, P, P, P, P]),
+    ("twosd_bootstrap_counts_vr", I, [P, I, C.c_uint64, C.c_uint64, C.c_int64, P, P]),
+    ("twosd_reform_cuts_vr", I, [P, I, I, P, I, C.c_uint64, C.c_uint64, P, P, P, P, P]),
+    ("twosd_reform_partial_vr", I, [P, I, I, P, I, C.c_uint64, C.c_uint64, D, P, P, P]),
 ]
 
 SAMPLING_IID, SAMPLING_ANTITHETIC, SAMPLING_LHS = 0, 1, 2

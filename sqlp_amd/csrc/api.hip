@@ -1808,7 +1808,7 @@ extern "C" int twosd_set_distributions(twosd_ctx *c, int k, const int *kind, con
 }
 
 // a caller's sampling plan -> (mode, G); NULL means i.i.d.
-static int sampling_plan(const twosd_sampling *plan, const char *who, int *mode, int *G) {
+int twosd::sampling_plan(const twosd_sampling *plan, const char *who, int *mode, int *G) {
     *mode = TWOSD_SAMPLING_IID;
     *G = 1;
     if (!plan) return TWOSD_OK;
@@ -1832,7 +1832,7 @@ static int sampling_plan(const twosd_sampling *plan, const char *who, int *mode,
 }
 
 // `what` = value must be a whole number of groups
-static int whole_groups(const char *who, const char *what, unsigned long long value, int G) {
+int twosd::whole_groups(const char *who, const char *what, unsigned long long value, int G) {
     if (G > 1 && value % (unsigned long long)G)
         return fail(TWOSD_E_ARG, "%s: %s = %llu is no multiple of the sampling group %d", who, what, value, G);
     return TWOSD_OK;

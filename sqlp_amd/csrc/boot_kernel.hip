@@ -22,6 +22,12 @@
 // the order of its terms: the per-vertex weights, W_jb and the epigraph totals are bit-identical on
 // every run and add exactly across ranks.  The S_e sums are fp64 with a fixed shard layout.
 //
+// On an epigraph filled from a variance-reduced stream (twosd_sampling, group G) the observations
+// are the groups: the _vr entry points give scenario s the count c_b((index_offset + s) / G) of its
+// global group index, every member of a group the same, each with its own q_s.  The kernels that
+// draw counts are templates: <false> / <KE, 0> are the i.i.d. kernels, the others index their draws
+// by the group (boot_index); the host divides index_offset by G once.
+//
 // Kernels:
 //   boot_counts_kernel   the counts themselves (diagnostic: twosd_bootstrap_counts)
 //   boot_weight_kernel   sum_{s < n} c_b(s) q_s per replicate (W_jb with n = N_j; the totals with n = N)
@@ -32,7 +38,7 @@
 //                        walks tiles of 64 scenarios; lanes = scenarios for the Philox draws, then
 //                        lanes = elements (e = lane, lane + 64) while the tile's scenarios go by one
 //                        at a time with wave-uniform picks and counts (v_readlane); 16 + 1
-//                        accumulators per element stay in VGPRs (KE = 2: 127 VGPRs, no scratch)
+//                        accumulators per element stay in VGPRs (KE = 2: 191 VGPRs, no scratch)
 //   boot_reduce_kernel   the blocks' S partials summed in block order
 //   boot_g_kernel        gpart = (per-vertex weights) x V for 8 replicate rows at a time, skipping the
 //                        vertices no scenario picked (the identity row's weight is 0)
@@ -69,14 +75,26 @@ __device__ __forceinline__ unsigned long long boot_q(double w, double scale) {
     return w > 0.0 ? (unsigned long long)__double2ull_rn(w * scale) : 0ull;   // NaN and w <= 0 weigh nothing
 }
 
+// GR (here and below): the draw's index is the scenario's group, first / off count groups and G is
+// the group size (a variance-reduced stream: every member of a group carries its group's count);
+// !GR: the scenario itself, G unused.  A 32-bit division per lane: a call's scenarios stay below 2^31.
+template <bool GR>
+__device__ __forceinline__ unsigned long long boot_index(unsigned long long off, int s, unsigned G) {
+    if constexpr (GR) return off + (unsigned long long)((unsigned)s / G);
+    else return off + (unsigned long long)s;
+}
+
+template <bool GR>
 __global__ void __launch_bounds__(256) boot_counts_kernel(int M, unsigned long long seed, unsigned long long first, long long count,
-                                                          uint8_t *__restrict__ out) {
+                                                          uint8_t *__restrict__ out, unsigned G) {
     const int nq = (M + 3) / 4;
     const long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (idx >= count * nq) return;
     const long long s = idx / nq;
     const int Q = (int)(idx - s * nq);
-    const Philox4 r = boot_words(first + (unsigned long long)s, Q, seed);
+    Philox4 r;
+    if constexpr (GR) r = boot_words(boot_index<true>(first, (int)s, G), Q, seed);   // s < count <= 2^24
+    else r = boot_words(first + (unsigned long long)s, Q, seed);
 #pragma unroll
     for (int t = 0; t < 4; ++t)
         if (4 * Q + t < M) out[s * M + 4 * Q + t] = (uint8_t)boot_count_of_word(r.v[t]);
@@ -85,16 +103,17 @@ __global__ void __launch_bounds__(256) boot_counts_kernel(int M, unsigned long l
 // out[0] += sum q_s, out[1 + b] += sum c_b(s) q_s over s < n; blockIdx.y = the Philox call Q of four
 // replicates, the last y the identity row.  Integer sums: any order gives the same bits.  One atomic
 // per block and replicate (a few blocks: every wave adding to the same 33 words took 0.5 ms).
+template <bool GR>
 __global__ void __launch_bounds__(256) boot_weight_kernel(int n, const double *__restrict__ w, double scale, int M,
                                                           unsigned long long seed, unsigned long long off,
-                                                          unsigned long long *__restrict__ out) {
+                                                          unsigned long long *__restrict__ out, unsigned G) {
     __shared__ unsigned long long sh[4][4];
     const int nq = (M + 3) / 4, Q = blockIdx.y;
     unsigned long long a[4] = {0ull, 0ull, 0ull, 0ull};
     for (int s = blockIdx.x * 256 + threadIdx.x; s < n; s += gridDim.x * 256) {
         const unsigned long long q = boot_q(w[s], scale);
         if (Q == nq) { a[0] += q; continue; }
-        const Philox4 r = boot_words(off + (unsigned long long)s, Q, seed);
+        const Philox4 r = boot_words(boot_index<GR>(off, s, G), Q, seed);
 #pragma unroll
         for (int t = 0; t < 4; ++t) a[t] += (unsigned long long)boot_count_of_word(r.v[t]) * q;
     }
@@ -120,9 +139,10 @@ __global__ void __launch_bounds__(256) boot_weight_kernel(int n, const double *_
 // row), blockIdx.z = a window of kBootVW vertices (a pick outside it is another block's).  Integer
 // sums: the atomics' order does not show in the result.
 constexpr int kBootVW = 2048;
+template <bool GR>
 __global__ void __launch_bounds__(1024) boot_hist_kernel(int n, int nv, int nvs, int M, const int *__restrict__ picks,
                                                          const double *__restrict__ w, double scale, unsigned long long seed,
-                                                         unsigned long long off, unsigned long long *__restrict__ hist) {
+                                                         unsigned long long off, unsigned long long *__restrict__ hist, unsigned G) {
     __shared__ unsigned long long hl[4 * kBootVW];
     const int nq = (M + 3) / 4, Q = blockIdx.y;
     const int v0 = blockIdx.z * kBootVW, v1 = min(nv, v0 + kBootVW);
@@ -137,7 +157,7 @@ __global__ void __launch_bounds__(1024) boot_hist_kernel(int n, int nv, int nvs,
             __hip_atomic_fetch_add(&hl[pick - v0], q, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
             continue;
         }
-        const Philox4 r = boot_words(off + (unsigned long long)s, Q, seed);
+        const Philox4 r = boot_words(boot_index<GR>(off, s, G), Q, seed);
 #pragma unroll
         for (int t = 0; t < 4; ++t) {
             const int cnt = (4 * Q + t < M) ? boot_count_of_word(r.v[t]) : 0;
@@ -157,6 +177,7 @@ __global__ void __launch_bounds__(1024) boot_hist_kernel(int n, int nv, int nvs,
 
 struct BootParams {
     int n, k, k4, nv, M, ngroups, tpb;   // tpb: 64-scenario tiles per block
+    int G;                               // sampling group (grouped kernels; off then counts groups)
     double scale;
     unsigned long long seed, off;
     const double *dv, *w, *PK;
@@ -164,8 +185,14 @@ struct BootParams {
     double *slots;                       // nchunks x (M + 1) x k
 };
 
-// KE: elements per lane (k <= 64 KE)
-template <int KE>
+// KE: elements per lane (k <= 64 KE).  GM: whose count a scenario carries --
+//   0  its own (the i.i.d. epigraph)
+//   1  its group's, any G: groups straddle tiles, waves and chunks, and a count is a pure function of
+//      the group index, so each lane draws the words of its own scenario's group
+//   2  its group's, G a multiple of 64: off and every tile start are multiples of 64, so a tile lies
+//      inside one group and its 16 counts are wave-uniform -- one draw per tile, held in SGPRs, and
+//      the tile's terms are summed once and weighed by the 16 counts at the tile's end
+template <int KE, int GM>
 __global__ void __launch_bounds__(256) boot_reform_kernel(BootParams P) {
     __shared__ double comb[(kBootGroup + 1) * KE * 64];
     const int lane = threadIdx.x & 63;
@@ -195,12 +222,19 @@ __global__ void __launch_bounds__(256) boot_reform_kernel(BootParams P) {
             const int Q = grp * (kBootGroup / 4) + qd;
             Philox4 r;
             r.v[0] = r.v[1] = r.v[2] = r.v[3] = 0u;
-            if (4 * Q < P.M) r = boot_words(P.off + (unsigned long long)s, Q, P.seed);   // wave-uniform
+            if (4 * Q < P.M) r = boot_words(boot_index<GM != 0>(P.off, GM == 2 ? t * 64 : s, (unsigned)P.G), Q, P.seed);   // wave-uniform
 #pragma unroll
             for (int tt = 0; tt < 4; ++tt) {
                 const int cnt = (4 * Q + tt < P.M) ? boot_count_of_word(r.v[tt]) : 0;
                 chi[4 * qd + tt] = (unsigned)__double2hiint((double)cnt);
+                if constexpr (GM == 2) chi[4 * qd + tt] = (unsigned)__builtin_amdgcn_readfirstlane((int)chi[4 * qd + tt]);
             }
+        }
+        // GM == 2: the identity row's accumulator takes the tile's terms alone, from 0
+        double idsum[KE];
+        if constexpr (GM == 2) {
+#pragma unroll
+            for (int u = 0; u < KE; ++u) { idsum[u] = acc[kBootGroup][u]; acc[kBootGroup][u] = 0.0; }
         }
         const double qf = (double)q;
         const int qlo = __double2loint(qf), qhi = __double2hiint(qf);
@@ -232,7 +266,7 @@ __global__ void __launch_bounds__(256) boot_reform_kernel(BootParams P) {
 #pragma unroll
                 for (int u = 0; u < KE; ++u) term[u] = wq * p[u4][u] * d[u4][u];
 #pragma unroll
-                for (int r = 0; r < kBootGroup; ++r) {
+                for (int r = 0; r < (GM == 2 ? 0 : kBootGroup); ++r) {   // GM == 2: at the tile's end
                     const double cd = __hiloint2double(__builtin_amdgcn_readlane((int)chi[r], i), 0);   // wave-uniform count
 #pragma unroll
                     for (int u = 0; u < KE; ++u) acc[r][u] = fma(cd, term[u], acc[r][u]);
@@ -249,6 +283,15 @@ __global__ void __launch_bounds__(256) boot_reform_kernel(BootParams P) {
             if (i0 + 4 >= nvalid) break;
             if (i0 + 8 < nvalid) load4(i0 + 8, da, pa);
             work4(i0 + 4, db, pb);
+        }
+        if constexpr (GM == 2) {   // the tile's sum weighed by its 16 counts (SGPR pairs), then back into the identity row
+#pragma unroll
+            for (int u = 0; u < KE; ++u) {
+                const double tsum = acc[kBootGroup][u];
+#pragma unroll
+                for (int r = 0; r < kBootGroup; ++r) acc[r][u] = fma(__hiloint2double((int)chi[r], 0), tsum, acc[r][u]);
+                acc[kBootGroup][u] = idsum[u] + tsum;
+            }
         }
     }
     // the block's four waves combined in wave order
@@ -419,8 +462,10 @@ static int boot_layout(twosd_ctx *c, int epi, int H, const int *handles, int M, 
     return TWOSD_OK;
 }
 
+// G > 1: the counts of a variance-reduced stream's groups (off and every scenario count are whole
+// groups: the callers check); the kernels then index their draws by off / G + s / G
 static int boot_partial_impl(twosd_ctx *c, int epi, const BootLayout &L, const int *handles, int M, unsigned long long seed,
-                             unsigned long long off, double total_weight, unsigned long long *d_u64, double *d_f64) {
+                             unsigned long long off, int G, double total_weight, unsigned long long *d_u64, double *d_f64) {
     const EpiDevice &E = c->epis[epi];
     const int k = c->k, B = L.B;
     const double scale = kBootFix / total_weight;
@@ -429,10 +474,15 @@ static int boot_partial_impl(twosd_ctx *c, int epi, const BootLayout &L, const i
     if ((rc = cut_pk_current(c, &PK, &k4))) return rc;
     HIPCHK(hipMemsetAsync(d_u64, 0, sizeof(unsigned long long) * L.n_u64, c->stream));
     const int nq = (M + 3) / 4;
+    if (G > 1) off /= (unsigned long long)G;   // the one 64-bit division of a grouped call
     auto weights = [&](int n, unsigned long long *out) {
         if (n <= 0) return;
-        hipLaunchKernelGGL(boot_weight_kernel, dim3(std::max(1, std::min((n + 8191) / 8192, 32)), nq + 1), dim3(256), 0, c->stream, n,
-                           E.d_w.p, scale, M, seed, off, out);
+        const dim3 grid(std::max(1, std::min((n + 8191) / 8192, 32)), nq + 1);
+        if (G == 1)
+            hipLaunchKernelGGL(boot_weight_kernel<false>, grid, dim3(256), 0, c->stream, n, E.d_w.p, scale, M, seed, off, out, 1u);
+        else
+            hipLaunchKernelGGL(boot_weight_kernel<true>, grid, dim3(256), 0, c->stream, n, E.d_w.p, scale, M, seed, off, out,
+                               (unsigned)G);
     };
     weights(E.count, d_u64);
     const int ngroups = std::max(1, (M + kBootGroup - 1) / kBootGroup);
@@ -456,19 +506,32 @@ static int boot_partial_impl(twosd_ctx *c, int epi, const BootLayout &L, const i
     for (int j = 0; j < L.H; ++j) {
         const PickSet &h = c->boot.picks[handles[j]];
         weights(h.n, d_u64 + L.o_wj + (size_t)j * B);
-        hipLaunchKernelGGL(boot_hist_kernel, dim3(std::max(1, std::min((h.n + 8191) / 8192, 64)), nq + 1, (h.nv + kBootVW - 1) / kBootVW),
-                           dim3(1024), 0, c->stream, h.n, h.nv, L.nvs, M, h.d.p, E.d_w.p, scale, seed, off,
-                           d_u64 + L.o_hist + (size_t)j * B * L.nvs);
+        const dim3 hgrid(std::max(1, std::min((h.n + 8191) / 8192, 64)), nq + 1, (h.nv + kBootVW - 1) / kBootVW);
+        if (G == 1)
+            hipLaunchKernelGGL(boot_hist_kernel<false>, hgrid, dim3(1024), 0, c->stream, h.n, h.nv, L.nvs, M, h.d.p, E.d_w.p, scale, seed,
+                               off, d_u64 + L.o_hist + (size_t)j * B * L.nvs, 1u);
+        else
+            hipLaunchKernelGGL(boot_hist_kernel<true>, hgrid, dim3(1024), 0, c->stream, h.n, h.nv, L.nvs, M, h.d.p, E.d_w.p, scale, seed,
+                               off, d_u64 + L.o_hist + (size_t)j * B * L.nvs, (unsigned)G);
         if (k == 0) continue;
         int tpb, nchunks;
         shard(h.n, &tpb, &nchunks);
         BootParams P{};
-        P.n = h.n; P.k = k; P.k4 = k4; P.nv = h.nv; P.M = M; P.ngroups = ngroups; P.tpb = tpb;
+        P.n = h.n; P.k = k; P.k4 = k4; P.nv = h.nv; P.M = M; P.ngroups = ngroups; P.tpb = tpb; P.G = G;
         P.scale = scale; P.seed = seed; P.off = off;
         P.dv = E.d_dv; P.w = E.d_w; P.PK = PK; P.picks = h.d;
         P.slots = c->boot.slots;
-        if (k <= 64) hipLaunchKernelGGL(boot_reform_kernel<1>, dim3(nchunks * ngroups), dim3(256), 0, c->stream, P);
-        else hipLaunchKernelGGL(boot_reform_kernel<2>, dim3(nchunks * ngroups), dim3(256), 0, c->stream, P);
+        const dim3 rgrid(nchunks * ngroups);
+        if (G == 1) {
+            if (k <= 64) hipLaunchKernelGGL((boot_reform_kernel<1, 0>), rgrid, dim3(256), 0, c->stream, P);
+            else hipLaunchKernelGGL((boot_reform_kernel<2, 0>), rgrid, dim3(256), 0, c->stream, P);
+        } else if (G % 64 == 0) {   // a tile lies inside one group
+            if (k <= 64) hipLaunchKernelGGL((boot_reform_kernel<1, 2>), rgrid, dim3(256), 0, c->stream, P);
+            else hipLaunchKernelGGL((boot_reform_kernel<2, 2>), rgrid, dim3(256), 0, c->stream, P);
+        } else {
+            if (k <= 64) hipLaunchKernelGGL((boot_reform_kernel<1, 1>), rgrid, dim3(256), 0, c->stream, P);
+            else hipLaunchKernelGGL((boot_reform_kernel<2, 1>), rgrid, dim3(256), 0, c->stream, P);
+        }
         hipLaunchKernelGGL(boot_reduce_kernel, dim3((B * k + 31) / 32), dim3(256), 0, c->stream, nchunks, B * k, c->boot.slots.p,
                            d_f64 + (size_t)j * B * k);
     }
@@ -530,7 +593,8 @@ using namespace twosd;
 
 extern "C" int twosd_bootstrap_count_of_word(uint32_t u) { return boot_count_of_word(u); }
 
-extern "C" int twosd_bootstrap_counts(twosd_ctx *c, int M, uint64_t seed, uint64_t first_index, int64_t count, uint8_t *out) {
+// G > 1: scenario first_index + s carries the counts of group (first_index + s) / G (whole groups: the caller checks)
+static int bootstrap_counts_impl(twosd_ctx *c, int M, uint64_t seed, uint64_t first_index, int64_t count, int G, uint8_t *out) {
     if (!c) return fail(TWOSD_E_ARG, "bootstrap_counts: ctx is NULL");
     if (M < 1 || M > kBootMaxM) return fail(TWOSD_E_ARG, "bootstrap_counts: M = %d replicates outside [1, %d]", M, kBootMaxM);
     if (count < 0 || count > (1ll << 24) || (count > 0 && !out))
@@ -540,12 +604,32 @@ extern "C" int twosd_bootstrap_counts(twosd_ctx *c, int M, uint64_t seed, uint64
     int rc;
     if ((rc = c->boot.counts.fit((size_t)count * M))) return rc;
     const long long total = count * ((M + 3) / 4);
-    hipLaunchKernelGGL(boot_counts_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, c->stream, M,
-                       (unsigned long long)seed, (unsigned long long)first_index, (long long)count, c->boot.counts.p);
+    const dim3 grid((unsigned)((total + 255) / 256));
+    if (G == 1)
+        hipLaunchKernelGGL(boot_counts_kernel<false>, grid, dim3(256), 0, c->stream, M, (unsigned long long)seed,
+                           (unsigned long long)first_index, (long long)count, c->boot.counts.p, 1u);
+    else
+        hipLaunchKernelGGL(boot_counts_kernel<true>, grid, dim3(256), 0, c->stream, M, (unsigned long long)seed,
+                           (unsigned long long)first_index / (unsigned long long)G, (long long)count, c->boot.counts.p, (unsigned)G);
     HIPCHK(hipGetLastError());
     HIPCHK(hipMemcpyAsync(out, c->boot.counts, (size_t)count * M, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
     return TWOSD_OK;
+}
+
+extern "C" int twosd_bootstrap_counts(twosd_ctx *c, int M, uint64_t seed, uint64_t first_index, int64_t count, uint8_t *out) {
+    return bootstrap_counts_impl(c, M, seed, first_index, count, 1, out);
+}
+
+extern "C" int twosd_bootstrap_counts_vr(twosd_ctx *c, int M, uint64_t seed, uint64_t first_index, int64_t count, uint8_t *out,
+                                         const twosd_sampling *plan) {
+    int mode, G, rc;
+    if ((rc = sampling_plan(plan, "bootstrap_counts", &mode, &G))) return rc;
+    if (G == 1) return twosd_bootstrap_counts(c, M, seed, first_index, count, out);
+    if ((rc = whole_groups("bootstrap_counts", "first_index", first_index, G)) ||
+        (count > 0 && (rc = whole_groups("bootstrap_counts", "count", (unsigned long long)count, G))))
+        return rc;
+    return bootstrap_counts_impl(c, M, seed, first_index, count, G, out);
 }
 
 extern "C" int twosd_picks_keep(twosd_ctx *c, int epi, int *handle) {
@@ -629,17 +713,50 @@ static int check_epi(twosd_ctx *c, int epi, const char *what) {
     return TWOSD_OK;
 }
 
-extern "C" int twosd_reform_partial(twosd_ctx *c, int epi, int H, const int *handles, int M, uint64_t seed, uint64_t index_offset,
-                                    double total_weight, uint64_t *d_u64, double *d_f64) {
+// under a plan with group G the observations are the groups: index_offset, the epigraph's scenario
+// count and every handle's N_j must be whole groups
+static int reform_whole_groups(twosd_ctx *c, int epi, int H, const int *handles, uint64_t index_offset, int G, const char *what) {
+    if (G == 1) return TWOSD_OK;
+    int rc;
+    if ((rc = whole_groups(what, "index_offset", index_offset, G))) return rc;
+    if (c->epis[epi].count % G)
+        return fail(TWOSD_E_ARG, "%s: epigraph %d holds %d scenarios, no multiple of the sampling group %d", what, epi,
+                    c->epis[epi].count, G);
+    for (int j = 0; j < H; ++j) {
+        const PickSet &h = c->boot.picks[handles[j]];
+        if (h.n % G)
+            return fail(TWOSD_E_ARG, "%s: pick handle %d holds %d scenarios, no multiple of the sampling group %d", what, handles[j],
+                        h.n, G);
+    }
+    return TWOSD_OK;
+}
+
+static int reform_partial_impl(twosd_ctx *c, int epi, int H, const int *handles, int M, uint64_t seed, uint64_t index_offset, int G,
+                               double total_weight, uint64_t *d_u64, double *d_f64) {
     BootLayout L;
     int rc = boot_layout(c, -1, H, handles, M, "reform_partial", &L);   // a dropped handle is named before the epigraph
     if (rc || (rc = check_epi(c, epi, "reform_partial")) || (rc = boot_layout(c, epi, H, handles, M, "reform_partial", &L))) return rc;
     if (!d_u64 || !d_f64) return fail(TWOSD_E_ARG, "reform_partial: device buffers NULL");
     if (!(total_weight > 0.0) || !std::isfinite(total_weight)) return fail(TWOSD_E_ARG, "reform_partial: total_weight must be > 0");
+    if ((rc = reform_whole_groups(c, epi, H, handles, index_offset, G, "reform_partial"))) return rc;
     HIPCHK(hipSetDevice(c->device));
-    if ((rc = boot_partial_impl(c, epi, L, handles, M, seed, index_offset, total_weight, (unsigned long long *)d_u64, d_f64))) return rc;
+    if ((rc = boot_partial_impl(c, epi, L, handles, M, seed, index_offset, G, total_weight, (unsigned long long *)d_u64, d_f64)))
+        return rc;
     HIPCHK(hipStreamSynchronize(c->stream));
     return TWOSD_OK;
+}
+
+extern "C" int twosd_reform_partial(twosd_ctx *c, int epi, int H, const int *handles, int M, uint64_t seed, uint64_t index_offset,
+                                    double total_weight, uint64_t *d_u64, double *d_f64) {
+    return reform_partial_impl(c, epi, H, handles, M, seed, index_offset, 1, total_weight, d_u64, d_f64);
+}
+
+extern "C" int twosd_reform_partial_vr(twosd_ctx *c, int epi, int H, const int *handles, int M, uint64_t seed, uint64_t index_offset,
+                                       double total_weight, uint64_t *d_u64, double *d_f64, const twosd_sampling *plan) {
+    int mode, G, rc;
+    if ((rc = sampling_plan(plan, "reform_partial", &mode, &G))) return rc;
+    if (G == 1) return twosd_reform_partial(c, epi, H, handles, M, seed, index_offset, total_weight, d_u64, d_f64);
+    return reform_partial_impl(c, epi, H, handles, M, seed, index_offset, G, total_weight, d_u64, d_f64);
 }
 
 extern "C" int twosd_reform_finalize(twosd_ctx *c, int H, const int *handles, int M, double total_weight, const uint64_t *d_u64,
@@ -654,18 +771,19 @@ extern "C" int twosd_reform_finalize(twosd_ctx *c, int H, const int *handles, in
                               total_weight_out);
 }
 
-extern "C" int twosd_reform_cuts(twosd_ctx *c, int epi, int H, const int *handles, int M, uint64_t seed, uint64_t index_offset,
-                                 double *alpha, double *beta, double *weight_mark, double *total_weight) {
+static int reform_cuts_impl(twosd_ctx *c, int epi, int H, const int *handles, int M, uint64_t seed, uint64_t index_offset, int G,
+                            double *alpha, double *beta, double *weight_mark, double *total_weight) {
     BootLayout L;
     int rc = boot_layout(c, -1, H, handles, M, "reform_cuts", &L);
     if (rc || (rc = check_epi(c, epi, "reform_cuts")) || (rc = boot_layout(c, epi, H, handles, M, "reform_cuts", &L))) return rc;
     if (!alpha || (c->n1 > 0 && !beta)) return fail(TWOSD_E_ARG, "reform_cuts: alpha/beta NULL");
     const EpiDevice &E = c->epis[epi];
     if (!(E.total_weight > 0.0)) return fail(TWOSD_E_STATE, "reform_cuts: epigraph %d holds no scenario weight", epi);
+    if ((rc = reform_whole_groups(c, epi, H, handles, index_offset, G, "reform_cuts"))) return rc;
     HIPCHK(hipSetDevice(c->device));
     if ((rc = c->boot.u64.fit(L.n_u64)) || (rc = c->boot.f64.fit(L.n_f64))) return rc;
     HIPCHK(hipEventRecord(c->ev[4], c->stream));
-    if ((rc = boot_partial_impl(c, epi, L, handles, M, seed, index_offset, E.total_weight, c->boot.u64, c->boot.f64))) return rc;
+    if ((rc = boot_partial_impl(c, epi, L, handles, M, seed, index_offset, G, E.total_weight, c->boot.u64, c->boot.f64))) return rc;
     HIPCHK(hipEventRecord(c->ev[5], c->stream));
     if ((rc = boot_finalize_impl(c, L, handles, E.total_weight, c->boot.u64, c->boot.f64, alpha, beta, weight_mark, total_weight)))
         return rc;
@@ -677,6 +795,20 @@ extern "C" int twosd_reform_cuts(twosd_ctx *c, int epi, int H, const int *handle
     c->boot.ms[0] = ms1;
     c->boot.ms[1] = ms2;
     return TWOSD_OK;
+}
+
+extern "C" int twosd_reform_cuts(twosd_ctx *c, int epi, int H, const int *handles, int M, uint64_t seed, uint64_t index_offset,
+                                 double *alpha, double *beta, double *weight_mark, double *total_weight) {
+    return reform_cuts_impl(c, epi, H, handles, M, seed, index_offset, 1, alpha, beta, weight_mark, total_weight);
+}
+
+extern "C" int twosd_reform_cuts_vr(twosd_ctx *c, int epi, int H, const int *handles, int M, uint64_t seed, uint64_t index_offset,
+                                    double *alpha, double *beta, double *weight_mark, double *total_weight,
+                                    const twosd_sampling *plan) {
+    int mode, G, rc;
+    if ((rc = sampling_plan(plan, "reform_cuts", &mode, &G))) return rc;
+    if (G == 1) return twosd_reform_cuts(c, epi, H, handles, M, seed, index_offset, alpha, beta, weight_mark, total_weight);
+    return reform_cuts_impl(c, epi, H, handles, M, seed, index_offset, G, alpha, beta, weight_mark, total_weight);
 }
 
 extern "C" int twosd_reform_last_ms(twosd_ctx *c, double *ms2) {

@@ -287,4 +287,8 @@ void cut_truncate_pk(twosd_ctx *c, int size);   // V truncated to size: PK rows 
 // brought up to date with the vertex set)
 const int *cut_last_arg(twosd_ctx *c);
 int cut_pk_current(twosd_ctx *c, const double **PK, int *k4);
+// sampling plans (api.hip): a caller's plan -> (mode, G), NULL meaning i.i.d.; and `what` = value
+// must be a whole number of groups.  Both fail with TWOSD_E_ARG and the offending value.
+int sampling_plan(const twosd_sampling *plan, const char *who, int *mode, int *G);
+int whole_groups(const char *who, const char *what, unsigned long long value, int G);
 }  // namespace twosd

@@ -239,6 +239,41 @@ def build_cut_sharded(ctx, epi, x, total_weight, tie_rel, device, verify=True, e
     return ex.build_cut(epi, x, total_weight, tie_rel, verify=verify, extra=extra)
 
 
+def allreduce_reform_partials(u64: torch.Tensor, f64: torch.Tensor):
+    """Sum the ranks' reform_partial buffers in place: u64 (int64 storage of the uint64 totals, W_jb
+    and per-vertex weights -- every sum stays below 2^62, so the int64 sum is the uint64 sum,
+    exact) and f64 (the unnormalised S_e).  No collective on a single rank.  Works on CPU tensors
+    (gloo) as on device tensors (RCCL)."""
+    if u64.dtype != torch.int64 or f64.dtype != torch.float64:
+        raise TypeError("allreduce_reform_partials: u64 must be int64 storage and f64 float64")
+    if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
+        dist.all_reduce(u64, op=dist.ReduceOp.SUM)
+        dist.all_reduce(f64, op=dist.ReduceOp.SUM)
+    return u64, f64
+
+
+def reform_cuts_sharded(epi, cuts, M, seed, index_offset, total_weight, sampling=None, device=None):
+    """twosd.reform_cuts over the scenarios of every rank: each rank runs reform_partial over its own
+    scenarios (index_offset = the global index of its first one; its handles mirror the other
+    ranks', vertex sets identical; total_weight = the epigraph's GLOBAL total scenario weight, the
+    same on every rank), the partials are all-reduced (allreduce_reform_partials) and every rank
+    finalizes: the same ReformedCuts on every rank.  sampling: the epigraph's Sampling plan; every
+    rank then holds whole groups (group_shard_ranges shards so).  device: the torch device of the
+    context's GPU (default: the current one).  One rank: no collective, and the result is
+    reform_cuts' bit for bit."""
+    from . import twosd
+    ctx = epi.ctx
+    n_u64, n_f64 = twosd.reform_partial_len(ctx, cuts, M)
+    device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+    u64 = torch.zeros(n_u64, dtype=torch.int64, device=device)
+    f64 = torch.zeros(n_f64, dtype=torch.float64, device=device)
+    torch.cuda.synchronize(device)   # torch's fill must land before the library's stream touches the buffers
+    twosd.reform_partial(epi, cuts, M, seed, index_offset, total_weight, u64.data_ptr(), f64.data_ptr(), sampling=sampling)
+    allreduce_reform_partials(u64, f64)
+    torch.cuda.synchronize(device)   # the collective runs on torch / RCCL streams, finalize on the library's
+    return twosd.reform_finalize(ctx, cuts, M, total_weight, u64.data_ptr(), f64.data_ptr())
+
+
 def _vertex_check_row(ctx) -> np.ndarray:
     """(|V|, the fingerprint's four 16-bit pieces) as fp64: integers whose squares and sums over
     any rank count stay exact."""

@@ -375,18 +375,27 @@ def sd_iteration(cell: sdCell, scenario_list, update_incumbent_cut=True, quad_sc
     cell.x_candidate = cell.solve_master()
 
 
-def sd_run(cell: sdCell, next_scenarios, max_iter, min_iter=0, check_every=10, stop=None, **iteration_args):
+def sd_run(cell: sdCell, next_scenarios, max_iter, min_iter=0, check_every=10, stop=None, sampling=None, stop_args=None,
+           **iteration_args):
     """The SD loop with its in-sample stopping rule (the reference has none: its readme lists
     "Need to implement stopping criteria", plugin/stopping_rule.jl is empty).  Runs
     sd_iteration(cell, next_scenarios(it), keep_picks=True) for it = 0, 1, ... and, every
     check_every iterations once min_iter have run, calls stop(cell) -- default
     stopping.bootstrap_gap_test -- ending when its result has .passed, or after max_iter.
+    sampling: the twosd.Sampling plan next_scenarios draws with (one, or a list per epigraph; every
+    iteration then adds whole groups, a (G, k) array per epigraph): the default stop resamples whole
+    groups (bootstrap_gap_test's sampling=).  stop_args: further keyword arguments of the default
+    stop (M, seed, eps, frac, index_offsets).  A stop of the caller's is called as stop(cell).
     Returns (iterations run, the last test result or None)."""
     if check_every < 1:
         raise ValueError("check_every must be at least 1")
     if stop is None:
         from . import stopping
-        stop = stopping.bootstrap_gap_test
+        if sampling is None and not stop_args:
+            stop = stopping.bootstrap_gap_test
+        else:
+            def stop(c):
+                return stopping.bootstrap_gap_test(c, sampling=sampling, **(stop_args or {}))
     result = None
     it = 0
     while it < max_iter:

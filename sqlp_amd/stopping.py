@@ -8,9 +8,11 @@ observations, re-form every cut the master holds from the argmax picks it was bu
 the re-formed upper estimate at the incumbent with the value of the re-formed master.  Stop when
 nearly all replicates show a small gap.
 
-The resampling is a Poisson(1) bootstrap (independent counts per scenario and replicate, every
+The resampling is a Poisson(1) bootstrap (independent counts per observation and replicate, every
 sum normalised by the replicate's own total weight), not the multinomial resample of the
-literature: DESIGN.md §9.
+literature: DESIGN.md §9.  The observations of an i.i.d. epigraph are its scenarios; those of an
+epigraph filled from a variance-reduced stream (twosd.Sampling) are its groups, and `sampling=`
+makes the bootstrap resample whole groups.
 """
 from __future__ import annotations
 
@@ -46,7 +48,17 @@ def _epigraph_cuts(epi, e):
     return cuts
 
 
-def bootstrap_gap_test(cell, M=32, seed=0, eps=1e-3, frac=0.95, index_offsets=None, reform=None) -> GapTest:
+def _plans(sampling, E):
+    """One plan (or None) per epigraph from bootstrap_gap_test's sampling= argument."""
+    if sampling is None or isinstance(sampling, twosd.Sampling):
+        return [sampling] * E
+    plans = list(sampling)
+    if len(plans) != E:
+        raise ValueError(f"bootstrap_gap_test: sampling lists {len(plans)} plans for {E} epigraphs")
+    return plans
+
+
+def bootstrap_gap_test(cell, M=32, seed=0, eps=1e-3, frac=0.95, index_offsets=None, reform=None, sampling=None) -> GapTest:
     """The bootstrap gap test at the cell's incumbent x^ = cell.x_incumbent.
 
     Every cut of every epigraph of the cell (epi.cuts and the incumbent cut) must carry picks.
@@ -58,18 +70,22 @@ def bootstrap_gap_test(cell, M=32, seed=0, eps=1e-3, frac=0.95, index_offsets=No
     fraction = #{b >= 1 : gap_b <= eps (1 + |U_0|)} / M and passed = fraction >= frac.  eps and
     frac are parameters (defaults: the prox schedule's tolerance 1e-3, and 0.95), not acceptance
     thresholds of the library.  Epigraph e draws its counts from the stream seed + e, its first
-    scenario at global index index_offsets[e] (default 0).  reform(epi, cuts, M, seed, index_offset)
-    replaces twosd.reform_cuts (tests)."""
+    scenario at global index index_offsets[e] (default 0).  sampling: the twosd.Sampling plan the
+    epigraphs were filled with, or a list with one plan (or None) per epigraph: the replicates of
+    such an epigraph resample whole groups (reform is then called with the keyword sampling=).
+    reform(epi, cuts, M, seed, index_offset) replaces twosd.reform_cuts (tests)."""
     if M < 1:
         raise ValueError("bootstrap_gap_test: M must be at least 1")
     reform = twosd.reform_cuts if reform is None else reform
     x = np.asarray(cell.x_incumbent, dtype=np.float64)
     E = len(cell.epi)
     offs = [0] * E if index_offsets is None else list(index_offsets)
+    plans = _plans(sampling, E)
     per_epi = []
     for e, epi in enumerate(cell.epi):
         cuts = _epigraph_cuts(epi, e)
-        per_epi.append((epi, len(epi.cuts), epi.incumbent_cut is not None, reform(epi, cuts, M, seed + e, offs[e])))
+        kw = {} if plans[e] is None else {"sampling": plans[e]}
+        per_epi.append((epi, len(epi.cuts), epi.incumbent_cut is not None, reform(epi, cuts, M, seed + e, offs[e], **kw)))
     cx = cell.objf_original(x)
     U = np.zeros(M + 1)
     L = np.zeros(M + 1)

@@ -975,12 +975,18 @@ def bootstrap_count_of_word(u: int) -> int:
     return int(_lib.load().twosd_bootstrap_count_of_word(C.c_uint32(int(u))))
 
 
-def bootstrap_counts(ctx: SDContext, M, seed, first_index, count) -> np.ndarray:
+def bootstrap_counts(ctx: SDContext, M, seed, first_index, count, sampling=None) -> np.ndarray:
     """The device draw of the replicate counts of scenarios [first_index, first_index + count):
-    uint8 (count, M)."""
+    uint8 (count, M).  sampling: a Sampling plan (twosd_bootstrap_counts_vr): whole groups are
+    resampled, scenario g carries the count of group g // G; first_index and count are whole groups."""
     out = np.zeros((int(count), int(M)), dtype=np.uint8)
-    check(ctx.lib.twosd_bootstrap_counts(ctx.h, int(M), C.c_uint64(seed), C.c_uint64(first_index), C.c_int64(count),
-                                         ptr(out)))
+    if sampling is None:
+        check(ctx.lib.twosd_bootstrap_counts(ctx.h, int(M), C.c_uint64(seed), C.c_uint64(first_index), C.c_int64(count),
+                                             ptr(out)))
+    else:
+        plan, _ = _plan(sampling)
+        check(ctx.lib.twosd_bootstrap_counts_vr(ctx.h, int(M), C.c_uint64(seed), C.c_uint64(first_index), C.c_int64(count),
+                                                ptr(out), C.byref(plan)))
     return out
 
 
@@ -1006,10 +1012,12 @@ def _handles_of(cuts):
     return np.ascontiguousarray(hs, dtype=np.int32)
 
 
-def reform_cuts(epi: sdEpigraph, cuts, M, seed, index_offset=0) -> ReformedCuts:
+def reform_cuts(epi: sdEpigraph, cuts, M, seed, index_offset=0, sampling=None) -> ReformedCuts:
     """twosd_reform_cuts: every cut of `cuts` (sdCut with picks, or pick handles) re-formed from its
     picks under the identity weights (row 0) and M Poisson(1) bootstrap replicates of the scenario
-    weights (seed; index_offset = the global index of the epigraph's first scenario)."""
+    weights (seed; index_offset = the global index of the epigraph's first scenario).  sampling: the
+    Sampling plan the epigraph was filled with (twosd_reform_cuts_vr): the replicates resample whole
+    groups; index_offset, the epigraph's scenario count and every cut's are then whole groups."""
     ctx = epi.ctx
     hs = _handles_of(cuts)
     H, B = len(hs), int(M) + 1
@@ -1017,8 +1025,13 @@ def reform_cuts(epi: sdEpigraph, cuts, M, seed, index_offset=0) -> ReformedCuts:
     beta = np.zeros((B, H, ctx.n1))
     wm = np.zeros((B, H))
     tw = np.zeros(B)
-    check(ctx.lib.twosd_reform_cuts(ctx.h, epi.index, H, ptr(hs), int(M), C.c_uint64(seed), C.c_uint64(index_offset),
-                                    ptr(alpha), ptr(beta), ptr(wm), ptr(tw)))
+    if sampling is None:
+        check(ctx.lib.twosd_reform_cuts(ctx.h, epi.index, H, ptr(hs), int(M), C.c_uint64(seed), C.c_uint64(index_offset),
+                                        ptr(alpha), ptr(beta), ptr(wm), ptr(tw)))
+    else:
+        plan, _ = _plan(sampling)
+        check(ctx.lib.twosd_reform_cuts_vr(ctx.h, epi.index, H, ptr(hs), int(M), C.c_uint64(seed), C.c_uint64(index_offset),
+                                           ptr(alpha), ptr(beta), ptr(wm), ptr(tw), C.byref(plan)))
     return ReformedCuts(alpha, beta, wm, tw)
 
 
@@ -1036,14 +1049,21 @@ def reform_partial_len(ctx: SDContext, cuts, M):
     return a.value, b.value
 
 
-def reform_partial(epi: sdEpigraph, cuts, M, seed, index_offset, total_weight, d_u64_ptr, d_f64_ptr):
+def reform_partial(epi: sdEpigraph, cuts, M, seed, index_offset, total_weight, d_u64_ptr, d_f64_ptr, sampling=None):
     """This rank's part of reform_cuts into caller device buffers (reform_partial_len entries);
-    total_weight: the global total scenario weight, the same on every rank."""
+    total_weight: the global total scenario weight, the same on every rank.  sampling: as
+    reform_cuts (twosd_reform_partial_vr); the rank then holds whole groups."""
     ctx = epi.ctx
     hs = _handles_of(cuts)
-    check(ctx.lib.twosd_reform_partial(ctx.h, epi.index, len(hs), ptr(hs), int(M), C.c_uint64(seed),
-                                       C.c_uint64(index_offset), float(total_weight), C.c_void_p(d_u64_ptr),
-                                       C.c_void_p(d_f64_ptr)))
+    if sampling is None:
+        check(ctx.lib.twosd_reform_partial(ctx.h, epi.index, len(hs), ptr(hs), int(M), C.c_uint64(seed),
+                                           C.c_uint64(index_offset), float(total_weight), C.c_void_p(d_u64_ptr),
+                                           C.c_void_p(d_f64_ptr)))
+    else:
+        plan, _ = _plan(sampling)
+        check(ctx.lib.twosd_reform_partial_vr(ctx.h, epi.index, len(hs), ptr(hs), int(M), C.c_uint64(seed),
+                                              C.c_uint64(index_offset), float(total_weight), C.c_void_p(d_u64_ptr),
+                                              C.c_void_p(d_f64_ptr), C.byref(plan)))
 
 
 def reform_finalize(ctx: SDContext, cuts, M, total_weight, d_u64_ptr, d_f64_ptr) -> ReformedCuts:

@@ -11,6 +11,11 @@ H N (8 k + 12) -- the deltas, the weight and the pick of every scenario, once pe
 kernel re-reads the deltas once per group of 16 replicates; the groups of a chunk are adjacent
 blocks, so the re-reads are meant to hit L2 / the Infinity Cache).
 
+--sampling lists sampling plans (antithetic, lhsS) whose grouped re-formation (reform_cuts with
+sampling=: whole groups resampled) is timed on the same epigraph and handles beside the i.i.d. call,
+the same way (warm-up, best of three, every repeat kept); the scenario count must be whole groups of
+each.  The epigraph's own stream stays the i.i.d. one: the work does not depend on the values.
+
 Prints one JSON line.  --out also writes it to a file.
 """
 import argparse
@@ -27,14 +32,29 @@ sys.path.insert(0, ROOT)
 HBM_PEAK_GBS = 8000.0     # MI355X HBM3E peak
 
 
-def best_of(f, reps=3):
+def runs_of(f, reps=3):
     f()                   # warm-up
     ts = []
     for _ in range(reps):
         t = time.perf_counter()
         f()
-        ts.append(time.perf_counter() - t)
-    return min(ts) * 1e3
+        ts.append((time.perf_counter() - t) * 1e3)
+    return ts
+
+
+def best_of(f, reps=3):
+    return min(runs_of(f, reps))
+
+
+def plan_of(name):
+    from sqlp_amd import twosd
+    if name == "iid":
+        return None
+    if name == "antithetic":
+        return twosd.Sampling.antithetic()
+    if name.startswith("lhs") and name[3:].isdigit():
+        return twosd.Sampling.lhs(int(name[3:]))
+    raise SystemExit(f"--sampling: unknown plan {name!r} (iid, antithetic, lhsS)")
 
 
 def main():
@@ -45,6 +65,7 @@ def main():
     ap.add_argument("--handles", type=int, default=20)
     ap.add_argument("--replicates", type=int, default=32)
     ap.add_argument("--seed", type=int, default=20250219)
+    ap.add_argument("--sampling", default="", help="comma-separated plans to time beside the i.i.d. call: antithetic, lhs64, ...")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     import torch
@@ -59,6 +80,10 @@ def main():
     ctx.compute_basis(x, smps.mean_values(sto))
     ctx.set_distributions(sto)
     N, H, M = args.scenarios, args.handles, args.replicates
+    plans = {p: plan_of(p) for p in args.sampling.split(",") if p}
+    for p, plan in plans.items():
+        if plan is not None and N % plan.group:
+            raise SystemExit(f"--sampling {p}: {N} scenarios are no whole number of groups of {plan.group}")
     epi = twosd.sdEpigraph(ctx, 1.0, 0.0)
     twosd.add_sampled_scenarios(epi, N, args.seed)
     V = twosd.sdDualVertexSet(ctx)
@@ -75,20 +100,28 @@ def main():
     cut_ms = best_of(lambda: twosd.build_sasa_cut(epi, x, V, tie_rel=1e-12))
     cut_kernel_ms = float(ctx.timings_us()[2] + ctx.timings_us()[3]) / 1e3
     one_ms = best_of(lambda: twosd.reform_cuts(epi, cuts[:1], M, args.seed))
-    all_ms = best_of(lambda: twosd.reform_cuts(epi, cuts, M, args.seed))
+    all_runs = runs_of(lambda: twosd.reform_cuts(epi, cuts, M, args.seed))
+    all_ms = min(all_runs)
     id_ms = best_of(lambda: twosd.reform_cuts(epi, cuts, 0, args.seed))
     R = twosd.reform_cuts(epi, cuts, M, args.seed)
     dev_ms = [float(v) for v in twosd.reform_last_ms(ctx)]
     err = max(abs(R.alpha[0, j] - c.alpha) / (1 + abs(c.alpha)) for j, c in enumerate(cuts))
+    grouped = {}
+    for p, plan in plans.items():
+        runs = runs_of(lambda: twosd.reform_cuts(epi, cuts, M, args.seed, sampling=plan))
+        grouped[p] = {"reform_ms": min(runs), "reform_ms_runs": runs, "reform_device_ms": [float(v) for v in twosd.reform_last_ms(ctx)],
+                      "over_iid": min(runs) / all_ms}
     k = ctx.k
     model = H * N * (8 * k + 12)
     out = {"instance": name, "scenarios": N, "vertices": len(V), "k": k, "handles": H, "replicates": M,
            "build_cut_ms": cut_ms, "build_cut_kernels_ms": cut_kernel_ms,
-           "reform_ms": all_ms, "reform_device_ms": dev_ms, "reform_ms_per_handle": all_ms / H, "reform_one_handle_ms": one_ms,
+           "reform_ms": all_ms, "reform_ms_runs": all_runs, "reform_device_ms": dev_ms, "reform_ms_per_handle": all_ms / H, "reform_one_handle_ms": one_ms,
            "reform_identity_only_ms": id_ms,
            "model_bytes": model, "achieved_GBs": model / (all_ms * 1e-3) / 1e9,
            "fraction_of_hbm_peak": model / (all_ms * 1e-3) / 1e9 / HBM_PEAK_GBS,
            "handle_over_cut": (all_ms / H) / cut_ms, "identity_row_max_rel_err": err}
+    if grouped:
+        out["sampling"] = grouped
     line = json.dumps(out)
     print(line)
     if args.out:
