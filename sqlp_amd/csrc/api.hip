@@ -34,12 +34,6 @@ int twosd::fail(int code, const char *fmt, ...) {
     return code;
 }
 
-#define HIPCHK(expr)                                                                            \
-    do {                                                                                        \
-        hipError_t _e = (expr);                                                                 \
-        if (_e != hipSuccess) return fail(TWOSD_E_DEVICE, "%s: %s", #expr, hipGetErrorString(_e)); \
-    } while (0)
-
 extern "C" const char *twosd_last_error(void) { return g_err.c_str(); }
 extern "C" const char *twosd_version(void) { return "twosd-mi355x 0.1 (gfx950)"; }
 
@@ -89,7 +83,7 @@ static void build_ell(int S, F colf, std::vector<int> &slot, std::vector<int> &i
 
 // the two-level candidate lists (device, or staged for the next selection) refer to pool
 // indices: every change of the pool drops them
-static void reset_candidates(twosd_ctx *c) {
+void twosd::reset_candidates(twosd_ctx *c) {
     c->pool_l1 = c->pool_ncand = 0;
     c->cand_pending = false;
     std::vector<int>().swap(c->cand_p1);
@@ -98,7 +92,7 @@ static void reset_candidates(twosd_ctx *c) {
 
 // the pool no longer matches the device arrays (a failed build or head read-back): keep only
 // the primary basis (a host basis) and refuse solves until a basis is installed again
-static int drop_pool(twosd_ctx *c, int code) {
+int twosd::drop_pool(twosd_ctx *c, int code) {
     if (c->pool.size() > 1) c->pool.resize(1);
     c->has_basis = false;
     c->prep_valid = false;
@@ -140,25 +134,9 @@ static int materialize_heads(twosd_ctx *c) {
     return TWOSD_OK;
 }
 
-// f(i) for i in [0, n) on up to 16 host threads (per-basis pool preparation: independent work)
-template <typename F>
-static void parallel_for(int n, F f) {
-    const int nth = (int)std::max(1u, std::min(16u, std::thread::hardware_concurrency()));
-    if (n < 64 || nth == 1) {
-        for (int i = 0; i < n; ++i) f(i);
-        return;
-    }
-    std::vector<std::thread> th;
-    for (int t = 0; t < nth; ++t)
-        th.emplace_back([&, t]() {
-            for (int i = t; i < n; i += nth) f(i);
-        });
-    for (auto &t : th) t.join();
-}
-
 // device selection-stream outputs of a pool of P bases with `records` records (prepare_x
 // writes them per x)
-static int reserve_selection(twosd_ctx *c, int P, int records) {
+int twosd::reserve_selection(twosd_ctx *c, int P, int records) {
     int rc;
     if ((rc = c->d_sel_code.fit(2 * (size_t)std::max(records, 1)))) return rc;   // (code, float bits) pairs
     if ((rc = c->d_sel_end.reserve((size_t)P)) || (rc = c->d_sel_cinf.reserve((size_t)P))) return rc;
@@ -521,7 +499,7 @@ static int make_pool_basis(twosd_ctx *c, const std::vector<int> &head, PoolBasis
 }
 
 // pi0 = c_B' B^{-1} from the CSR rows (rows ascending)
-static void pi0_from_rows(const twosd_ctx *c, PoolBasis &B) {
+void twosd::pi0_from_rows(const twosd_ctx *c, PoolBasis &B) {
     const HostLP &L = c->L;
     const int m = L.m, n = L.n;
     B.pi0.assign(m, 0.0);
@@ -535,7 +513,7 @@ static void pi0_from_rows(const twosd_ctx *c, PoolBasis &B) {
 
 // host CSR rows and pi0 of the bases a device refresh built (dev_only), read back from the
 // pool arrays: upload_pool, prepare_elements and the host compose work on the host forms
-static int ensure_host_pool(twosd_ctx *c) {
+int twosd::ensure_host_pool(twosd_ctx *c) {
     if (int rc = materialize_heads(c)) return rc;
     const int P = (int)c->pool.size(), MP = c->MP, m = c->L.m;
     int last = -1;
@@ -572,7 +550,7 @@ static int ensure_host_pool(twosd_ctx *c) {
 // the leading MP / 64 / 64C entries are the primary basis): hb0 (MP), basic0 (64),
 // d0 (64C), B^{-1} columns as CSC (bcp absolute into the concatenated bci/bcv),
 // B^{-1} rows as CSR (brptr absolute into the concatenated brcol/brval).
-static int upload_pool(twosd_ctx *c) {
+int twosd::upload_pool(twosd_ctx *c) {
     const auto t_up0 = std::chrono::steady_clock::now();
     if (int rc0 = ensure_host_pool(c)) return rc0;
     const HostLP &L = c->L;
@@ -589,9 +567,9 @@ static int upload_pool(twosd_ctx *c) {
     if (ro[P] > INT32_MAX) return fail(TWOSD_E_UNSUPPORTED, "basis pool too large (> 2^31 entries)");
     const size_t nz = std::max<size_t>(ro[P], 1);
     std::vector<int> rp_all((size_t)P * (MP + 1)), cp_all((size_t)P * (MP + 1));
-    int *rc_all = c->stage[0].reserve<int>(nz), *ci_all = c->stage[1].reserve<int>(nz);
-    double *rv_all = c->stage[2].reserve<double>(nz), *cv_all = c->stage[3].reserve<double>(nz);
-    double *d0_all = c->stage[4].reserve<double>((size_t)P * 64 * std::max(c->CH, 1));
+    int *rc_all = c->stage[STG_POOL_RCOL].reserve<int>(nz), *ci_all = c->stage[STG_POOL_CROW].reserve<int>(nz);
+    double *rv_all = c->stage[STG_POOL_RVAL].reserve<double>(nz), *cv_all = c->stage[STG_POOL_CVAL].reserve<double>(nz);
+    double *d0_all = c->stage[STG_POOL_D0].reserve<double>((size_t)P * 64 * std::max(c->CH, 1));
     if (!rc_all || !ci_all || !rv_all || !cv_all || !d0_all) return fail(TWOSD_E_DEVICE, "pool upload: pinned staging allocation failed");
     parallel_for(P, [&](int p) {
         const PoolBasis &B = c->pool[p];
@@ -659,7 +637,7 @@ static int install_basis(twosd_ctx *c, const std::vector<int> &head) {
     c->pool.clear();
     c->sel_lo.clear();
     c->sel_hi.clear();
-    c->box_epi = -1;
+    c->sel_box = BoxCache{};
     c->pool.push_back(std::move(pb));
     if ((rc = upload_pool(c))) return rc;
     c->has_basis = true;
@@ -748,6 +726,24 @@ static int64_t pivots_of_last_lp(twosd_ctx *c, int N) {
     return sum;
 }
 
+int twosd::training_box(twosd_ctx *c, const EpiDevice &E, int epi, int first, int count, std::vector<double> &lo,
+                        std::vector<double> &hi, BoxCache *cache) {
+    const int k = c->k;
+    const BoxCache range{epi, first, count, E.count};
+    if (k <= 0 || (cache && *cache == range)) return TWOSD_OK;
+    std::vector<double> dv((size_t)count * k);
+    HIPCHK(hipMemcpy(dv.data(), E.d_dv + (size_t)first * k, sizeof(double) * dv.size(), hipMemcpyDeviceToHost));
+    lo.assign(k, INFINITY);
+    hi.assign(k, -INFINITY);
+    for (int s = 0; s < count; ++s)
+        for (int e = 0; e < k; ++e) {
+            lo[e] = std::min(lo[e], dv[(size_t)s * k + e]);
+            hi[e] = std::max(hi[e], dv[(size_t)s * k + e]);
+        }
+    if (cache) *cache = range;
+    return TWOSD_OK;
+}
+
 // Grow the pool from training scenarios [first, first + count) of epigraph epi at x.  The
 // first half harvests: solved from the current pool, its optimal bases are added in order
 // of decreasing frequency (ties: first occurrence) up to max_pool bases.  The second half
@@ -765,16 +761,8 @@ extern "C" int twosd_pool_build(twosd_ctx *c, int epi, const double *x, int firs
     const int m = c->L.m;
     const int nh = count / 2, nv = count - nh;
     if (count > 0 && c->k > 0) {   // training box of the deltas (selection row pruning)
-        std::vector<double> dv((size_t)count * c->k);
-        HIPCHK(hipMemcpy(dv.data(), E.d_dv + (size_t)first * c->k, sizeof(double) * dv.size(), hipMemcpyDeviceToHost));
-        c->box_epi = -1;   // the refresh's cached box no longer applies
-        c->sel_lo.assign(c->k, INFINITY);
-        c->sel_hi.assign(c->k, -INFINITY);
-        for (int s = 0; s < count; ++s)
-            for (int e = 0; e < c->k; ++e) {
-                c->sel_lo[e] = std::min(c->sel_lo[e], dv[(size_t)s * c->k + e]);
-                c->sel_hi[e] = std::max(c->sel_hi[e], dv[(size_t)s * c->k + e]);
-            }
+        if (int rc = training_box(c, E, epi, first, count, c->sel_lo, c->sel_hi, nullptr)) return rc;
+        c->sel_box = BoxCache{};   // the refresh's cached box no longer applies
         c->prep_valid = false;
     }
     if (nh > 0 && (int)c->pool.size() < max_pool) {
@@ -814,18 +802,12 @@ extern "C" int twosd_pool_build(twosd_ctx *c, int epi, const double *x, int firs
         const size_t want = std::min(order.size(), (size_t)max_pool - old_size);
         std::vector<PoolBasis> cand(want);
         std::vector<int> ok(want, 0);
-        const unsigned nth = std::max(1u, std::min(16u, std::thread::hardware_concurrency()));
-        std::vector<std::thread> th;
-        for (unsigned t = 0; t < nth; ++t)
-            th.emplace_back([&, t]() {
-                for (size_t a = t; a < want; a += nth) {
-                    const int s = order[a].second;
-                    std::vector<int> head(heads.begin() + (size_t)s * m, heads.begin() + (size_t)(s + 1) * m);
-                    ok[a] = compute_pool_basis(c, head, cand[a]) == nullptr;
-                    std::vector<double>().swap(cand[a].Binv);   // sparse forms kept; dense m x m only for the primary
-                }
-            });
-        for (auto &t : th) t.join();
+        parallel_for((int)want, [&](int a) {   // threaded at any size: a dense m x m inverse each
+            const int s = order[a].second;
+            std::vector<int> head(heads.begin() + (size_t)s * m, heads.begin() + (size_t)(s + 1) * m);
+            ok[a] = compute_pool_basis(c, head, cand[a]) == nullptr;
+            std::vector<double>().swap(cand[a].Binv);   // sparse forms kept; dense m x m only for the primary
+        }, 1);
         for (size_t a = 0; a < want; ++a)
             if (ok[a]) c->pool.push_back(std::move(cand[a]));
         if (c->pool.size() > old_size) {
@@ -846,724 +828,6 @@ extern "C" int twosd_pool_build(twosd_ctx *c, int epi, const double *x, int firs
 }
 
 static int select_pool(twosd_ctx *c, const double *d_dv, int N, int *d_pick, int npool_override);
-static int prepare_elements(twosd_ctx *c);
-
-// ---- pool refresh at x: the pool's bases are optimal near the x they were harvested at
-// (storm: 8.9 pivots per scenario at the training x, 28-67 at SD candidates 25-37 % away), so a
-// new x gets a pool of its own.  B^{-1} of a harvested basis is composed from its start basis
-// and the eta file of its solve, B^{-1} = E_K..E_1 B_pb^{-1} (sparse row merges), so no
-// refactorisation: the cost is the training solves plus O(K nnz) host work per basis.
-
-// pi0 = c_B' B^{-1} from the composed rows, then the checks of host_basis.cpp; nullptr if the
-// basis is usable
-static const char *finish_composed(const twosd_ctx *c, PoolBasis &B) {
-    const HostLP &L = c->L;
-    pi0_from_rows(c, B);
-    if (sparse_dual_infeasibility(L, B.head, B.pi0) > 1e-7) return "composed basis is not dual feasible";
-    if (sparse_basis_residual(L, B.head, B.rptr, B.rcol, B.rval, 4) > 1e-8) return "composed B^{-1} inconsistent";
-    return nullptr;
-}
-
-// Device build of the refreshed pool (pool_gpu.hip) from the eta files and heads of the
-// training solves (rows = training scenarios in c->d_eo_* / c->d_head_out; the representatives
-// in c->d_refresh_sel).  Two phases:
-//   pg_compute   sources a = 0 (primary), a = 1..R (eta-file row d_refresh_sel[a - 1]) composed
-//                column by column into an intermediate CSC and checked (d_pg_* arrays);
-//   pg_assemble  the sources listed in `order` that passed the checks become pool[0..P), in
-//                that order: the arrays upload_pool + prepare_elements would produce.
-// The single-GPU refresh runs both on one source table; the distributed refresh
-// (twosd_refresh_*) runs pg_compute on each rank's own representatives and pg_assemble on the
-// table all ranks gathered.
-
-// workspace + PgArgs of a compute over nsrc sources (the template and start-pool fields)
-static int pg_args(twosd_ctx *c, int nsrc, PgArgs &A) {
-    const HostLP &L = c->L;
-    const int m = L.m;
-    int rc;
-    if ((rc = c->d_pg_pos.reserve((size_t)std::max(c->k, 1))) || (rc = c->d_pg_amax.reserve((size_t)nsrc)) ||
-        (rc = c->d_pg_cnt.reserve((size_t)4 * nsrc * m)) || (rc = c->d_pg_tot.reserve((size_t)5 * nsrc)) ||
-        (rc = c->d_pg_valid.reserve((size_t)nsrc)) || (rc = c->d_pg_head0.reserve((size_t)m)) ||
-        (rc = c->d_pg_d0p.reserve((size_t)64 * c->CH)) || (rc = c->d_pg_ioff.reserve((size_t)nsrc)))
-        return rc;
-    HIPCHK(hipMemcpyAsync(c->d_pg_head0, c->head0.data(), sizeof(int) * m, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(hipMemcpyAsync(c->d_pg_d0p, c->d_d0, sizeof(double) * 64 * c->CH, hipMemcpyDeviceToDevice, c->stream));
-    if (c->k) HIPCHK(hipMemcpyAsync(c->d_pg_pos, c->pos_row.data(), sizeof(int) * c->k, hipMemcpyHostToDevice, c->stream));
-    A = PgArgs{};
-    A.m = m; A.n = L.n; A.MP = c->MP; A.CH = c->CH; A.R9 = c->R; A.k = c->k; A.kmax = c->eo_kmax;
-    A.npool_old = (int)c->pool.size();
-    A.colptr = c->d_colptr; A.rowidx = c->d_rowidx; A.val = c->d_val; A.q = c->d_q; A.btype = c->d_btype;
-    A.pos_row = c->d_pg_pos;
-    A.bcp0 = c->d_bcp; A.bci0 = c->d_bci; A.bcv0 = c->d_bcv;
-    A.eo_pb = c->d_eo_pb; A.eo_K = c->d_eo_K; A.eo_off = c->d_eo_off; A.eo_etap = c->d_eo_etap;
-    A.eo_etaoff = c->d_eo_etaoff; A.eo_eidx = c->d_eo_eidx; A.eo_evals = c->d_eo_evals;
-    A.head0 = c->d_pg_head0; A.heads = c->d_head_out; A.src_row = c->d_refresh_sel;
-    A.a0 = 0;
-    A.amax = c->d_pg_amax;
-    A.nzc = c->d_pg_cnt; A.keptc = c->d_pg_cnt + (size_t)nsrc * m;
-    A.rowcnt = c->d_pg_cnt + (size_t)2 * nsrc * m; A.erowcnt = c->d_pg_cnt + (size_t)3 * nsrc * m;
-    A.tot = c->d_pg_tot; A.nztot = c->d_pg_tot + (size_t)4 * nsrc; A.valid = c->d_pg_valid;
-    return TWOSD_OK;
-}
-
-// compute phase over sources [0, nsrc): FTRAN passes + counts and checks; the per-source
-// totals (4 each), nonzero counts and validity are read back into h_tot / h_nz / h_valid
-// (pinned staging), the intermediate offsets prefixed into A.inter_off
-static int pg_compute(twosd_ctx *c, int nsrc, PgArgs &A, int **h_tot, int **h_valid, long long *inz_out, bool dbg) {
-    int rc;
-    if ((rc = pg_args(c, nsrc, A))) return rc;
-    // the first pass keeps each source's nonzeros (up to sc_cap entries, sized from the last
-    // build's largest source; at most 1.5 GiB in all) for pg_gather_kernel: one FTRAN per
-    // column instead of two; a source past sc_cap runs the second FTRAN pass
-    const int m = c->L.m;
-    long long cap = c->pg_sc_cap > 0 ? c->pg_sc_cap : std::min<long long>((long long)m * m, 16384);
-    if (getenv("TWOSD_PG_NOSCRATCH")) cap = 0;   // A/B knob: two FTRAN passes
-    if (const char *e = getenv("TWOSD_PG_SCCAP")) cap = atoll(e);   // test hook: sources past it take pass 1
-    cap = std::min(cap, ((3LL << 29) / 12) / std::max(nsrc, 1));
-    if (cap > 0 && ((rc = c->d_pg_scrow.reserve((size_t)nsrc * cap)) || (rc = c->d_pg_scval.reserve((size_t)nsrc * cap)) ||
-                    (rc = c->d_pg_scoff.reserve((size_t)nsrc * m))))
-        return rc;
-    A.sc_cap = cap; A.sc_row = c->d_pg_scrow; A.sc_val = c->d_pg_scval; A.sc_off = c->d_pg_scoff;
-    HIPCHK(pg_launch_ftran(A, 0, nsrc, c->stream));
-    int *h_nz = c->stage[11].reserve<int>((size_t)nsrc);
-    long long *h_ioff = c->stage[12].reserve<long long>((size_t)nsrc);
-    if (!h_nz || !h_ioff) return fail(TWOSD_E_DEVICE, "pool refresh: pinned staging allocation failed");
-    HIPCHK(hipMemcpyAsync(h_nz, A.nztot, sizeof(int) * nsrc, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
-    long long inz = 0, nzmax = 0;
-    int over = 0;
-    for (int a = 0; a < nsrc; ++a) {
-        h_ioff[a] = inz;
-        inz += h_nz[a];
-        nzmax = std::max<long long>(nzmax, h_nz[a]);
-        over += h_nz[a] > cap;
-    }
-    if ((rc = c->d_pg_irow.reserve((size_t)inz)) || (rc = c->d_pg_ival.reserve((size_t)inz))) return rc;
-    HIPCHK(hipMemcpyAsync(c->d_pg_ioff, h_ioff, sizeof(long long) * nsrc, hipMemcpyHostToDevice, c->stream));
-    A.inter_off = c->d_pg_ioff; A.inter_row = c->d_pg_irow; A.inter_val = c->d_pg_ival;
-    if (cap > 0) HIPCHK(pg_launch_gather(A, nsrc, c->stream));
-    if (over || cap == 0) HIPCHK(pg_launch_ftran(A, 1, nsrc, c->stream));
-    c->pg_sc_cap = std::max<long long>(1024, nzmax + nzmax / 2);   // the next build's scratch
-    HIPCHK(pg_launch_count(A, nsrc, c->stream));
-    int *ht = c->stage[9].reserve<int>((size_t)5 * nsrc);
-    if (!ht) return fail(TWOSD_E_DEVICE, "pool refresh: pinned staging allocation failed");
-    HIPCHK(hipMemcpyAsync(ht, c->d_pg_tot, sizeof(int) * 4 * nsrc, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipMemcpyAsync(ht + (size_t)4 * nsrc, c->d_pg_valid, sizeof(int) * nsrc, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
-    if (dbg) fprintf(stderr, "pg_compute: %d sources, %lld intermediate entries, largest %lld, %d past the scratch of %lld\n", nsrc, inz,
-                     nzmax, over, cap);
-    *h_tot = ht;
-    *h_valid = ht + (size_t)4 * nsrc;
-    *inz_out = inz;
-    return TWOSD_OK;
-}
-
-// assemble phase: pool = the sources of `order` (order[0] = 0, the primary) that passed, in
-// order; A describes the source table (compute output or the gathered table)
-static int pg_assemble(twosd_ctx *c, PgArgs &A, const int *h_tot, const int *h_valid, const std::vector<int> &order) {
-    const HostLP &L = c->L;
-    const int m = L.m, MP = c->MP;
-    int rc;
-    if (order.empty() || order[0] != 0 || !h_valid[0]) return 1;   // the primary failed the device checks: host path
-    std::vector<int> map, off;
-    std::vector<int64_t> acc(4, 0);
-    for (int a : order) {
-        if (!h_valid[a]) continue;
-        map.push_back(a);
-        for (int f = 0; f < 4; ++f) {
-            off.push_back((int)acc[f]);
-            acc[f] += h_tot[(size_t)a * 4 + f];
-        }
-        if (acc[0] > INT32_MAX || acc[1] > INT32_MAX || acc[2] * 64 > INT32_MAX || acc[3] > INT32_MAX)
-            return fail(TWOSD_E_UNSUPPORTED, "basis pool too large (> 2^31 entries)");
-    }
-    const int P = (int)map.size();
-    const bool dbg = getenv("TWOSD_DEBUG") != nullptr;
-    const auto t0 = std::chrono::steady_clock::now();
-    if ((rc = c->d_pg_map.reserve((size_t)P)) || (rc = c->d_pg_off.reserve((size_t)4 * P))) return rc;
-    // From here the live pool arrays are grown in place (a grown array does not keep its
-    // contents) and then overwritten: a failure past this point leaves c->pool describing
-    // arrays that no longer hold it.  The context then drops its basis, so every later solve
-    // fails cleanly (TWOSD_E_STATE) until twosd_compute_basis / twosd_set_basis installs one.
-    // the device-built bases read their heads lazily from pool_hb, which the failing path may
-    // have reallocated or overwritten: keep only the primary (a host basis)
-    auto broken = [c](int code) { return drop_pool(c, code); };
-    if (const char *inj = getenv("TWOSD_INJECT_FAIL"); inj && !strcmp(inj, "refresh_fill"))   // test hook
-        return broken(fail(TWOSD_E_DEVICE, "pool refresh: injected failure after the pool-array reservation"));
-    HIPCHK(hipMemcpyAsync(c->d_pg_map, map.data(), sizeof(int) * P, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(hipMemcpyAsync(c->d_pg_off, off.data(), sizeof(int) * 4 * P, hipMemcpyHostToDevice, c->stream));
-    const size_t nz = (size_t)acc[0], kz = (size_t)acc[1], ez = (size_t)acc[2] * 64;
-    if ((rc = c->d_brptr.reserve((size_t)P * (MP + 1))) || (rc = c->d_brcol.reserve(nz)) ||
-        (rc = c->d_brval.reserve(nz)) || (rc = c->d_bcp.reserve((size_t)P * (MP + 1))) ||
-        (rc = c->d_bci.reserve(nz)) || (rc = c->d_bcv.reserve(nz)) ||
-        (rc = c->d_kp.reserve((size_t)P * (m + 1))) || (rc = c->d_ke.reserve(kz)) ||
-        (rc = c->d_kraw.reserve(kz)) || (rc = c->d_kslot.reserve((size_t)P * (c->R + 1))) ||
-        (rc = c->d_kix.reserve(ez)) || (rc = c->d_kv.reserve(ez)) ||
-        (rc = c->d_hb0.reserve((size_t)P * MP)) || (rc = c->d_basic0.reserve((size_t)P * 64)) ||
-        (rc = c->d_bnnz.reserve((size_t)P)) || (rc = c->d_d0.reserve((size_t)P * 64 * c->CH)) ||
-        (rc = c->d_sel_ptr.reserve((size_t)P + 1)) || (rc = reserve_selection(c, P, (int)acc[3])))
-        return broken(rc);
-    // (a grown array is reallocated: the start pool's CSC was read only by the FTRAN passes)
-    PgFill F{};
-    F.P = P; F.map = c->d_pg_map; F.off = c->d_pg_off; F.sel_total = (int)acc[3]; F.d0_primary = c->d_pg_d0p;
-    F.brptr = c->d_brptr; F.brcol = c->d_brcol; F.brval = c->d_brval; F.bcp = c->d_bcp; F.bci = c->d_bci; F.bcv = c->d_bcv;
-    F.kp = c->d_kp; F.ke = c->d_ke; F.kraw = c->d_kraw; F.kslot = c->d_kslot; F.kix = c->d_kix; F.kv = c->d_kv;
-    F.hb0 = c->d_hb0; F.basic0 = c->d_basic0; F.bnnz = c->d_bnnz; F.d0 = c->d_d0; F.sel_ptr = c->d_sel_ptr;
-    F.P0 = 0;
-    if (pg_launch_fill(A, F, P, c->stream) != hipSuccess) return broken(fail(TWOSD_E_DEVICE, "pool refresh: fill launch failed"));
-    // the pool's heads (hb0 = 4 head + type) stay on the device; a host head is fetched on first
-    // use (head_of)
-    c->pool_hb_valid = false;
-    const auto t1 = std::chrono::steady_clock::now();
-    // host pool: the primary keeps its host forms; the new bases refer to their head rows
-    std::vector<PoolBasis> keep(P);
-    keep[0] = std::move(c->pool[0]);
-    for (int p = 1; p < P; ++p) {
-        keep[p].hb_row = p;
-        keep[p].dev_only = true;
-    }
-    c->pool.swap(keep);
-    std::thread([old = std::move(keep)]() mutable { old.clear(); }).detach();
-    c->b0_nnz = h_tot[0];
-    c->prep_valid = false;
-    c->k_valid = true;
-    reset_candidates(c);
-    if (dbg) {
-        auto ms = [](auto a, auto b) { return std::chrono::duration<double, std::milli>(b - a).count(); };
-        fprintf(stderr, "pg_assemble: P=%d fill + heads %.2f ms, host pool %.2f ms\n", P, ms(t0, t1),
-                ms(t1, std::chrono::steady_clock::now()));
-    }
-    return TWOSD_OK;
-}
-
-// Returns 1, with the pool unchanged, when the LDS layouts do not fit or the primary fails the
-// device checks (the caller then composes on the host).
-static int refresh_build_device(twosd_ctx *c, const std::vector<int> &sel) {
-    const int R = (int)sel.size();
-    if (!pg_supported(c->L.m, c->L.n, c->eo_kmax)) return 1;
-    const bool dbg = getenv("TWOSD_DEBUG") != nullptr;
-    PgArgs A;
-    int *h_tot = nullptr, *h_valid = nullptr;
-    long long inz = 0;
-    int rc;
-    if ((rc = pg_compute(c, R + 1, A, &h_tot, &h_valid, &inz, dbg))) return rc;
-    std::vector<int> order(R + 1);
-    for (int a = 0; a <= R; ++a) order[a] = a;
-    return pg_assemble(c, A, h_tot, h_valid, order);
-}
-
-// pivot cap of the training solves of a refresh.  One wavefront solves one scenario, so a
-// training launch lasts as long as its slowest scenario; the scenarios far from the current
-// pool (tens of pivots) mostly end at rare bases.  Auto: 3 x the mean pivots of the last large
-// batch, at least 32 (storm: 32-33; ssn, ~33 pivots a solve: ~100); none before any batch.
-// Storm 1M, 4096-basis pool (profiles/r03/train_kcap_1M.txt): cap 32 vs none -- refresh
-// 18.3 vs 25.6 ms, and the next solve 86.6 vs 108.5 ms (fewer pivots from the capped pool).
-// The one statement of the rule (twosd_training_cap exposes it to the distributed refresh, which
-// applies it to the all-reduced pivot sum and size of every rank): setting = TWOSD_TRAIN_KCAP if
-// set, else the context's (twosd_set_refresh_kcap); > 0 that cap, < 0 none, 0 auto =
-// max(32, ceil(3 sum / n)) in integers, none before any large batch.
-static int training_cap_rule(const twosd_ctx *c, int64_t sum, int64_t n) {
-    const char *e = getenv("TWOSD_TRAIN_KCAP");   // A/B knob
-    const int setting = e ? atoi(e) : (c ? c->train_kcap : 0);
-    if (setting > 0) return setting;
-    if (setting < 0 || n <= 0 || sum <= 0) return 0;
-    const int64_t q = (3 * sum + n - 1) / n;
-    return (int)std::max<int64_t>(32, std::min<int64_t>(q, INT32_MAX));
-}
-static int train_kcap(const twosd_ctx *c) { return training_cap_rule(c, c->piv_ref_sum, c->piv_ref_n); }
-
-// The training solves of a refresh (basis keys, eta files, final heads) under the pivot cap.  The
-// auto cap follows the last batch's pivots at the previous x; when x moved far from the pool's x
-// (bench with warmup 4: the x_EV pool trained from the primary basis, next x SD candidate 4 --
-// 58.5 pivots a scenario against a cap of 35), most training scenarios hit the cap and the
-// refresh would find almost no optimal bases.  If fewer than half end optimal, the training is
-// solved again without a cap (one extra launch, only on such a jump).
-static int refresh_training(twosd_ctx *c, const double *x, const double *d_dv, int count, int kcap, bool retry, int *n_opt) {
-    LpRun o;
-    o.want_bkey = true;
-    o.want_etas = true;
-    o.want_head = true;
-    // training scenarios beyond the pivot cap only drop out of the basis count (one launch
-    // lasts as long as its slowest scenario: with one scenario per wave the cap bounds it)
-    o.kcap = kcap;
-    int rc;
-    if ((rc = run_lp_ex(c, x, d_dv, count, o))) return rc;
-    int opt = count;
-    if (o.kcap > 0) {
-        std::vector<int> st(count);
-        HIPCHK(hipMemcpy(st.data(), c->d_status, sizeof(int) * count, hipMemcpyDeviceToHost));
-        opt = (int)std::count(st.begin(), st.end(), (int)TWOSD_LP_OPTIMAL);
-        if (retry && 2 * opt < count) {
-            if (getenv("TWOSD_DEBUG")) fprintf(stderr, "refresh training: %d of %d optimal under cap %d, solved again uncapped\n", opt, count, o.kcap);
-            o.kcap = 0;
-            if ((rc = run_lp_ex(c, x, d_dv, count, o))) return rc;
-        }
-    }
-    // The eta files share one arena, claimed through an atomic counter that keeps counting past
-    // its end.  Files that did not fit are lost (K = -1), and which ones those are depends on the
-    // order the waves finish in: solve again with an arena of the size this run asked for, so that
-    // the refreshed pool does not depend on that order.  Past 2^31 entries (32-bit offsets) the
-    // losses stay.
-    HIPCHK(hipStreamSynchronize(c->stream));
-    unsigned long long used64 = 0;
-    HIPCHK(hipMemcpy(&used64, c->d_eo_used, sizeof(used64), hipMemcpyDeviceToHost));
-    if (used64 > c->eo_cap && used64 <= (unsigned long long)INT32_MAX) {
-        if (getenv("TWOSD_DEBUG"))
-            fprintf(stderr, "refresh training: eta files of %llu entries past the arena of %zu, solved again\n", used64, c->eo_cap);
-        c->eo_min_cap = (size_t)std::min<unsigned long long>(used64 + used64 / 8, INT32_MAX);
-        if ((rc = run_lp_ex(c, x, d_dv, count, o))) return rc;
-    }
-    c->last_train_opt = opt;
-    if (n_opt) *n_opt = opt;
-    return TWOSD_OK;
-}
-
-extern "C" int twosd_pool_refresh(twosd_ctx *c, int epi, const double *x, int first, int count, int max_pool,
-                                  int *pool_size) {
-    if (!c || !c->has_basis) return fail(TWOSD_E_STATE, "pool_refresh: no primary basis");
-    if (epi < 0 || epi >= (int)c->epis.size()) return fail(TWOSD_E_ARG, "pool_refresh: epigraph %d does not exist", epi);
-    const EpiDevice &E = c->epis[epi];
-    if (first < 0 || count < 1 || first + count > E.count || max_pool < 1 || (c->n1 > 0 && !x))
-        return fail(TWOSD_E_ARG, "pool_refresh: bad arguments");
-    if (c->CH <= 0) return fail(TWOSD_E_UNSUPPORTED, "pool_refresh: needs the hypersparse LP kernel");
-    HIPCHK(hipSetDevice(c->device));
-    const auto t0 = std::chrono::steady_clock::now();
-    const int m = c->L.m;
-    const double *d_dv = E.d_dv + (size_t)first * c->k;
-    int rc;
-    // 1. training solves at x from the current pool: basis keys, eta files and heads by scenario
-    if ((rc = refresh_training(c, x, d_dv, count, train_kcap(c), true, nullptr))) return rc;
-    if (getenv("TWOSD_DEBUG")) {
-        std::vector<int> st(count), itv(count);
-        HIPCHK(hipMemcpy(st.data(), c->d_status, sizeof(int) * count, hipMemcpyDeviceToHost));
-        HIPCHK(hipMemcpy(itv.data(), c->d_iters, sizeof(int) * count, hipMemcpyDeviceToHost));
-        int h[8] = {0};
-        long long itsum = 0;
-        for (int s2 = 0; s2 < count; ++s2) { h[std::min(std::max(st[s2], 0), 7)]++; itsum += itv[s2]; }
-        fprintf(stderr, "pool_refresh training: kcap %d (ref %.2f), pool %zu, statuses 0:%d 1:%d 2:%d 3:%d 4:%d 5+:%d, mean iters %.2f\n",
-                train_kcap(c), c->piv_mean_ref, c->pool.size(), h[0], h[1], h[2], h[3], h[4], h[5] + h[6] + h[7], (double)itsum / count);
-    }
-    const auto t1 = std::chrono::steady_clock::now();
-    // 2. distinct optimal bases, most frequent first (ties: first occurrence), primary excluded
-    const int *d_list = nullptr, *d_counts = nullptr;
-    int U = 0;
-    if ((rc = vkey_first_occurrences(c, count, c->d_bkey, c->d_status, &d_list, &U, &d_counts))) return rc;
-    std::vector<int> reps(U), cnts(U);
-    if (U > 0) {
-        HIPCHK(hipMemcpy(reps.data(), d_list, sizeof(int) * U, hipMemcpyDeviceToHost));
-        HIPCHK(hipMemcpy(cnts.data(), d_counts, sizeof(int) * U, hipMemcpyDeviceToHost));
-    }
-    const auto t1b = std::chrono::steady_clock::now();
-    std::vector<int> ord(U);
-    for (int a = 0; a < U; ++a) ord[a] = a;
-    std::stable_sort(ord.begin(), ord.end(), [&](int a, int b) { return cnts[a] > cnts[b]; });
-    const int R = std::min(U, max_pool - 1);
-    std::vector<int> sel(R);
-    for (int a = 0; a < R; ++a) sel[a] = reps[ord[a]];
-    std::vector<PoolBasis> fresh;
-    bool device_built = false;
-    c->last_refresh_ms[1] = std::chrono::duration<double, std::milli>(t1b - t1).count();
-    c->last_refresh_ms[2] = c->last_refresh_ms[3] = 0.0;
-    if (R > 0 && !getenv("TWOSD_REFRESH_HOST")) {
-        // 3. B^{-1} of the representatives from their eta files, and the pool arrays, on the device
-        if ((rc = c->d_refresh_sel.fit((size_t)R))) return rc;
-        HIPCHK(hipMemcpyAsync(c->d_refresh_sel, sel.data(), sizeof(int) * R, hipMemcpyHostToDevice, c->stream));
-        const int dev = refresh_build_device(c, sel);
-        if (dev < 0) return dev;
-        device_built = dev == 0;
-        c->last_refresh_ms[2] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t1b).count();
-    }
-    if (R > 0 && !device_built) {
-        // 3'. host path: compose on the host threads, then upload_pool + prepare_elements
-        if ((rc = ensure_host_pool(c))) return rc;   // start bases in host form
-        const int kmax = c->eo_kmax;
-        std::vector<int> pb(count), K(count), off(count), etap((size_t)count * kmax), etaoff((size_t)count * (kmax + 1)),
-            heads((size_t)count * m);
-        int used = 0;
-        HIPCHK(hipMemcpy(pb.data(), c->d_eo_pb, sizeof(int) * count, hipMemcpyDeviceToHost));
-        HIPCHK(hipMemcpy(K.data(), c->d_eo_K, sizeof(int) * count, hipMemcpyDeviceToHost));
-        HIPCHK(hipMemcpy(off.data(), c->d_eo_off, sizeof(int) * count, hipMemcpyDeviceToHost));
-        HIPCHK(hipMemcpy(etap.data(), c->d_eo_etap, sizeof(int) * etap.size(), hipMemcpyDeviceToHost));
-        HIPCHK(hipMemcpy(etaoff.data(), c->d_eo_etaoff, sizeof(int) * etaoff.size(), hipMemcpyDeviceToHost));
-        HIPCHK(hipMemcpy(heads.data(), c->d_head_out, sizeof(int) * heads.size(), hipMemcpyDeviceToHost));
-        unsigned long long used64 = 0;
-        HIPCHK(hipMemcpy(&used64, c->d_eo_used, sizeof(used64), hipMemcpyDeviceToHost));
-        used = (int)std::min<unsigned long long>(used64, std::min<size_t>(c->eo_cap, INT32_MAX));
-        std::vector<int> ei(std::max(used, 1));
-        std::vector<double> ev(std::max(used, 1));
-        if (used > 0) {
-            HIPCHK(hipMemcpy(ei.data(), c->d_eo_eidx, sizeof(int) * used, hipMemcpyDeviceToHost));
-            HIPCHK(hipMemcpy(ev.data(), c->d_eo_evals, sizeof(double) * used, hipMemcpyDeviceToHost));
-        }
-        const auto t2 = std::chrono::steady_clock::now();
-        fresh.resize(R);
-        std::vector<char> ok(R, 0);
-        const unsigned nth = std::max(1u, std::min(16u, std::thread::hardware_concurrency()));
-        std::vector<std::thread> th;
-        for (unsigned t = 0; t < nth; ++t)
-            th.emplace_back([&, t]() {
-                for (int a = (int)t; a < R; a += (int)nth) {
-                    const int l = sel[a];   // eta-file row: the training scenario
-                    if (K[l] < 0 || pb[l] < 0 || pb[l] >= (int)c->pool.size()) continue;
-                    PoolBasis &B = fresh[a];
-                    B.head.assign(heads.begin() + (size_t)l * m, heads.begin() + (size_t)(l + 1) * m);
-                    const int *eo = etaoff.data() + (size_t)l * (kmax + 1);
-                    const PoolBasis &B0 = c->pool[pb[l]];
-                    compose_binv(m, B0.rptr, B0.rcol, B0.rval, K[l], etap.data() + (size_t)l * kmax, eo, ei.data() + off[l],
-                                 ev.data() + off[l], B.rptr, B.rcol, B.rval);
-                    ok[a] = finish_composed(c, B) == nullptr;
-                }
-            });
-        for (auto &t : th) t.join();
-        c->last_refresh_ms[2] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t2).count();
-        std::vector<PoolBasis> keep;
-        keep.reserve(R + 1);
-        keep.push_back(std::move(c->pool[0]));   // the primary basis stays pool[0]
-        for (int a = 0; a < R; ++a)
-            if (ok[a]) keep.push_back(std::move(fresh[a]));
-        c->pool.swap(keep);
-        // the old pool's host data is released on a helper thread (thousands of vectors)
-        std::thread([old = std::move(keep)]() mutable { old.clear(); }).detach();
-    }
-    // R == 0 (no training scenario optimal): the current pool stays (any pool basis is a valid
-    // start; dropping to the primary basis alone would cost ~90 pivots a scenario)
-    const auto tb = std::chrono::steady_clock::now();
-    // training box of the deltas (selection row pruning), as twosd_pool_build; cached per
-    // training range
-    if (c->k > 0 && !(c->box_epi == epi && c->box_first == first && c->box_count == count && c->box_n == E.count)) {
-        c->box_epi = epi; c->box_first = first; c->box_count = count; c->box_n = E.count;
-        std::vector<double> dv((size_t)count * c->k);
-        HIPCHK(hipMemcpy(dv.data(), d_dv, sizeof(double) * dv.size(), hipMemcpyDeviceToHost));
-        c->sel_lo.assign(c->k, INFINITY);
-        c->sel_hi.assign(c->k, -INFINITY);
-        for (int s2 = 0; s2 < count; ++s2)
-            for (int e = 0; e < c->k; ++e) {
-                c->sel_lo[e] = std::min(c->sel_lo[e], dv[(size_t)s2 * c->k + e]);
-                c->sel_hi[e] = std::max(c->sel_hi[e], dv[(size_t)s2 * c->k + e]);
-            }
-    }
-    const auto tu = std::chrono::steady_clock::now();
-    const bool host_built = R > 0 && !device_built;   // R == 0: the pool is unchanged
-    if (host_built && (rc = upload_pool(c))) return rc;
-    const auto tua = std::chrono::steady_clock::now();
-    if (host_built && (rc = prepare_elements(c))) return rc;
-    const auto t3 = std::chrono::steady_clock::now();
-    if (getenv("TWOSD_DEBUG")) {
-        auto ms = [](auto a, auto b) { return std::chrono::duration<double, std::milli>(b - a).count(); };
-        fprintf(stderr, "pool_refresh: train %.2f, keys %.2f, build %.2f, box %.2f, upload_pool %.2f, elements %.2f ms (R=%d)\n",
-                ms(t0, t1), ms(t1, t1b), ms(t1b, tb), ms(tb, tu), ms(tu, tua), ms(tua, t3), R);
-    }
-    c->last_refresh_ms[0] = std::chrono::duration<double, std::milli>(t1 - t0).count();
-    c->last_refresh_ms[3] = std::chrono::duration<double, std::milli>(t3 - tu).count();
-    c->last_refresh_ms[4] = std::chrono::duration<double, std::milli>(t3 - t0).count();
-    if (pool_size) *pool_size = (int)c->pool.size();
-    return TWOSD_OK;
-}
-
-// ---- distributed pool refresh -------------------------------------------------------------
-// The refresh of twosd_pool_refresh split over the ranks (one process per GPU, the pool
-// replicated): each rank solves its slice of the training scenarios (twosd_refresh_train), the
-// ranks exchange the distinct optimal bases with their counts and pick the same most frequent
-// max_pool - 1 (the caller's selection, sqlp_amd/dist.py), each rank composes the B^{-1} of the
-// picked bases whose first occurrence it holds (twosd_refresh_build_local -> a pack of the
-// intermediate CSC, counts and heads), the packs are all-gathered, and every rank assembles the
-// same pool from the gathered table (twosd_refresh_assemble).  With the training scenarios
-// split contiguously the pool equals the single-rank refresh of all of them, bit for bit.
-
-// pack: 8-byte aligned sections of n sources with nz intermediate entries
-struct RtPack {
-    size_t heads, cnt, tot, nztot, valid, irow, ival, bytes;
-};
-static inline size_t al8(size_t b) { return (b + 7) & ~(size_t)7; }
-static RtPack rt_layout(long long n, long long nz, int m) {
-    RtPack L{};
-    size_t o = 32;   // header: n, nz, bytes, m (int64)
-    L.heads = o; o = al8(o + sizeof(int) * (size_t)n * m);
-    L.cnt = o; o = al8(o + sizeof(int) * 4 * (size_t)n * m);
-    L.tot = o; o = al8(o + sizeof(int) * 4 * (size_t)n);
-    L.nztot = o; o = al8(o + sizeof(int) * (size_t)n);
-    L.valid = o; o = al8(o + sizeof(int) * (size_t)n);
-    L.irow = o; o = al8(o + sizeof(int) * (size_t)nz);
-    L.ival = o; o = al8(o + sizeof(double) * (size_t)nz);
-    L.bytes = o;
-    return L;
-}
-
-// rows src_row[j] of the training heads -> out row j
-__global__ void rt_heads_kernel(int n, int m, const int *__restrict__ heads, const int *__restrict__ src_row, int *__restrict__ out) {
-    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < (size_t)n * m; i += (size_t)gridDim.x * blockDim.x)
-        out[i] = heads[(size_t)src_row[i / m] * m + i % m];
-}
-
-// batched copy: segment blockIdx.y = (src, dst, 4-byte words)
-struct CopySeg { const int *src; int *dst; long long words; };
-__global__ void rt_copy_kernel(const CopySeg *__restrict__ seg) {
-    const CopySeg S = seg[blockIdx.y];
-    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < S.words; i += (long long)gridDim.x * blockDim.x)
-        S.dst[i] = S.src[i];
-}
-static int rt_copy(twosd_ctx *c, const std::vector<CopySeg> &segs) {
-    if (segs.empty()) return TWOSD_OK;
-    CopySeg *h = c->stage[13].reserve<CopySeg>(segs.size());
-    if (!h) return fail(TWOSD_E_DEVICE, "refresh: pinned staging allocation failed");
-    std::copy(segs.begin(), segs.end(), h);
-    if (int rc = c->d_gs_seg.fit(sizeof(CopySeg) * std::max<size_t>(segs.size(), 64))) return rc;
-    HIPCHK(hipMemcpyAsync(c->d_gs_seg, h, sizeof(CopySeg) * segs.size(), hipMemcpyHostToDevice, c->stream));
-    hipLaunchKernelGGL(rt_copy_kernel, dim3(64, (unsigned)segs.size()), dim3(256), 0, c->stream, (const CopySeg *)c->d_gs_seg.p);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipStreamSynchronize(c->stream));   // the staging buffer is reused by the next call
-    return TWOSD_OK;
-}
-
-// kcap: the training pivot cap (> 0; <= 0 none); retry: solve again uncapped when fewer than
-// half end optimal (the single-rank rule, decided by this rank alone)
-static int refresh_train_impl(twosd_ctx *c, int epi, const double *x, int first, int count, int kcap, bool retry,
-                              int *n_bases, int *n_opt, double *box_lo, double *box_hi) {
-    if (!c || !c->has_basis) return fail(TWOSD_E_STATE, "refresh_train: no primary basis");
-    if (epi < 0 || epi >= (int)c->epis.size()) return fail(TWOSD_E_ARG, "refresh_train: epigraph %d does not exist", epi);
-    const EpiDevice &E = c->epis[epi];
-    if (first < 0 || count < 1 || first + count > E.count || (c->n1 > 0 && !x) || !n_bases)
-        return fail(TWOSD_E_ARG, "refresh_train: bad arguments");
-    if (c->CH <= 0) return fail(TWOSD_E_UNSUPPORTED, "refresh_train: needs the hypersparse LP kernel");
-    HIPCHK(hipSetDevice(c->device));
-    const auto t0 = std::chrono::steady_clock::now();
-    const double *d_dv = E.d_dv + (size_t)first * c->k;
-    int rc;
-    c->rt_trained = false;
-    if ((rc = refresh_training(c, x, d_dv, count, kcap, retry, n_opt))) return rc;   // as twosd_pool_refresh step 1
-    const auto t1 = std::chrono::steady_clock::now();
-    const int *d_list = nullptr, *d_counts = nullptr;
-    int U = 0;
-    if ((rc = vkey_first_occurrences(c, count, c->d_bkey, c->d_status, &d_list, &U, &d_counts))) return rc;
-    c->rt_reps.resize(U);
-    c->rt_counts.resize(U);
-    c->rt_keys.resize(U);
-    std::vector<unsigned long long> bk(count);
-    if (U > 0) {
-        HIPCHK(hipMemcpy(c->rt_reps.data(), d_list, sizeof(int) * U, hipMemcpyDeviceToHost));
-        HIPCHK(hipMemcpy(c->rt_counts.data(), d_counts, sizeof(int) * U, hipMemcpyDeviceToHost));
-        HIPCHK(hipMemcpy(bk.data(), c->d_bkey, sizeof(unsigned long long) * count, hipMemcpyDeviceToHost));
-        for (int a = 0; a < U; ++a) c->rt_keys[a] = bk[c->rt_reps[a]];
-    }
-    // training box of the slice (cached per training range, as the single-rank refresh)
-    if (c->k > 0 && !(c->rt_epi == epi && c->rt_first == first && c->rt_count == count && c->rt_n == E.count)) {
-        std::vector<double> dv((size_t)count * c->k);
-        HIPCHK(hipMemcpy(dv.data(), d_dv, sizeof(double) * dv.size(), hipMemcpyDeviceToHost));
-        c->rt_lo.assign(c->k, INFINITY);
-        c->rt_hi.assign(c->k, -INFINITY);
-        for (int s2 = 0; s2 < count; ++s2)
-            for (int e = 0; e < c->k; ++e) {
-                c->rt_lo[e] = std::min(c->rt_lo[e], dv[(size_t)s2 * c->k + e]);
-                c->rt_hi[e] = std::max(c->rt_hi[e], dv[(size_t)s2 * c->k + e]);
-            }
-    }
-    c->rt_epi = epi; c->rt_first = first; c->rt_count = count; c->rt_n = E.count;
-    if (box_lo) std::copy(c->rt_lo.begin(), c->rt_lo.end(), box_lo);
-    if (box_hi) std::copy(c->rt_hi.begin(), c->rt_hi.end(), box_hi);
-    c->rt_nown = -1;
-    c->rt_trained = true;
-    c->last_refresh_ms[0] = std::chrono::duration<double, std::milli>(t1 - t0).count();
-    c->last_refresh_ms[1] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t1).count();
-    *n_bases = U;
-    return TWOSD_OK;
-}
-
-extern "C" int twosd_refresh_train(twosd_ctx *c, int epi, const double *x, int first, int count, int *n_bases,
-                                   double *box_lo, double *box_hi) {
-    if (!c) return fail(TWOSD_E_ARG, "refresh_train: NULL context");
-    return refresh_train_impl(c, epi, x, first, count, train_kcap(c), true, n_bases, nullptr, box_lo, box_hi);
-}
-
-extern "C" int twosd_refresh_train_ex(twosd_ctx *c, int epi, const double *x, int first, int count, int kcap, int *n_bases,
-                                      int *n_optimal, double *box_lo, double *box_hi) {
-    return refresh_train_impl(c, epi, x, first, count, kcap > 0 ? kcap : 0, false, n_bases, n_optimal, box_lo, box_hi);
-}
-
-extern "C" int twosd_refresh_train_bases(twosd_ctx *c, uint64_t *keys, int *counts, int *reps) {
-    if (!c || !c->rt_trained) return fail(TWOSD_E_STATE, "refresh_train_bases: no training solve (twosd_refresh_train)");
-    const size_t U = c->rt_keys.size();
-    if (keys) std::copy(c->rt_keys.begin(), c->rt_keys.end(), keys);
-    if (counts) std::copy(c->rt_counts.begin(), c->rt_counts.end(), counts);
-    if (reps) std::copy(c->rt_reps.begin(), c->rt_reps.begin() + U, reps);
-    return TWOSD_OK;
-}
-
-extern "C" int twosd_refresh_build_local(twosd_ctx *c, int n_own, const int *reps, int64_t *pack_bytes) {
-    if (!c || !c->rt_trained) return fail(TWOSD_E_STATE, "refresh_build_local: no training solve (twosd_refresh_train)");
-    if (n_own < 0 || (n_own > 0 && !reps) || !pack_bytes) return fail(TWOSD_E_ARG, "refresh_build_local: bad arguments");
-    for (int j = 0; j < n_own; ++j)
-        if (reps[j] < 0 || reps[j] >= c->rt_count) return fail(TWOSD_E_ARG, "refresh_build_local: representative %d outside the slice", reps[j]);
-    if (!pg_supported(c->L.m, c->L.n, c->eo_kmax))
-        return fail(TWOSD_E_UNSUPPORTED, "refresh_build_local: the device pool build does not fit this template");
-    HIPCHK(hipSetDevice(c->device));
-    const auto t0 = std::chrono::steady_clock::now();
-    const int m = c->L.m;
-    int rc;
-    if ((rc = c->d_refresh_sel.fit((size_t)std::max(n_own, 1)))) return rc;
-    if (n_own) HIPCHK(hipMemcpyAsync(c->d_refresh_sel, reps, sizeof(int) * n_own, hipMemcpyHostToDevice, c->stream));
-    PgArgs A;
-    int *h_tot = nullptr, *h_valid = nullptr;
-    long long inz = 0;
-    const int nsrc = n_own + 1;
-    if ((rc = pg_compute(c, nsrc, A, &h_tot, &h_valid, &inz, getenv("TWOSD_DEBUG") != nullptr))) return rc;
-    const long long *h_ioff = c->stage[12].as<long long>();
-    const long long nz0 = n_own ? h_ioff[1] : inz;
-    const RtPack L = rt_layout(n_own, inz - nz0, m);
-    if ((rc = c->d_rt_pack.reserve(L.bytes))) return rc;
-    long long *hdr = c->stage[14].reserve<long long>(4);
-    if (!hdr) return fail(TWOSD_E_DEVICE, "refresh: pinned staging allocation failed");
-    hdr[0] = n_own; hdr[1] = inz - nz0; hdr[2] = (long long)L.bytes; hdr[3] = m;
-    HIPCHK(hipMemcpyAsync(c->d_rt_pack, hdr, 32, hipMemcpyHostToDevice, c->stream));
-    char *P = c->d_rt_pack;
-    if (n_own) {
-        hipLaunchKernelGGL(rt_heads_kernel, dim3(std::min(1024, (n_own * m + 255) / 256)), dim3(256), 0, c->stream, n_own, m,
-                           c->d_head_out, c->d_refresh_sel, reinterpret_cast<int *>(P + L.heads));
-        HIPCHK(hipGetLastError());
-    }
-    std::vector<CopySeg> seg;
-    auto add = [&](const void *src, void *dst, size_t bytes) {
-        if (bytes) seg.push_back({static_cast<const int *>(src), static_cast<int *>(dst), (long long)(bytes / 4)});
-    };
-    const size_t nm = (size_t)n_own * m;
-    for (int f = 0; f < 4; ++f)   // nzc, keptc, rowcnt, erowcnt: rows 1..n_own of each
-        add(c->d_pg_cnt + (size_t)f * nsrc * m + m, P + L.cnt + sizeof(int) * f * nm, sizeof(int) * nm);
-    add(c->d_pg_tot + 4, P + L.tot, sizeof(int) * 4 * n_own);
-    add(c->d_pg_tot + (size_t)4 * nsrc + 1, P + L.nztot, sizeof(int) * n_own);
-    add(c->d_pg_valid + 1, P + L.valid, sizeof(int) * n_own);
-    add(c->d_pg_irow + nz0, P + L.irow, sizeof(int) * (inz - nz0));
-    add(c->d_pg_ival + nz0, P + L.ival, sizeof(double) * (inz - nz0));
-    if ((rc = rt_copy(c, seg))) return rc;
-    c->rt_nz0 = nz0;
-    c->rt_nsrc_local = nsrc;
-    c->rt_nown = n_own;
-    c->last_refresh_ms[2] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    *pack_bytes = (int64_t)L.bytes;
-    return TWOSD_OK;
-}
-
-extern "C" int twosd_refresh_pack(twosd_ctx *c, void *d_dst) {
-    if (!c || c->rt_nown < 0 || !d_dst) return fail(TWOSD_E_STATE, "refresh_pack: no local build (twosd_refresh_build_local)");
-    HIPCHK(hipSetDevice(c->device));
-    const RtPack L = rt_layout(c->rt_nown, 0, c->L.m);
-    long long bytes = 0;
-    HIPCHK(hipMemcpy(&bytes, c->d_rt_pack + 16, sizeof(bytes), hipMemcpyDeviceToHost));
-    (void)L;
-    HIPCHK(hipMemcpyAsync(d_dst, c->d_rt_pack, (size_t)bytes, hipMemcpyDeviceToDevice, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
-    return TWOSD_OK;
-}
-
-extern "C" int twosd_refresh_assemble(twosd_ctx *c, int G, const void *d_packs, int64_t stride, int R, const int *order,
-                                      const double *box_lo, const double *box_hi, int *pool_size) {
-    if (!c || c->rt_nown < 0) return fail(TWOSD_E_STATE, "refresh_assemble: no local build (twosd_refresh_build_local)");
-    if (G < 1 || !d_packs || stride < 32 || (stride & 7) || R < 0 || (R > 0 && !order) || (c->k > 0 && (!box_lo || !box_hi)))
-        return fail(TWOSD_E_ARG, "refresh_assemble: bad arguments");
-    HIPCHK(hipSetDevice(c->device));
-    const auto t0 = std::chrono::steady_clock::now();
-    const int m = c->L.m;
-    int rc;
-    const char *packs = static_cast<const char *>(d_packs);
-    std::vector<long long> hdr((size_t)4 * G);
-    HIPCHK(hipMemcpy2D(hdr.data(), 32, packs, (size_t)stride, 32, G, hipMemcpyDeviceToHost));
-    std::vector<long long> an(G + 1, 1), zn(G + 1, c->rt_nz0);
-    for (int r = 0; r < G; ++r) {
-        if (hdr[4 * r] < 0 || hdr[4 * r + 3] != m || hdr[4 * r + 2] > stride)
-            return fail(TWOSD_E_ARG, "refresh_assemble: pack %d is not a pack of this template", r);
-        an[r + 1] = an[r] + hdr[4 * r];
-        zn[r + 1] = zn[r] + hdr[4 * r + 1];
-    }
-    const long long nsrc = an[G], nzg = zn[G];
-    if (nsrc > INT32_MAX / std::max(m, 1)) return fail(TWOSD_E_UNSUPPORTED, "refresh_assemble: too many sources");
-    for (int i = 0; i < R; ++i)
-        if (order[i] < 1 || order[i] >= nsrc) return fail(TWOSD_E_ARG, "refresh_assemble: source %d outside [1, %lld)", order[i], nsrc);
-    if ((rc = c->d_gs_heads.reserve((size_t)std::max<long long>(nsrc - 1, 1) * m)) ||
-        (rc = c->d_gs_cnt.reserve((size_t)4 * nsrc * m)) || (rc = c->d_gs_tot.reserve((size_t)5 * nsrc)) ||
-        (rc = c->d_gs_valid.reserve((size_t)nsrc)) || (rc = c->d_gs_ioff.reserve((size_t)nsrc)) ||
-        (rc = c->d_gs_irow.reserve((size_t)nzg)) || (rc = c->d_gs_ival.reserve((size_t)nzg)))
-        return rc;
-    // the table: source 0 = this rank's primary (local compute row 0), then every rank's pack
-    std::vector<CopySeg> seg;
-    auto add = [&](const void *src, void *dst, size_t bytes) {
-        if (bytes) seg.push_back({static_cast<const int *>(src), static_cast<int *>(dst), (long long)(bytes / 4)});
-    };
-    const size_t nl = (size_t)c->rt_nsrc_local;
-    for (int f = 0; f < 4; ++f) add(c->d_pg_cnt + f * nl * m, c->d_gs_cnt + (size_t)f * nsrc * m, sizeof(int) * m);
-    add(c->d_pg_tot, c->d_gs_tot, sizeof(int) * 4);
-    add(c->d_pg_tot + 4 * nl, c->d_gs_tot + 4 * nsrc, sizeof(int));
-    add(c->d_pg_valid, c->d_gs_valid, sizeof(int));
-    add(c->d_pg_irow, c->d_gs_irow, sizeof(int) * c->rt_nz0);
-    add(c->d_pg_ival, c->d_gs_ival, sizeof(double) * c->rt_nz0);
-    for (int r = 0; r < G; ++r) {
-        const long long n = hdr[4 * r], nz = hdr[4 * r + 1], a = an[r];
-        const RtPack L = rt_layout(n, nz, m);
-        const char *P = packs + (size_t)r * stride;
-        const size_t nm = (size_t)n * m;
-        add(P + L.heads, c->d_gs_heads + (size_t)(a - 1) * m, sizeof(int) * nm);
-        for (int f = 0; f < 4; ++f) add(P + L.cnt + sizeof(int) * f * nm, c->d_gs_cnt + (size_t)f * nsrc * m + (size_t)a * m, sizeof(int) * nm);
-        add(P + L.tot, c->d_gs_tot + 4 * a, sizeof(int) * 4 * n);
-        add(P + L.nztot, c->d_gs_tot + 4 * nsrc + a, sizeof(int) * n);
-        add(P + L.valid, c->d_gs_valid + a, sizeof(int) * n);
-        add(P + L.irow, c->d_gs_irow + zn[r], sizeof(int) * nz);
-        add(P + L.ival, c->d_gs_ival + zn[r], sizeof(double) * nz);
-    }
-    if ((rc = rt_copy(c, seg))) return rc;
-    const auto t_copy = std::chrono::steady_clock::now();
-    if (getenv("TWOSD_DEBUG"))
-        fprintf(stderr, "refresh_assemble: %lld sources, %lld entries, unpack %.2f ms\n", nsrc, nzg,
-                std::chrono::duration<double, std::milli>(t_copy - t0).count());
-    int *h_tot = c->stage[9].reserve<int>((size_t)6 * nsrc);
-    long long *h_ioff = c->stage[12].reserve<long long>((size_t)nsrc);
-    if (!h_tot || !h_ioff) return fail(TWOSD_E_DEVICE, "refresh: pinned staging allocation failed");
-    int *h_nz = h_tot + 4 * nsrc, *h_valid = h_tot + 5 * nsrc;
-    HIPCHK(hipMemcpyAsync(h_tot, c->d_gs_tot, sizeof(int) * 5 * nsrc, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipMemcpyAsync(h_valid, c->d_gs_valid, sizeof(int) * nsrc, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
-    long long z = 0;
-    for (long long a = 0; a < nsrc; ++a) {
-        h_ioff[a] = z;
-        z += h_nz[a];
-    }
-    if (z != nzg) return fail(TWOSD_E_ARG, "refresh_assemble: packs inconsistent (%lld vs %lld entries)", z, nzg);
-    HIPCHK(hipMemcpyAsync(c->d_gs_ioff, h_ioff, sizeof(long long) * nsrc, hipMemcpyHostToDevice, c->stream));
-    // source table of the gathered build (template fields as the local compute)
-    PgArgs A;
-    if ((rc = pg_args(c, c->rt_nsrc_local, A))) return rc;
-    A.nzc = c->d_gs_cnt; A.keptc = c->d_gs_cnt + (size_t)nsrc * m;
-    A.rowcnt = c->d_gs_cnt + (size_t)2 * nsrc * m; A.erowcnt = c->d_gs_cnt + (size_t)3 * nsrc * m;
-    A.tot = c->d_gs_tot; A.nztot = c->d_gs_tot + 4 * nsrc; A.valid = c->d_gs_valid;
-    A.inter_off = c->d_gs_ioff; A.inter_row = c->d_gs_irow; A.inter_val = c->d_gs_ival;
-    A.gheads = c->d_gs_heads;
-    // R == 0 (no rank had an optimal training scenario, or max_pool <= 1): the current pool stays,
-    // as in twosd_pool_refresh (falling back to the primary basis alone costs ~90 pivots a scenario)
-    if (R > 0) {
-        std::vector<int> ord(R + 1);
-        ord[0] = 0;
-        std::copy(order, order + R, ord.begin() + 1);
-        if ((rc = pg_assemble(c, A, h_tot, h_valid, ord)) != 0)
-            return rc < 0 ? rc : fail(TWOSD_E_STATE, "refresh_assemble: the primary basis failed the device checks");
-    } else {
-        c->prep_valid = false;   // the selection box below changes
-    }
-    // selection box: the union of the ranks' training boxes
-    if (c->k > 0) {
-        c->sel_lo.assign(box_lo, box_lo + c->k);
-        c->sel_hi.assign(box_hi, box_hi + c->k);
-        c->box_epi = -1;   // not the single-rank cache
-    }
-    c->rt_nown = -1;
-    c->rt_trained = false;
-    const double ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    c->last_refresh_ms[3] = ms;
-    c->last_refresh_ms[4] = c->last_refresh_ms[0] + c->last_refresh_ms[1] + c->last_refresh_ms[2] + ms;
-    if (pool_size) *pool_size = (int)c->pool.size();
-    return TWOSD_OK;
-}
-
-extern "C" int twosd_last_refresh_ms(twosd_ctx *c, double *ms5) {
-    if (!c || !ms5) return fail(TWOSD_E_ARG, "last_refresh_ms: NULL");
-    for (int i = 0; i < 5; ++i) ms5[i] = c->last_refresh_ms[i];
-    return TWOSD_OK;
-}
-
 
 // Two-level selection from training scenarios [first, first + count) of epigraph epi at x:
 // level 1 = pool[0, level1) (the most frequent bases); the candidates of a level-1 basis p are
@@ -1627,7 +891,7 @@ static int set_candidates(twosd_ctx *c, int level1, int ncand, int n, const int 
                 c->pool.size(), level1, diff, n, filled);
     }
     int rc;
-    int *h = c->stage[15].reserve<int>(cand.size());
+    int *h = c->stage[STG_CAND].reserve<int>(cand.size());
     if (!h) return fail(TWOSD_E_DEVICE, "pool candidates: pinned staging allocation failed");
     std::copy(cand.begin(), cand.end(), h);
     if ((rc = c->d_cand.reserve(cand.size()))) return rc;
@@ -1949,7 +1213,7 @@ extern "C" int twosd_epigraph_info(twosd_ctx *c, int epi, int *ns, double *tw) {
 // per basis p the rows of B_p^{-1}[:, row_e] over the random elements e (host CSR kptr/ke/
 // kraw, e ascending) and the same as sliced ELL on the device (kslot pool-strided, absolute
 // into kix/kv).  The kernels multiply the scenario deltas by coef_e(x) (d_kcoef) themselves.
-static int prepare_elements(twosd_ctx *c) {
+int twosd::prepare_elements(twosd_ctx *c) {
     const auto t_pe0 = std::chrono::steady_clock::now();
     if (int rc0 = ensure_host_pool(c)) return rc0;
     const int m = c->L.m, k = c->k, R = c->R;
@@ -1992,8 +1256,8 @@ static int prepare_elements(twosd_ctx *c) {
     // by row (x_B warm start of the LP kernel), written in place
     const size_t kz = std::max<size_t>(kcnt[P], 1), ez = std::max<size_t>(ecnt[P], 1);
     std::vector<int> kp((size_t)P * (m + 1)), ks((size_t)P * (R + 1)), cap(P + 1);
-    int *ke = c->stage[5].reserve<int>(kz), *ki = c->stage[6].reserve<int>(ez);
-    double *kr = c->stage[7].reserve<double>(kz), *kv = c->stage[8].reserve<double>(ez);
+    int *ke = c->stage[STG_ELEM_KE].reserve<int>(kz), *ki = c->stage[STG_ELEM_KIX].reserve<int>(ez);
+    double *kr = c->stage[STG_ELEM_KRAW].reserve<double>(kz), *kv = c->stage[STG_ELEM_KV].reserve<double>(ez);
     if (!ke || !ki || !kr || !kv) return fail(TWOSD_E_DEVICE, "pool elements: pinned staging allocation failed");
     for (int p = 0; p <= P; ++p) cap[p] = (int)ccnt[p];
     parallel_for(P, [&](int p) {
@@ -3099,54 +2363,6 @@ extern "C" int twosd_evaluate_ci_vr(twosd_ctx *c, const double *x, uint64_t seed
     return evaluate_ci(c, x, seed, first, batch, n_max, z, rel_tol, abs_tol, offset, out, half_width, converged, pl);
 }
 
-extern "C" int twosd_training_cap(twosd_ctx *c, int64_t pivots_sum, int64_t scenarios, int *cap) {
-    if (!cap) return fail(TWOSD_E_ARG, "training_cap: NULL");   // ctx NULL: setting 0 (host code only)
-    if (pivots_sum < 0 || scenarios < 0) return fail(TWOSD_E_ARG, "training_cap: negative pivot sum / size");
-    *cap = training_cap_rule(c, pivots_sum, scenarios);
-    return TWOSD_OK;
-}
-
-extern "C" int twosd_refresh_cap_stats(twosd_ctx *c, int64_t *pivots_sum, int64_t *scenarios) {
-    if (!c) return fail(TWOSD_E_ARG, "refresh_cap_stats: NULL");
-    if (pivots_sum) *pivots_sum = c->piv_ref_sum;
-    if (scenarios) *scenarios = c->piv_ref_n;
-    return TWOSD_OK;
-}
-
-// The global basis selection of a distributed refresh (host, no context): the bases the ranks
-// list (concatenated in rank order), a key seen by several ranks counting the sum of its counts
-// and owned by its first occurrence; the max_pool - 1 largest totals, ties by first occurrence --
-// the single-rank refresh's stable sort over all training scenarios.
-extern "C" int twosd_select_refresh_bases(const uint64_t *keys, const int64_t *counts, const int64_t *reps, const int32_t *rank_of,
-                                          int n, int max_pool, int64_t *owner, int64_t *rep, int *npick) {
-    if (n < 0 || !npick || (n > 0 && (!keys || !counts || !reps || !rank_of))) return fail(TWOSD_E_ARG, "select_refresh_bases: bad arguments");
-    *npick = 0;
-    if (n == 0 || max_pool <= 1) return TWOSD_OK;
-    if (!owner || !rep) return fail(TWOSD_E_ARG, "select_refresh_bases: NULL output");
-    std::vector<int> idx(n);
-    for (int i = 0; i < n; ++i) idx[i] = i;
-    std::sort(idx.begin(), idx.end(), [&](int a, int b) { return keys[a] != keys[b] ? keys[a] < keys[b] : a < b; });
-    struct G { int64_t tot; int first; };
-    std::vector<G> g;
-    g.reserve(n);
-    for (int a = 0; a < n;) {
-        int b = a;
-        int64_t t = 0;
-        while (b < n && keys[idx[b]] == keys[idx[a]]) t += counts[idx[b++]];
-        g.push_back({t, idx[a]});   // the lowest index of the key: its first occurrence
-        a = b;
-    }
-    const size_t k = std::min<size_t>(g.size(), (size_t)max_pool - 1);
-    std::partial_sort(g.begin(), g.begin() + k, g.end(),
-                      [](const G &a, const G &b) { return a.tot != b.tot ? a.tot > b.tot : a.first < b.first; });
-    for (size_t i = 0; i < k; ++i) {
-        owner[i] = rank_of[g[i].first];
-        rep[i] = reps[g[i].first];
-    }
-    *npick = (int)k;
-    return TWOSD_OK;
-}
-
 extern "C" int twosd_solve_batch(twosd_ctx *c, int epi, const double *x, int first, int count, double *obj,
                                  double *pi, double *y, int *status) {
     if (!c || !c->has_template) return fail(TWOSD_E_STATE, "solve_batch: no template");
@@ -3197,12 +2413,6 @@ extern "C" int twosd_last_lp_stats(twosd_ctx *c, int64_t *sum, int *mx) {
     if (!c) return fail(TWOSD_E_ARG, "last_lp_stats: NULL");
     if (sum) *sum = c->last_pivots_sum;
     if (mx) *mx = c->last_pivots_max;
-    return TWOSD_OK;
-}
-
-extern "C" int twosd_set_refresh_kcap(twosd_ctx *c, int kcap) {
-    if (!c) return fail(TWOSD_E_ARG, "set_refresh_kcap: NULL");
-    c->train_kcap = kcap;
     return TWOSD_OK;
 }
 

@@ -411,12 +411,6 @@ __global__ void __launch_bounds__(256) boot_final_kernel(int B, int H, int j, in
     }
 }
 
-#define HIPCHK(expr)                                                                               \
-    do {                                                                                           \
-        hipError_t _e = (expr);                                                                    \
-        if (_e != hipSuccess) return fail(TWOSD_E_DEVICE, "%s: %s", #expr, hipGetErrorString(_e)); \
-    } while (0)
-
 static PickSet *pick_of(twosd_ctx *c, int handle) {
     if (handle < 0 || handle >= (int)c->boot.picks.size() || !c->boot.picks[handle].live) return nullptr;
     return &c->boot.picks[handle];

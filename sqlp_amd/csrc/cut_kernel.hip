@@ -1961,12 +1961,6 @@ void cut_invalidate_pk(twosd_ctx *c) {
     w->rows.release();   // forces re-upload of the element rows (and their order)
 }
 
-#define HIPCHK(expr)                                                                               \
-    do {                                                                                           \
-        hipError_t _e = (expr);                                                                    \
-        if (_e != hipSuccess) return fail(TWOSD_E_DEVICE, "%s: %s", #expr, hipGetErrorString(_e)); \
-    } while (0)
-
 // a cut that returns before the argmax (no scenarios) leaves no fixup counters: clear the last
 // cut's, so twosd_cut_stats does not report them as this cut's
 static int clear_cut_stats(twosd_ctx *c) {

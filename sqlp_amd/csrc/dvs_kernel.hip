@@ -221,12 +221,6 @@ int dvs_init(twosd_ctx *c) {
 
 void dvs_free(DvsWs *w) { delete w; }
 
-#define HIPCHK(expr)                                                                               \
-    do {                                                                                           \
-        hipError_t _e = (expr);                                                                    \
-        if (_e != hipSuccess) return fail(TWOSD_E_DEVICE, "%s: %s", #expr, hipGetErrorString(_e)); \
-    } while (0)
-
 static int ensure_capacity(twosd_ctx *c, int need) {
     DvsDevice &D = c->dvs;
     const int m = D.m;

@@ -1,7 +1,7 @@
 // pool_gpu.hip -- device side of a pool refresh: the B^{-1} of every harvested basis and every
 // pool-strided array the LP kernel and the pool selection read, built on the GPU.
 //
-// The host path of api.hip (compose_binv in host_basis.cpp, then upload_pool and
+// The host path of pool_refresh.hip (compose_binv in host_basis.cpp, then upload_pool and
 // prepare_elements) composes B^{-1} = E_K..E_1 B_pb^{-1} by sparse row merges and re-derives
 // CSC, element rows, sliced ELL, d0 and the basis words on 16 host threads before a PCIe
 // upload -- at 4096 bases ~60 ms of a ~90 ms refresh.  Here every column of B^{-1} is the

@@ -2,12 +2,43 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <algorithm>
 #include <memory>
+#include <thread>
 #include <vector>
 #include "devbuf.h"
 #include "twosd_internal.h"
 
+// a failed HIP call ends the enclosing function with TWOSD_E_DEVICE and the call's text
+#define HIPCHK(expr)                                                                                      \
+    do {                                                                                                  \
+        hipError_t _e = (expr);                                                                           \
+        if (_e != hipSuccess) return twosd::fail(TWOSD_E_DEVICE, "%s: %s", #expr, hipGetErrorString(_e)); \
+    } while (0)
+
 namespace twosd {
+
+// the pinned staging slots (twosd_ctx::stage) by use; a slot's buffer grows to its largest use
+enum StageSlot : int {
+    STG_POOL_RCOL = 0, STG_POOL_CROW, STG_POOL_RVAL, STG_POOL_CVAL, STG_POOL_D0,   // upload_pool: B^{-1} CSR / CSC, d0
+    STG_ELEM_KE, STG_ELEM_KIX, STG_ELEM_KRAW, STG_ELEM_KV,                         // prepare_elements: CSR and ELL rows
+    STG_PG_TOT,       // source table read-back: tot (4 nsrc) [, nztot (nsrc): the gathered table's], valid (nsrc)
+    STG_FREE_10,      // unused
+    STG_PG_NZ,        // pg_compute: nztot of the first FTRAN pass
+    STG_PG_IOFF,      // intermediate CSC offsets before their upload
+    STG_RT_SEG,       // copy-segment list of rt_copy
+    STG_RT_HDR,       // pack header
+    STG_CAND,         // candidate lists of the two-level selection
+    STG_COUNT
+};
+static_assert(STG_PG_TOT == 9 && STG_CAND == 15 && STG_COUNT == 16, "a slot keeps its buffer: do not renumber");
+
+// the training range a cached box of the deltas was taken over (epigraph, first, count, and the
+// epigraph's size then); the default matches no range
+struct BoxCache {
+    int epi = -1, first = -1, count = -1, n = -1;
+    bool operator==(const BoxCache &o) const { return epi == o.epi && first == o.first && count == o.count && n == o.n; }
+};
 
 struct EpiDevice {
     DevBuf<double> d_dv;          // count x k scenario deltas (value - template value)
@@ -206,7 +237,7 @@ struct TemplateState {
     int eo_kmax = 0;
     double last_refresh_ms[5] = {0, 0, 0, 0, 0};   // train solves, re-solves, compose, upload, total
     twosd::DevBuf<int> d_refresh_sel;                  // refresh: scenarios to re-solve
-    int box_epi = -1, box_first = -1, box_count = -1, box_n = -1;   // training range of sel_lo / sel_hi
+    twosd::BoxCache sel_box;                           // training range of sel_lo / sel_hi (single-rank refresh)
     // device pool build of a refresh (pool_gpu.hip): intermediate CSC, per-source counts and
     // checks, pool map / offsets, primary head and d0
     twosd::DevBuf<double> d_pg_amax, d_pg_d0p, d_pg_ival;
@@ -218,12 +249,13 @@ struct TemplateState {
     twosd::DevBuf<int> d_pg_scrow, d_pg_scoff;
     twosd::DevBuf<double> d_pg_scval;
     long long pg_sc_cap = 0;                       // entries per source of the last build (0: first build)
-    // distributed refresh (twosd_refresh_*): this rank's training keys, its pack of built
+    // distributed refresh (twosd_refresh_*, pool_refresh.hip): this rank's training keys, its pack of built
     // sources, and the source table gathered from all ranks
     std::vector<unsigned long long> rt_keys;
     std::vector<int> rt_counts, rt_reps;
     std::vector<double> rt_lo, rt_hi;     // training box of this rank's slice
-    int rt_epi = -1, rt_first = -1, rt_count = -1, rt_n = -1, rt_nown = -1;
+    twosd::BoxCache rt_box;               // the slice of the last twosd_refresh_train*, the range of rt_lo / rt_hi
+    int rt_nown = -1;
     bool rt_trained = false;              // a twosd_refresh_train* ran since the last assemble
     long long rt_nz0 = 0;                 // intermediate entries of the primary (local source 0)
     int rt_nsrc_local = 0;
@@ -250,7 +282,7 @@ struct twosd_ctx : TemplateState {
     int num_cus = 256;
     int kmax_override = 0;
     int train_kcap = 0;           // pivot cap of the refresh training solves (> 0; 0: auto; < 0: none): a caller setting
-    twosd::PinnedBuf stage[16];   // pinned host staging slots of the uploads
+    twosd::PinnedBuf stage[twosd::STG_COUNT];   // pinned host staging slots of the uploads (StageSlot)
     ~twosd_ctx() {
         for (hipEvent_t e : ev)
             if (e) hipEventDestroy(e);
@@ -274,6 +306,37 @@ struct LpRun {
     int kcap = 0;                 // > 0: pivot cap below kmax, no retry from the primary basis (refresh training)
 };
 int run_lp_ex(twosd_ctx *c, const double *x, const double *d_dv, int N, const LpRun &o);
+// the pool's host and device forms (api.hip), as the refresh (pool_refresh.hip) needs them; hidden:
+// they were file-local before the refresh had a file of its own, and the library's dynamic
+// symbols stay what they were
+#pragma GCC visibility push(hidden)
+int ensure_host_pool(twosd_ctx *c);      // host CSR rows and pi0 of device-built bases
+int upload_pool(twosd_ctx *c);
+int prepare_elements(twosd_ctx *c);
+int reserve_selection(twosd_ctx *c, int P, int records);
+int drop_pool(twosd_ctx *c, int code);   // keep the primary only, refuse solves; returns code
+void reset_candidates(twosd_ctx *c);
+void pi0_from_rows(const twosd_ctx *c, PoolBasis &B);
+// box [lo, hi] of the deltas of training scenarios [first, first + count) of epigraph epi (E): the
+// selection's row pruning.  With a cache, recomputed only when the range differs from the cached one.
+int training_box(twosd_ctx *c, const EpiDevice &E, int epi, int first, int count, std::vector<double> &lo,
+                 std::vector<double> &hi, BoxCache *cache);
+#pragma GCC visibility pop
+// f(i) for i in [0, n) on up to 16 host threads (independent work per i); serial when n < serial_below
+template <typename F>
+void parallel_for(int n, F f, int serial_below = 64) {
+    const int nth = (int)std::max(1u, std::min(16u, std::thread::hardware_concurrency()));
+    if (n < serial_below || nth == 1) {
+        for (int i = 0; i < n; ++i) f(i);
+        return;
+    }
+    std::vector<std::thread> th;
+    for (int t = 0; t < nth; ++t)
+        th.emplace_back([&, t]() {
+            for (int i = t; i < n; i += nth) f(i);
+        });
+    for (auto &t : th) t.join();
+}
 // vkey.hip
 int vkey_first_occurrences(twosd_ctx *c, int N, const unsigned long long *d_vkey, const int *d_status, const int **d_list,
                            int *U, const int **d_counts = nullptr);

@@ -110,6 +110,29 @@ struct PgArgs {
     long long sc_cap;
     int *sc_row, *sc_off; double *sc_val;                // nsrc x sc_cap, nsrc x m, nsrc x sc_cap
 };
+// A source table: what the compute phase leaves per source and the fill reads.  cnt is 4 planes
+// (nzc, keptc, rowcnt, erowcnt) of nsrc x m; tot is nsrc x 4 with nztot (nsrc) behind it; ioff /
+// irow / ival are the intermediate CSC; gheads the heads of sources >= 1 (a gathered table; else
+// nullptr).  A context has two: the local one (d_pg_*) and the gathered one (d_gs_*).
+struct PgTable {
+    int nsrc;
+    int *cnt, *tot, *valid;
+    long long *ioff;
+    int *irow;
+    double *ival;
+    int *gheads;
+    static size_t plane_size(int nsrc, int m) { return (size_t)nsrc * m; }
+    static size_t cnt_size(int nsrc, int m) { return 4 * plane_size(nsrc, m); }
+    static size_t tot_size(int nsrc) { return (size_t)5 * nsrc; }
+    int *plane(int f, int m) const { return cnt + f * plane_size(nsrc, m); }
+    int *nztot() const { return tot + (size_t)4 * nsrc; }
+};
+inline void pg_bind(PgArgs &A, const PgTable &T) {
+    A.nzc = T.plane(0, A.m); A.keptc = T.plane(1, A.m); A.rowcnt = T.plane(2, A.m); A.erowcnt = T.plane(3, A.m);
+    A.tot = T.tot; A.nztot = T.nztot(); A.valid = T.valid;
+    A.inter_off = T.ioff; A.inter_row = T.irow; A.inter_val = T.ival;
+    A.gheads = T.gheads;
+}
 struct PgFill {
     int P0, P;                                           // pool bases [P0, P0 + grid) of P
     const int *map;                                      // P: source of pool basis p

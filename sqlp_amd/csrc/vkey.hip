@@ -16,12 +16,6 @@
 
 namespace twosd {
 
-#define HIPCHK(expr)                                                                               \
-    do {                                                                                           \
-        hipError_t _e = (expr);                                                                    \
-        if (_e != hipSuccess) return fail(TWOSD_E_DEVICE, "%s: %s", #expr, hipGetErrorString(_e)); \
-    } while (0)
-
 __device__ __forceinline__ unsigned long long vk_norm(unsigned long long k) { return k ? k : 1ull; }   // 0 = empty slot
 __device__ __forceinline__ unsigned vk_slot(unsigned long long k, unsigned mask) {
     return (unsigned)((k * 0x9E3779B97F4A7C15ull) >> 32) & mask;

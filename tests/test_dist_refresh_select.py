@@ -32,7 +32,7 @@ def _slice_bases(keys):
 
 def _single_rank(keys, max_pool):
     k, c, f = _slice_bases(keys)
-    sel = np.argsort(-c, kind="stable")[: max_pool - 1]           # api.hip: stable_sort by count
+    sel = np.argsort(-c, kind="stable")[: max_pool - 1]           # pool_refresh.hip: stable_sort by count
     return f[sel]
 
 

@@ -340,3 +340,77 @@ def test_training_cap_setting_and_env(monkeypatch):
     assert ctx.training_cap(50000, 1000) == 150
     monkeypatch.setenv("TWOSD_TRAIN_KCAP", "77")
     assert ctx.training_cap(50000, 1000) == 77
+
+
+# ---- a rank that owns no pick: the empty pack ----------------------------------------------
+E_TRAIN = 512
+E_EVAL = 256
+
+
+def _lands_ctx():
+    from sqlp_amd import smps, twosd
+    inst = I.load("lands")
+    ctx = twosd.SDContext(inst["sp2"], inst["sto"])
+    ctx.compute_basis(I.x_ev("lands"), smps.mean_values(inst["sto"]))
+    return ctx
+
+
+def _lands_state(ctx, x):
+    from sqlp_amd import twosd
+    heads = np.stack([ctx.pool_get(p) for p in range(ctx.pool_size())])
+    ev = twosd.sdEpigraph(ctx, 1.0, 0.0)
+    twosd.add_scenarios(ev, I.sample("lands", E_EVAL, seed=52))
+    obj, _, _, st = twosd.solve_batch(ev, x, 0, E_EVAL, want_pi=False)
+    return heads, obj, st, ctx.last_pool_picks(E_EVAL)
+
+
+def _empty_pack_worker(rank, world, port, x, out):
+    os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK=str(rank), WORLD_SIZE=str(world))
+    import torch
+    import torch.distributed as dist
+    torch.cuda.set_device(0)
+    dist.init_process_group("gloo", rank=rank, world_size=world)
+    try:
+        from sqlp_amd import dist as sdist
+        from sqlp_amd import twosd
+        ctx = _lands_ctx()
+        lo, hi = sdist.shard_range(E_TRAIN, rank, world)
+        tr = twosd.sdEpigraph(ctx, 1.0, 0.0)
+        twosd.add_scenarios(tr, I.sample("lands", E_TRAIN, seed=51)[lo:hi])
+        owned = []
+        build_local = ctx.refresh_build_local
+        ctx.refresh_build_local = lambda reps: (owned.append(len(reps)), build_local(reps))[1]
+        size, _ = sdist.refresh_sharded(ctx, tr, x, 0, hi - lo, 2, 0, 0, torch.device("cuda", 0))
+        heads, obj, st, picks = _lands_state(ctx, x)
+        out[rank] = dict(size=size, owned=owned, heads=heads, obj=obj, st=st, picks=picks)
+    finally:
+        dist.destroy_process_group()
+
+
+def test_refresh_sharded_rank_with_empty_pack():
+    """max_pool = 2 picks exactly one representative, so one of the two ranks composes nothing:
+    its twosd_refresh_build_local runs with n_own = 0 and its pack is the header alone.  Both
+    ranks still assemble the pool one rank builds from all training scenarios (flat selection on
+    both sides: a pool of 2 has no second level), and the next solves are bit-identical."""
+    import torch.multiprocessing as mp
+    from sqlp_amd import twosd
+    x = I.x_ev("lands")
+    port = _free_port()
+    with mp.get_context("spawn").Manager() as mgr:
+        out = mgr.dict()
+        mp.start_processes(_empty_pack_worker, args=(2, port, x, out), nprocs=2, join=True, start_method="spawn")
+        res = dict(out)
+    ctx = _lands_ctx()
+    tr = twosd.sdEpigraph(ctx, 1.0, 0.0)
+    twosd.add_scenarios(tr, I.sample("lands", E_TRAIN, seed=51))
+    size = ctx.pool_refresh(tr, x, 0, E_TRAIN, 2)
+    heads, obj, st, picks = _lands_state(ctx, x)
+    assert size == 2                                           # the refresh found a new basis at x
+    assert sorted(res[r]["owned"] for r in (0, 1)) == [[0], [1]]   # one rank's pack is empty
+    for r in (0, 1):
+        o = res[r]
+        assert o["size"] == size
+        np.testing.assert_array_equal(o["heads"], heads)
+        np.testing.assert_array_equal(o["st"], st)
+        np.testing.assert_array_equal(o["obj"], obj)
+        np.testing.assert_array_equal(o["picks"], picks)
