@@ -4,6 +4,10 @@
 //   template (W CSC, q, bound types), shared warm-start basis (B0^{-1}, pi0), per-epigraph
 //   scenario pools (deltas, weights), the dual vertex set, and the LP/cut workspaces.
 // Every call is synchronous on the context's own HIP stream.
+// Here: errors, create / destroy, canonical form, template, positions, the host basis and pool
+// (build, upload), epigraphs, distributions, sampling plans.  The per-x preparation and warm-start
+// selection are in pool_select.hip, the LP launch with its outputs and solve_* in lp_batch.hip,
+// out-of-sample evaluation in evaluate.hip, the pool refresh in pool_refresh.hip.
 #include <hip/hip_runtime.h>
 #include <algorithm>
 #include <cmath>
@@ -46,7 +50,7 @@ extern "C" int twosd_create(int device, twosd_ctx **out) {
     std::unique_ptr<twosd_ctx> c(new twosd_ctx());   // a failure below destroys what was created
     c->device = device;
     HIPCHK(hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking));
-    for (int i = 0; i < 8; ++i) HIPCHK(hipEventCreate(&c->ev[i]));
+    for (hipEvent_t &e : c->ev) HIPCHK(hipEventCreate(&e));
     hipDeviceProp_t prop;
     HIPCHK(hipGetDeviceProperties(&prop, device));
     c->num_cus = prop.multiProcessorCount;
@@ -54,40 +58,6 @@ extern "C" int twosd_create(int device, twosd_ctx **out) {
     if (km) c->kmax_override = atoi(km);
     *out = c.release();
     return TWOSD_OK;
-}
-
-// Sliced ELL of S*64 columns: column j = 64*s + l gives (row, value) entries via colf.
-// Slot s has width E_s = max entries over its 64 columns; entry e of lane l is stored at
-// [(slot[s] + e) * 64 + l], padding (row 0, value 0).
-template <typename F>
-static void build_ell(int S, F colf, std::vector<int> &slot, std::vector<int> &ix, std::vector<double> &v) {
-    slot.assign(S + 1, 0);
-    std::vector<std::vector<std::pair<int, double>>> cols(64);
-    ix.clear(); v.clear();
-    for (int s = 0; s < S; ++s) {
-        int width = 0;
-        for (int l = 0; l < 64; ++l) {
-            cols[l].clear();
-            colf(64 * s + l, cols[l]);
-            width = std::max(width, (int)cols[l].size());
-        }
-        for (int e = 0; e < width; ++e)
-            for (int l = 0; l < 64; ++l) {
-                const bool has = e < (int)cols[l].size();
-                ix.push_back(has ? cols[l][e].first : 0);
-                v.push_back(has ? cols[l][e].second : 0.0);
-            }
-        slot[s + 1] = slot[s] + width;
-    }
-}
-
-// the two-level candidate lists (device, or staged for the next selection) refer to pool
-// indices: every change of the pool drops them
-void twosd::reset_candidates(twosd_ctx *c) {
-    c->pool_l1 = c->pool_ncand = 0;
-    c->cand_pending = false;
-    std::vector<int>().swap(c->cand_p1);
-    std::vector<int>().swap(c->cand_pf);
 }
 
 // the pool no longer matches the device arrays (a failed build or head read-back): keep only
@@ -131,16 +101,6 @@ static int head_of(twosd_ctx *c, int p, const std::vector<int> **h) {
 static int materialize_heads(twosd_ctx *c) {
     for (int p = 0; p < (int)c->pool.size(); ++p)
         if (int rc = head_of(c, p, nullptr)) return rc;
-    return TWOSD_OK;
-}
-
-// device selection-stream outputs of a pool of P bases with `records` records (prepare_x
-// writes them per x)
-int twosd::reserve_selection(twosd_ctx *c, int P, int records) {
-    int rc;
-    if ((rc = c->d_sel_code.fit(2 * (size_t)std::max(records, 1)))) return rc;   // (code, float bits) pairs
-    if ((rc = c->d_sel_end.reserve((size_t)P)) || (rc = c->d_sel_cinf.reserve((size_t)P))) return rc;
-    c->sel_cap_total = records;
     return TWOSD_OK;
 }
 
@@ -441,13 +401,13 @@ extern "C" int twosd_set_random_positions(twosd_ctx *c, int k, const int *row, c
 
 // template value at position e (RHS or T entry), in the caller's space: the caller's r, not the
 // shifted r' of a template with general bounds (a delta is the same in both)
-static double template_value(const twosd_ctx *c, int e) {
+double twosd::template_value(const twosd_ctx *c, int e) {
     const int rr = c->pos_row[e], cc = c->pos_col[e];
     return cc < 0 ? c->r_user[rr] : c->T[(size_t)rr * c->n1 + cc];
 }
 
 // b = r - T x + effect of the element deltas dv (k)
-static void rhs_at(const twosd_ctx *c, const double *x, const double *dv, std::vector<double> &b) {
+void twosd::rhs_at(const twosd_ctx *c, const double *x, const double *dv, std::vector<double> &b) {
     const int m = c->L.m, n1 = c->n1;
     b.assign(c->r.begin(), c->r.end());
     if (x)
@@ -609,14 +569,12 @@ int twosd::upload_pool(twosd_ctx *c) {
     const auto tc = std::chrono::steady_clock::now();
     int rc;
     if ((rc = c->d_hb0.upload_reserve(hb)) || (rc = c->d_basic0.upload_reserve(basic)) || (rc = c->d_bnnz.upload_reserve(bnnz))) return rc;
-    if (c->CH > 0) {
-        if ((rc = c->d_bcp.upload_reserve(cp_all)) || (rc = c->d_bci.upload_reserve(ci_all, ro[P])) ||
-            (rc = c->d_bcv.upload_reserve(cv_all, ro[P])) || (rc = c->d_brptr.upload_reserve(rp_all)) ||
-            (rc = c->d_brcol.upload_reserve(rc_all, ro[P])) || (rc = c->d_brval.upload_reserve(rv_all, ro[P])) ||
-            (rc = c->d_d0.upload_reserve(d0_all, (size_t)P * 64 * c->CH)))
-            return rc;
-        c->b0_nnz = bnnz[0];
-    }
+    if (c->CH > 0 &&
+        ((rc = c->d_bcp.upload_reserve(cp_all)) || (rc = c->d_bci.upload_reserve(ci_all, ro[P])) ||
+         (rc = c->d_bcv.upload_reserve(cv_all, ro[P])) || (rc = c->d_brptr.upload_reserve(rp_all)) ||
+         (rc = c->d_brcol.upload_reserve(rc_all, ro[P])) || (rc = c->d_brval.upload_reserve(rv_all, ro[P])) ||
+         (rc = c->d_d0.upload_reserve(d0_all, (size_t)P * 64 * c->CH))))
+        return rc;
     if (getenv("TWOSD_DEBUG")) {
         const auto td = std::chrono::steady_clock::now();
         auto ms = [](auto a, auto b) { return std::chrono::duration<double, std::milli>(b - a).count(); };
@@ -726,24 +684,6 @@ static int64_t pivots_of_last_lp(twosd_ctx *c, int N) {
     return sum;
 }
 
-int twosd::training_box(twosd_ctx *c, const EpiDevice &E, int epi, int first, int count, std::vector<double> &lo,
-                        std::vector<double> &hi, BoxCache *cache) {
-    const int k = c->k;
-    const BoxCache range{epi, first, count, E.count};
-    if (k <= 0 || (cache && *cache == range)) return TWOSD_OK;
-    std::vector<double> dv((size_t)count * k);
-    HIPCHK(hipMemcpy(dv.data(), E.d_dv + (size_t)first * k, sizeof(double) * dv.size(), hipMemcpyDeviceToHost));
-    lo.assign(k, INFINITY);
-    hi.assign(k, -INFINITY);
-    for (int s = 0; s < count; ++s)
-        for (int e = 0; e < k; ++e) {
-            lo[e] = std::min(lo[e], dv[(size_t)s * k + e]);
-            hi[e] = std::max(hi[e], dv[(size_t)s * k + e]);
-        }
-    if (cache) *cache = range;
-    return TWOSD_OK;
-}
-
 // Grow the pool from training scenarios [first, first + count) of epigraph epi at x.  The
 // first half harvests: solved from the current pool, its optimal bases are added in order
 // of decreasing frequency (ties: first occurrence) up to max_pool bases.  The second half
@@ -768,12 +708,11 @@ extern "C" int twosd_pool_build(twosd_ctx *c, int epi, const double *x, int firs
     if (nh > 0 && (int)c->pool.size() < max_pool) {
         const double *dh = E.d_dv + (size_t)first * c->k, *dval = dh + (size_t)nh * c->k;
         int rc;
-        if ((rc = run_lp(c, x, dval, nv, false, false))) return rc;
+        if ((rc = run_lp(c, x, dval, nv))) return rc;
         const int64_t piv0 = pivots_of_last_lp(c, nv);
-        c->want_head = true;
-        rc = run_lp(c, x, dh, nh, false, false);
-        c->want_head = false;
-        if (rc) return rc;
+        LpRun harvest;
+        harvest.want_head = true;
+        if ((rc = run_lp(c, x, dh, nh, harvest))) return rc;
         std::vector<int> heads((size_t)nh * m), st(nh);
         HIPCHK(hipMemcpy(heads.data(), c->d_head_out, sizeof(int) * heads.size(), hipMemcpyDeviceToHost));
         HIPCHK(hipMemcpy(st.data(), c->d_status, sizeof(int) * nh, hipMemcpyDeviceToHost));
@@ -812,7 +751,7 @@ extern "C" int twosd_pool_build(twosd_ctx *c, int epi, const double *x, int firs
             if (ok[a]) c->pool.push_back(std::move(cand[a]));
         if (c->pool.size() > old_size) {
             if ((rc = upload_pool(c))) return rc;
-            if ((rc = run_lp(c, x, dval, nv, false, false))) return rc;
+            if ((rc = run_lp(c, x, dval, nv))) return rc;
             const int64_t piv1 = pivots_of_last_lp(c, nv);
             std::vector<int> st2(nv);
             HIPCHK(hipMemcpy(st2.data(), c->d_status, sizeof(int) * nv, hipMemcpyDeviceToHost));
@@ -824,152 +763,6 @@ extern "C" int twosd_pool_build(twosd_ctx *c, int epi, const double *x, int firs
         }
     }
     if (pool_size) *pool_size = (int)c->pool.size();
-    return TWOSD_OK;
-}
-
-static int select_pool(twosd_ctx *c, const double *d_dv, int N, int *d_pick, int npool_override);
-
-// Two-level selection from training scenarios [first, first + count) of epigraph epi at x:
-// level 1 = pool[0, level1) (the most frequent bases); the candidates of a level-1 basis p are
-// the ncand bases that the flat selection over the whole pool picks most often for training
-// scenarios whose level-1 pick is p (ties: lower index).  level1 = 0 back to flat selection.
-// flat and level-1 picks of training scenarios [first, first + count) of epi at x
-static int candidate_picks(twosd_ctx *c, const EpiDevice &E, const double *x, int first, int count, int level1,
-                           int *p1, int *pf) {
-    int rc;
-    if ((rc = prepare_x(c, x))) return rc;
-    if ((rc = c->d_cpick.reserve((size_t)count))) return rc;   // grow-only: no reallocation per refresh
-    int *d_p = c->d_cpick;
-    const double *dv = E.d_dv + (size_t)first * c->k;
-    auto picks = [&](int np, int *out) {   // selection runs on c->stream
-        int r = select_pool(c, dv, count, d_p, np);
-        if (!r && (hipStreamSynchronize(c->stream) != hipSuccess ||
-                   hipMemcpy(out, d_p, sizeof(int) * count, hipMemcpyDeviceToHost) != hipSuccess))
-            r = fail(TWOSD_E_DEVICE, "pool candidates: selection failed");
-        return r;
-    };
-    rc = picks(level1, p1);
-    if (!rc) rc = picks((int)c->pool.size(), pf);
-    return rc;
-}
-
-// candidate lists from the picks of the training scenarios (any order): the ncand bases the flat
-// selection picks most often among the scenarios of each level-1 pick (ties: lower index)
-static int set_candidates(twosd_ctx *c, int level1, int ncand, int n, const int *p1, const int *pf) {
-    // the differing (level-1 pick, flat pick) pairs bucketed by level-1 pick (counting sort), then
-    // per bucket the flat picks sorted and counted by runs; the ncand most frequent kept (ties:
-    // lower basis)
-    std::vector<int> start(level1 + 1, 0);
-    for (int s = 0; s < n; ++s)
-        if (pf[s] != p1[s] && p1[s] >= 0 && p1[s] < level1) ++start[p1[s] + 1];
-    for (int p = 0; p < level1; ++p) start[p + 1] += start[p];
-    std::vector<int> fill(start.begin(), start.end() - 1), bucket(start[level1]);
-    for (int s = 0; s < n; ++s)
-        if (pf[s] != p1[s] && p1[s] >= 0 && p1[s] < level1) bucket[fill[p1[s]]++] = pf[s];
-    std::vector<int> cand((size_t)level1 * ncand, -1);
-    std::vector<std::pair<int, int>> v;   // (-count, basis) of one level-1 pick
-    for (int p = 0; p < level1; ++p) {
-        int *b0 = bucket.data() + start[p], *b1 = bucket.data() + start[p + 1];
-        if (b0 == b1) continue;
-        std::sort(b0, b1);
-        v.clear();
-        for (int *a = b0; a < b1;) {
-            int *b = a;
-            while (b < b1 && *b == *a) ++b;
-            v.push_back({-(int)(b - a), *a});
-            a = b;
-        }
-        const size_t nk = std::min<size_t>(v.size(), ncand);
-        std::partial_sort(v.begin(), v.begin() + nk, v.end());
-        for (size_t i = 0; i < nk; ++i) cand[(size_t)p * ncand + i] = v[i].second;
-    }
-    if (getenv("TWOSD_DEBUG")) {
-        int diff = 0, filled = 0;
-        for (int s = 0; s < n; ++s) diff += pf[s] != p1[s];
-        for (int v : cand) filled += v >= 0;
-        fprintf(stderr, "pool candidates: P=%zu level1=%d: %d of %d training picks change, %d candidate slots filled\n",
-                c->pool.size(), level1, diff, n, filled);
-    }
-    int rc;
-    int *h = c->stage[STG_CAND].reserve<int>(cand.size());
-    if (!h) return fail(TWOSD_E_DEVICE, "pool candidates: pinned staging allocation failed");
-    std::copy(cand.begin(), cand.end(), h);
-    if ((rc = c->d_cand.reserve(cand.size()))) return rc;
-    HIPCHK(hipMemcpyAsync(c->d_cand, h, sizeof(int) * cand.size(), hipMemcpyHostToDevice, c->stream));
-    c->pool_l1 = level1;
-    c->pool_ncand = ncand;
-    c->cand_pending = false;
-    return TWOSD_OK;
-}
-
-// the lists are built by the next two-level selection (select_pool), on the host while its
-// level-1 pass runs on the device: same lists, the host time off the critical path
-static int defer_candidates(twosd_ctx *c, int level1, int ncand, std::vector<int> &&p1, std::vector<int> &&pf) {
-    c->cand_p1 = std::move(p1);
-    c->cand_pf = std::move(pf);
-    c->cand_pl1 = level1;
-    c->cand_pnc = ncand;
-    c->cand_pending = true;
-    c->pool_l1 = level1;
-    c->pool_ncand = ncand;
-    return TWOSD_OK;
-}
-
-extern "C" int twosd_pool_candidate_picks(twosd_ctx *c, int epi, const double *x, int first, int count, int level1, int *p1,
-                                          int *pf) {
-    if (!c || !c->has_basis) return fail(TWOSD_E_STATE, "pool_candidate_picks: no primary basis");
-    if (epi < 0 || epi >= (int)c->epis.size()) return fail(TWOSD_E_ARG, "pool_candidate_picks: epigraph %d does not exist", epi);
-    const EpiDevice &E = c->epis[epi];
-    const int P = (int)c->pool.size();
-    if (first < 0 || count < 1 || first + count > E.count || level1 < 1 || level1 >= P || !p1 || !pf || (c->n1 > 0 && !x) ||
-        c->CH <= 0)
-        return fail(TWOSD_E_ARG, "pool_candidate_picks: bad arguments");
-    HIPCHK(hipSetDevice(c->device));
-    reset_candidates(c);   // the flat pick runs over the whole pool
-    return candidate_picks(c, E, x, first, count, level1, p1, pf);
-}
-
-extern "C" int twosd_pool_set_candidates(twosd_ctx *c, int level1, int ncand, int n, const int *p1, const int *pf) {
-    if (!c || !c->has_basis) return fail(TWOSD_E_STATE, "pool_set_candidates: no primary basis");
-    const int P = (int)c->pool.size();
-    if (level1 < 1 || level1 >= P || ncand < 1 || ncand > 1024 || n < 0 || (n > 0 && (!p1 || !pf)))
-        return fail(TWOSD_E_ARG, "pool_set_candidates: bad arguments");
-    for (int s = 0; s < n; ++s)
-        if (p1[s] < 0 || p1[s] >= P || pf[s] < 0 || pf[s] >= P) return fail(TWOSD_E_ARG, "pool_set_candidates: pick outside the pool");
-    HIPCHK(hipSetDevice(c->device));
-    return defer_candidates(c, level1, ncand, std::vector<int>(p1, p1 + n), std::vector<int>(pf, pf + n));
-}
-
-extern "C" int twosd_pool_build_candidates(twosd_ctx *c, int epi, const double *x, int first, int count, int level1,
-                                           int ncand) {
-    if (!c || !c->has_basis) return fail(TWOSD_E_STATE, "pool_build_candidates: no primary basis");
-    if (epi < 0 || epi >= (int)c->epis.size()) return fail(TWOSD_E_ARG, "pool_build_candidates: epigraph %d does not exist", epi);
-    const EpiDevice &E = c->epis[epi];
-    const int P = (int)c->pool.size();
-    if (first < 0 || count < 1 || first + count > E.count || level1 < 0 || ncand < 0 || ncand > 1024 || (c->n1 > 0 && !x))
-        return fail(TWOSD_E_ARG, "pool_build_candidates: bad arguments");
-    reset_candidates(c);
-    if (level1 == 0 || ncand == 0 || level1 >= P || P < 2 || c->CH <= 0) return TWOSD_OK;   // flat selection
-    HIPCHK(hipSetDevice(c->device));
-    std::vector<int> p1(count), pf(count);
-    int rc;
-    if ((rc = candidate_picks(c, E, x, first, count, level1, p1.data(), pf.data()))) return rc;
-    return defer_candidates(c, level1, ncand, std::move(p1), std::move(pf));
-}
-
-extern "C" int twosd_last_pool_picks(twosd_ctx *c, int N, int *picks) {
-    if (!c || !picks || N < 0 || N > c->last_lp_N) return fail(TWOSD_E_ARG, "last_pool_picks: bad arguments");
-    if (c->pool.size() <= 1 || !c->d_pool_pick) {
-        std::fill(picks, picks + N, 0);
-        return TWOSD_OK;
-    }
-    HIPCHK(hipMemcpy(picks, c->d_pool_pick, sizeof(int) * N, hipMemcpyDeviceToHost));
-    return TWOSD_OK;
-}
-
-extern "C" int twosd_invalidate_x(twosd_ctx *c) {
-    if (!c) return fail(TWOSD_E_ARG, "invalidate_x: NULL context");
-    c->prep_valid = false;   // (the cut's PK rows do not depend on x: kept)
     return TWOSD_OK;
 }
 
@@ -1102,6 +895,14 @@ int twosd::whole_groups(const char *who, const char *what, unsigned long long va
     return TWOSD_OK;
 }
 
+SampleParams twosd::sample_params(const twosd_ctx *c, int n, uint64_t seed, uint64_t first_index, double *out) {
+    SampleParams S{};
+    S.N = n; S.k = c->k; S.seed = seed; S.first_index = first_index;
+    S.kind = c->d_dist_kind; S.off = c->d_dist_off; S.val = c->d_dist_val; S.prob = c->d_dist_prob;
+    S.p0 = c->d_dist_p0; S.p1 = c->d_dist_p1; S.tmpl = c->d_dist_tmpl; S.out = out;
+    return S;
+}
+
 static int add_sampled(twosd_ctx *c, int epi, int N, uint64_t seed, uint64_t first_index, const double *weights, int mode,
                        int G);
 
@@ -1139,52 +940,12 @@ static int add_sampled(twosd_ctx *c, int epi, int N, uint64_t seed, uint64_t fir
     int rc;
     if ((rc = E.d_dv.grow((size_t)(E.count + N) * k, (size_t)E.count * k, c->stream))) return rc;
     if ((rc = E.d_w.grow((size_t)(E.count + N), (size_t)E.count, c->stream))) return rc;
-    SampleParams S{};
-    S.N = N; S.k = k; S.seed = seed; S.first_index = first_index;
-    S.kind = c->d_dist_kind; S.off = c->d_dist_off; S.val = c->d_dist_val; S.prob = c->d_dist_prob;
-    S.p0 = c->d_dist_p0; S.p1 = c->d_dist_p1; S.tmpl = c->d_dist_tmpl; S.out = E.d_dv + (size_t)E.count * k;
-    HIPCHK(launch_sample_plan(S, mode, G, c->stream));
+    HIPCHK(launch_sample_plan(sample_params(c, N, seed, first_index, E.d_dv + (size_t)E.count * k), mode, G, c->stream));
     HIPCHK(hipMemcpyAsync(E.d_w + E.count, w.data(), sizeof(double) * N, hipMemcpyHostToDevice, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
     E.w_host.insert(E.w_host.end(), w.begin(), w.end());
     for (int s = 0; s < N; ++s) E.total_weight += w[s];   // epigraph.jl:89, in insertion order
     E.count += N;
-    return TWOSD_OK;
-}
-
-static int copy_lp_outputs(twosd_ctx *c, int N, double *obj, double *pi, double *y, int *status, const double *d_w);
-
-// evaluate(sp1, sp2, sto, x; N) stage-2 part (smps_routines.jl:67-82) on device-drawn
-// scenarios: *s2 = sum over scenarios first..first+count-1 of the stream `seed`, in index
-// order, of (1/N_total) * obj (s2_cost += 1/N*obj, :79).  Chunks of <= 1M scenarios:
-// sample into scratch, LP solve (objective only), objectives summed on the host in order.
-extern "C" int twosd_evaluate_sampled(twosd_ctx *c, const double *x, int64_t N_total, int64_t first, int64_t count,
-                                      uint64_t seed, double *s2) {
-    if (!c || !c->has_template) return fail(TWOSD_E_STATE, "evaluate_sampled: no template");
-    if (!c->has_basis) return fail(TWOSD_E_STATE, "evaluate_sampled: no warm-start basis");
-    if (!c->has_dist) return fail(TWOSD_E_STATE, "evaluate_sampled: no distributions (twosd_set_distributions)");
-    if (!s2 || N_total <= 0 || first < 0 || count < 0 || (c->n1 > 0 && !x)) return fail(TWOSD_E_ARG, "evaluate_sampled: bad arguments");
-    HIPCHK(hipSetDevice(c->device));
-    const int k = c->k;
-    const int64_t chunk = 1 << 20;
-    const double invN = 1.0 / (double)N_total;
-    double acc = 0.0;
-    std::vector<double> obj;
-    for (int64_t at = 0; at < count; at += chunk) {
-        const int n = (int)std::min(chunk, count - at);
-        int rc;
-        if ((rc = c->d_dvtmp.grow((size_t)n * std::max(k, 1), 0, c->stream))) return rc;
-        SampleParams S{};
-        S.N = n; S.k = k; S.seed = seed; S.first_index = (unsigned long long)(first + at);
-        S.kind = c->d_dist_kind; S.off = c->d_dist_off; S.val = c->d_dist_val; S.prob = c->d_dist_prob;
-        S.p0 = c->d_dist_p0; S.p1 = c->d_dist_p1; S.tmpl = c->d_dist_tmpl; S.out = c->d_dvtmp;
-        HIPCHK(launch_sample(S, c->stream));
-        if ((rc = run_lp(c, x, c->d_dvtmp, n, false, false))) return rc;
-        obj.resize(n);
-        if ((rc = copy_lp_outputs(c, n, obj.data(), nullptr, nullptr, nullptr, nullptr))) return rc;
-        for (int i = 0; i < n; ++i) acc += invN * obj[i];
-    }
-    *s2 = acc;
     return TWOSD_OK;
 }
 
@@ -1206,1364 +967,5 @@ extern "C" int twosd_epigraph_info(twosd_ctx *c, int epi, int *ns, double *tw) {
     if (!c || epi < 0 || epi >= (int)c->epis.size()) return fail(TWOSD_E_ARG, "epigraph_info: bad epigraph");
     if (ns) *ns = c->epis[epi].count;
     if (tw) *tw = c->epis[epi].total_weight;
-    return TWOSD_OK;
-}
-
-// x-independent element data of the pool (rebuilt when the pool or the positions change):
-// per basis p the rows of B_p^{-1}[:, row_e] over the random elements e (host CSR kptr/ke/
-// kraw, e ascending) and the same as sliced ELL on the device (kslot pool-strided, absolute
-// into kix/kv).  The kernels multiply the scenario deltas by coef_e(x) (d_kcoef) themselves.
-int twosd::prepare_elements(twosd_ctx *c) {
-    const auto t_pe0 = std::chrono::steady_clock::now();
-    if (int rc0 = ensure_host_pool(c)) return rc0;
-    const int m = c->L.m, k = c->k, R = c->R;
-    std::vector<std::vector<int>> bycol(m);   // random elements on each row
-    for (int e = 0; e < k; ++e) bycol[c->pos_row[e]].push_back(e);
-    const int P = (int)c->pool.size();
-    std::vector<int8_t> bt(c->L.n + m);
-    HIPCHK(hipMemcpy(bt.data(), c->d_btype, bt.size(), hipMemcpyDeviceToHost));
-    // pass 1: per basis and row the number of element entries; CSR / ELL / record sizes
-    std::vector<int> rowcnt((size_t)P * m), width((size_t)P * R);
-    std::vector<size_t> kcnt(P + 1, 0), ecnt(P + 1, 0);
-    std::vector<int64_t> ccnt(P + 1, 0);
-    parallel_for(P, [&](int p) {
-        const PoolBasis &B = c->pool[p];
-        int *rc = rowcnt.data() + (size_t)p * m;
-        size_t tot = 0;
-        int64_t cp = 0;   // selection records: every row active; rows of fixed (E) basics twice
-        for (int i = 0; i < m; ++i) {
-            int n_i = 0;
-            for (int q = B.rptr[i]; q < B.rptr[i + 1]; ++q) n_i += (int)bycol[B.rcol[q]].size();
-            rc[i] = n_i;
-            tot += n_i;
-            cp += (int64_t)(1 + n_i) * (bt[B.head[i]] == BT_E ? 2 : 1);
-        }
-        size_t ell = 0;
-        for (int t = 0; t < R; ++t) {
-            int w = 0;
-            for (int l = 0; l < 64 && 64 * t + l < m; ++l) w = std::max(w, rc[64 * t + l]);
-            width[(size_t)p * R + t] = w;
-            ell += (size_t)w * 64;
-        }
-        kcnt[p + 1] = tot;
-        ecnt[p + 1] = ell;
-        ccnt[p + 1] = cp;
-    });
-    for (int p = 0; p < P; ++p) { kcnt[p + 1] += kcnt[p]; ecnt[p + 1] += ecnt[p]; ccnt[p + 1] += ccnt[p]; }
-    if (kcnt[P] > INT32_MAX || ecnt[P] / 64 > INT32_MAX || ccnt[P] > INT32_MAX)
-        return fail(TWOSD_E_UNSUPPORTED, "basis pool element data too large (> 2^31 entries)");
-    // pass 2: rows of B_p^{-1}[:, row_e] (e ascending) as CSR (selection inputs) and sliced ELL
-    // by row (x_B warm start of the LP kernel), written in place
-    const size_t kz = std::max<size_t>(kcnt[P], 1), ez = std::max<size_t>(ecnt[P], 1);
-    std::vector<int> kp((size_t)P * (m + 1)), ks((size_t)P * (R + 1)), cap(P + 1);
-    int *ke = c->stage[STG_ELEM_KE].reserve<int>(kz), *ki = c->stage[STG_ELEM_KIX].reserve<int>(ez);
-    double *kr = c->stage[STG_ELEM_KRAW].reserve<double>(kz), *kv = c->stage[STG_ELEM_KV].reserve<double>(ez);
-    if (!ke || !ki || !kr || !kv) return fail(TWOSD_E_DEVICE, "pool elements: pinned staging allocation failed");
-    for (int p = 0; p <= P; ++p) cap[p] = (int)ccnt[p];
-    parallel_for(P, [&](int p) {
-        const PoolBasis &B = c->pool[p];
-        const int *rc = rowcnt.data() + (size_t)p * m;
-        std::vector<std::pair<int, double>> row;
-        size_t at = kcnt[p];
-        const size_t e_row0 = ecnt[p] / 64;   // first ELL entry row of this basis
-        size_t so = 0;                        // slot offset (entry rows) within the basis
-        for (int t = 0; t <= R; ++t) {
-            ks[(size_t)p * (R + 1) + t] = (int)(e_row0 + so);
-            if (t < R) so += width[(size_t)p * R + t];
-        }
-        for (int i = 0; i < m; ++i) {
-            row.clear();
-            for (int q = B.rptr[i]; q < B.rptr[i + 1]; ++q)
-                for (int e : bycol[B.rcol[q]]) row.push_back({e, B.rval[q]});
-            std::sort(row.begin(), row.end());
-            kp[(size_t)p * (m + 1) + i] = (int)at;
-            for (auto &ev : row) { ke[at] = ev.first; kr[at] = ev.second; ++at; }
-        }
-        kp[(size_t)p * (m + 1) + m] = (int)at;
-        (void)rc;
-        for (int t = 0; t < R; ++t) {
-            const int w = width[(size_t)p * R + t];
-            const size_t r0 = (size_t)ks[(size_t)p * (R + 1) + t];
-            for (int l = 0; l < 64; ++l) {
-                const int i = 64 * t + l;
-                const int q0 = i < m ? kp[(size_t)p * (m + 1) + i] : 0, q1 = i < m ? kp[(size_t)p * (m + 1) + i + 1] : 0;
-                for (int e = 0; e < w; ++e) {
-                    const bool has = q0 + e < q1;
-                    ki[(r0 + e) * 64 + l] = has ? ke[q0 + e] : 0;
-                    kv[(r0 + e) * 64 + l] = has ? kr[q0 + e] : 0.0;
-                }
-            }
-        }
-    });
-    const auto t_pe1 = std::chrono::steady_clock::now();
-    int rc;
-    if (c->CH > 0 && ((rc = c->d_kslot.upload_reserve(ks)) || (rc = c->d_kix.upload_reserve(ki, ecnt[P])) ||
-                      (rc = c->d_kv.upload_reserve(kv, ecnt[P]))))
-        return rc;
-    const auto t_pe2 = std::chrono::steady_clock::now();
-    if (c->CH > 0 && P > 1) {
-        // device selection-stream inputs: CSR rows of every basis, and a static record capacity
-        // per basis (every row active: m row starts + all its entries)
-        if ((rc = c->d_kp.upload_reserve(kp)) || (rc = c->d_ke.upload_reserve(ke, kz)) || (rc = c->d_kraw.upload_reserve(kr, kz)) ||
-            (rc = c->d_sel_ptr.upload_reserve(cap)) || (rc = reserve_selection(c, P, cap[P])))
-            return rc;
-    }
-    c->k_valid = true;
-    if (getenv("TWOSD_DEBUG")) {
-        auto ms = [](auto a, auto b) { return std::chrono::duration<double, std::milli>(b - a).count(); };
-        fprintf(stderr, "prepare_elements P=%d: build %.1f ms, upload ell %.1f ms (%zu entries), selection inputs %.1f ms\n",
-                P, ms(t_pe0, t_pe1), ms(t_pe1, t_pe2), ecnt[P], ms(t_pe2, std::chrono::steady_clock::now()));
-    }
-    return TWOSD_OK;
-}
-
-// x_B of every pool basis at b: xbase[p][i] = sum_q B_p^{-1}[i][col_q] b[col_q] over the CSR
-// rows (pool-strided brptr, MP + 1 per basis; rows >= m are empty), q ascending
-__global__ void pool_xbase_kernel(int P, int MP, const int *__restrict__ brptr, const int *__restrict__ brcol,
-                                  const double *__restrict__ brval, const double *__restrict__ b, double *__restrict__ xbase) {
-    const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (t >= (size_t)P * MP) return;
-    const size_t p = t / MP, i = t - p * MP;
-    const int *rp = brptr + p * (MP + 1);
-    double s = 0.0;
-    int q = rp[i];
-    const int q1 = rp[i + 1];
-    // four entries' loads in flight together; the fmas stay in column order (same bits)
-    for (; q + 4 <= q1; q += 4) {
-        const int c0 = brcol[q], c1 = brcol[q + 1], c2 = brcol[q + 2], c3 = brcol[q + 3];
-        const double v0 = brval[q], v1 = brval[q + 1], v2 = brval[q + 2], v3 = brval[q + 3];
-        const double b0 = b[c0], b1 = b[c1], b2 = b[c2], b3 = b[c3];
-        s = fma(v0, b0, s);
-        s = fma(v1, b1, s);
-        s = fma(v2, b2, s);
-        s = fma(v3, b3, s);
-    }
-    for (; q < q1; ++q) s = fma(brval[q], b[brcol[q]], s);
-    xbase[t] = s;
-}
-
-// primal infeasibility of a basic variable at value x (h_infeas of lp_hyper.hip, tolerance 1e-9)
-__device__ __forceinline__ double dev_infeas(double x, int bt) {
-    const double tol = 1e-9;
-    if (bt == BT_Y || bt == BT_L) return x < -tol ? x : 0.0;
-    if (bt == BT_G) return x > tol ? x : 0.0;
-    return fabs(x) > tol ? x : 0.0;
-}
-
-// Selection stream of one pool basis per block (prepare_x, per x; hb0 = head * 4 + bound type): the rows of basis p that can
-// turn infeasible on the training box of the deltas, ordered by their worst box infeasibility
-// (largest first, row index on ties), each written as a row-start record (sign-folded
-// x_B,i, the sentinel offset k * 65 * 8) followed by its element entries (e, B_p^{-1}[i][row_e]) at the basis's static capacity
-// offset; rows without entries add their constant infeasibility to cinf[p] (fixed-order sum).
-constexpr int kSelStreamThreads = 256;
-// count weight of the selection key in units of the mean |coef_e| E|V_e - E V_e| (storm: 13.5;
-// 1M bench: 0 -> 111.5 ms per step, 0.37 - 0.74 -> 105.5 - 105.8, 1.5 -> 112, 3 -> 115; ssn: no effect)
-constexpr double kSelCountWeight = 0.5;
-constexpr int kSelStreamRows = 1024;   // MP <= 1024 (R <= 16)
-__global__ void __launch_bounds__(kSelStreamThreads) pool_selstream_kernel(
-    int m, int MP, int k, const double *__restrict__ xbase, const int *__restrict__ hb0,
-    const int *__restrict__ kp, const int *__restrict__ ke, const double *__restrict__ kraw, const double *__restrict__ xaux,
-    int box, int order_rows, float cw, const int *__restrict__ scap, int2 *__restrict__ rec, int *__restrict__ send,
-    float *__restrict__ cinf) {
-    __shared__ double skey[kSelStreamRows];
-    __shared__ int sidx[kSelStreamRows];
-    __shared__ int soff[kSelStreamRows];
-    __shared__ float cpart[kSelStreamThreads];
-    __shared__ int tsum[kSelStreamThreads];
-    const int p = blockIdx.x, tid = threadIdx.x;
-    const double *coef = xaux + m, *lo_e = xaux + m + k, *hi_e = xaux + m + 2 * k;
-    const int *kpp = kp + (size_t)p * (m + 1);
-    float cf = 0.0f;
-    for (int i = tid; i < kSelStreamRows; i += kSelStreamThreads) {
-        double key = INFINITY;   // inactive rows sort last
-        if (i < m) {
-            const int t = (hb0[(size_t)p * MP + i] & 3);
-            const double xv = xbase[(size_t)p * MP + i];
-            const int q0 = kpp[i], q1 = kpp[i + 1];
-            if (q0 == q1) {
-                const double f = fabs(dev_infeas(xv, t));
-                cf += (float)f + (f > 0.0 ? cw : 0.0f);
-            } else {
-                double worst = 0.0;
-                bool active = true;
-                if (box) {
-                    double lo = xv, hi = xv, mag = fabs(xv);
-                    for (int q = q0; q < q1; ++q) {
-                        const int e = ke[q];
-                        const double g = coef[e] * kraw[q];
-                        const double a = g * lo_e[e], bb = g * hi_e[e];
-                        lo += fmin(a, bb);
-                        hi += fmax(a, bb);
-                        mag += fmax(fabs(a), fabs(bb));
-                    }
-                    const double tol = 1e-9 + 1e-12 * mag;
-                    const bool feasible_box = (t == BT_Y || t == BT_L) ? lo > tol : (t == BT_G) ? hi < -tol : false;
-                    if (isfinite(lo) && isfinite(hi) && feasible_box) active = false;
-                    worst = (t == BT_Y || t == BT_L) ? -lo : (t == BT_G) ? hi : fmax(fabs(lo), fabs(hi));
-                    if (!isfinite(worst)) worst = HUGE_VAL;
-                }
-                if (active) key = order_rows ? -worst : 0.0;
-            }
-        }
-        skey[i] = key;
-        sidx[i] = i;
-    }
-    cpart[tid] = cf;
-    __syncthreads();
-    // bitonic sort of (key, row) ascending: (-worst, i) lexicographic = the host's stable sort
-    for (int kk = 2; kk <= kSelStreamRows; kk <<= 1) {
-        for (int j = kk >> 1; j > 0; j >>= 1) {
-            for (int t2 = tid; t2 < kSelStreamRows / 2; t2 += kSelStreamThreads) {
-                const int a = 2 * j * (t2 / j) + (t2 % j), b2 = a + j;
-                const bool up = (a & kk) == 0;
-                const double ka = skey[a], kb = skey[b2];
-                const int ia = sidx[a], ib = sidx[b2];
-                const bool gt = ka > kb || (ka == kb && ia > ib);
-                if (gt == up) {
-                    skey[a] = kb; skey[b2] = ka;
-                    sidx[a] = ib; sidx[b2] = ia;
-                }
-            }
-            __syncthreads();
-        }
-    }
-    // records per sorted position, exclusive scan (4 consecutive positions per thread)
-    constexpr int PER = kSelStreamRows / kSelStreamThreads;
-    int loc[PER], run = 0;
-#pragma unroll
-    for (int u = 0; u < PER; ++u) {
-        const int sp = tid * PER + u;
-        const int i = sidx[sp];
-        const int c = skey[sp] != INFINITY ? (1 + kpp[i + 1] - kpp[i]) * ((hb0[(size_t)p * MP + i] & 3) == BT_E ? 2 : 1) : 0;
-        loc[u] = run;
-        run += c;
-    }
-    tsum[tid] = run;
-    __syncthreads();
-    if (tid == 0) {   // fixed-order sums: 256 partials (records, constant-row infeasibility)
-        int acc = 0;
-        float cacc = 0.0f;
-        for (int t = 0; t < kSelStreamThreads; ++t) {
-            const int v = tsum[t];
-            tsum[t] = acc;
-            acc += v;
-            cacc += cpart[t];
-        }
-        send[p] = scap[p] + acc;
-        cinf[p] = cacc;
-    }
-    __syncthreads();
-#pragma unroll
-    for (int u = 0; u < PER; ++u) soff[tid * PER + u] = tsum[tid] + loc[u];
-    __syncthreads();
-    // emit: one wave per sorted row at a time, the row's entries written by consecutive lanes
-    const int lane = tid & 63, wv = tid >> 6;
-    const size_t base = (size_t)scap[p];
-    for (int sp = wv; sp < kSelStreamRows; sp += kSelStreamThreads / 64) {
-        if (skey[sp] == INFINITY) break;   // sorted: the inactive rows are all at the end
-        const int i = sidx[sp];
-        const int q0 = kpp[i], q1 = kpp[i + 1];
-        int2 *out = rec + base + soff[sp];
-        // records are sign-folded so that the kernels' test is always "x' > tol": x' = -x for
-        // Y / L basics (infeasible below 0), x for G (above 0); a fixed (E) basic is written
-        // twice, with +x and -x (|x| > tol <=> one of them > tol)
-        const int t = hb0[(size_t)p * MP + i] & 3;
-        const int ncopy = t == BT_E ? 2 : 1;
-        for (int cpy = 0; cpy < ncopy; ++cpy) {
-            const float sg = (t == BT_Y || t == BT_L || cpy == 1) ? -1.0f : 1.0f;
-            int2 *o = out + cpy * (1 + q1 - q0);
-            // record (value bits, byte offset of the element's staged pair row e * 65 * 8; row start: the
-            // offset of row k, which the selection kernels keep zeroed)
-            if (lane == 0) o[0] = make_int2(__float_as_int(sg * (float)xbase[(size_t)p * MP + i]), k * 65 * 8);
-            for (int q = q0 + lane; q < q1; q += 64) o[1 + q - q0] = make_int2(__float_as_int(sg * (float)kraw[q]), ke[q] * 65 * 8);
-        }
-    }
-}
-
-// per-x shared data: b = r - T x; per pool basis xbase_p = B_p^{-1} b (sparse rows);
-// coef_e(x); with a pool, the
-// selection stream (active rows that can turn infeasible on the training box of the deltas).
-// Every pool basis is independent, so the per-basis work runs on host threads.
-int twosd::prepare_x(twosd_ctx *c, const double *x) {
-    const int m = c->L.m, MP = c->MP, k = c->k, n1 = c->n1;
-    if (c->prep_valid && c->prep_x.size() == (size_t)n1 && (n1 == 0 || std::equal(c->prep_x.begin(), c->prep_x.end(), x)))
-        return TWOSD_OK;
-    int rc;
-    const auto t_start = std::chrono::steady_clock::now();
-    if (!c->k_valid && (rc = prepare_elements(c))) return rc;
-    std::vector<double> b;
-    rhs_at(c, x, nullptr, b);
-    const int P = (int)c->pool.size();
-    std::vector<double> coef(std::max(k, 1), 1.0);
-    for (int e = 0; e < k; ++e) coef[e] = c->pos_col[e] < 0 ? 1.0 : -x[c->pos_col[e]];
-    if ((rc = c->d_xbase.fit((size_t)P * MP))) return rc;
-    if (c->CH > 0) {
-        // everything per x on the device: one upload of [b, coef, box lo, box hi], x_B of every
-        // pool basis, then the selection stream (pool_selstream_kernel)
-        const bool sel = P > 1;
-        const bool box = !c->sel_lo.empty();
-        std::vector<double> aux((size_t)m + 3 * (size_t)k, 0.0);
-        std::copy(b.begin(), b.end(), aux.begin());
-        std::copy(coef.begin(), coef.begin() + k, aux.begin() + m);
-        if (box) {
-            std::copy(c->sel_lo.begin(), c->sel_lo.end(), aux.begin() + m + k);
-            std::copy(c->sel_hi.begin(), c->sel_hi.end(), aux.begin() + m + 2 * k);
-        }
-        // re-uploaded in place: no reallocation per x
-        if ((rc = c->d_xaux.fit(aux.size())) || (rc = c->d_xaux.copy_from(aux.data(), aux.size())) ||
-            (rc = c->d_kcoef.fit(coef.size())) || (rc = c->d_kcoef.copy_from(coef.data(), coef.size())))
-            return rc;
-        const size_t tot = (size_t)P * MP;
-        hipLaunchKernelGGL(pool_xbase_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, c->stream, P, MP, c->d_brptr,
-                           c->d_brcol, c->d_brval, c->d_xaux, c->d_xbase);
-        HIPCHK(hipGetLastError());
-        if (sel) {
-            if (MP > kSelStreamRows) return fail(TWOSD_E_UNSUPPORTED, "pool selection: m = %d rows > %d", m, kSelStreamRows);
-            // count weight of the selection key: kSelCountWeight x the mean over the random elements
-            // of |coef_e(x)| E|V_e - E V_e| (one infeasible row is worth about half a typical
-            // scenario perturbation), 0 without distributions.  The same on every rank.
-            double sc = 0.0;
-            if (c->has_dist && k > 0) {
-                for (int e = 0; e < k; ++e) sc += fabs(coef[e]) * c->dist_mad[e];
-                sc /= k;
-            }
-            c->sel_cw = (float)(kSelCountWeight * sc);
-            if (const char *e = getenv("TWOSD_SEL_CW")) c->sel_cw = (float)atof(e);   // selection-key experiments
-            static const bool sel_order = !getenv("TWOSD_SEL_ROWORDER") || atoi(getenv("TWOSD_SEL_ROWORDER")) != 0;   // A/B knob
-            hipLaunchKernelGGL(pool_selstream_kernel, dim3(P), dim3(kSelStreamThreads), 0, c->stream, m, MP, k, c->d_xbase,
-                               c->d_hb0, c->d_kp, c->d_ke, c->d_kraw, c->d_xaux, box ? 1 : 0, sel_order ? 1 : 0,
-                               c->sel_cw, c->d_sel_ptr, reinterpret_cast<int2 *>(c->d_sel_code.p), c->d_sel_end, c->d_sel_cinf);
-            HIPCHK(hipGetLastError());
-        }
-        if (getenv("TWOSD_DEBUG") && sel) {
-            HIPCHK(hipStreamSynchronize(c->stream));
-            std::vector<int> beg(P + 1), end(P);
-            HIPCHK(hipMemcpy(beg.data(), c->d_sel_ptr, sizeof(int) * (P + 1), hipMemcpyDeviceToHost));
-            HIPCHK(hipMemcpy(end.data(), c->d_sel_end, sizeof(int) * P, hipMemcpyDeviceToHost));
-            c->sel_nnz = 0;
-            for (int p = 0; p < P; ++p) c->sel_nnz += end[p] - beg[p];
-            c->sel_rows = 0;
-        }
-    }
-    c->prep_x.assign(x, x + n1);
-    c->prep_valid = true;
-    if (getenv("TWOSD_DEBUG")) {
-        HIPCHK(hipStreamSynchronize(c->stream));
-        fprintf(stderr, "prepare_x: P=%d %.3f ms (%lld selection records)\n", P,
-                std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_start).count(),
-                (long long)(c->sel_nnz + c->sel_rows));
-    }
-    return TWOSD_OK;
-}
-
-// Warm-start selection for scenarios [0, N) at the prepared x: pick[s] = pool basis, and
-// c->d_order = the scenarios grouped by pick (stable).  Flat: least key over the whole pool.
-// Two-level (pool_l1 > 0): least key over pool[0, pool_l1), then over the candidates of that
-// pick.  npool_override > 0: flat over pool[0, npool_override) (candidate training).
-static int select_pool(twosd_ctx *c, const double *d_dv, int N, int *d_pick, int npool_override) {
-    const int P = (int)c->pool.size();
-    const bool two = npool_override <= 0 && c->pool_l1 > 0 && c->pool_l1 < P && c->pool_ncand > 0 && (c->d_cand || c->cand_pending);
-    const int np1 = npool_override > 0 ? npool_override : two ? c->pool_l1 : P;
-    int rc;
-    size_t tb = 0, tb2 = 0;
-    HIPCHK(sort_by_pool(d_pick, nullptr, N, P, nullptr, &tb, c->stream));
-    HIPCHK(sort_by_pool(d_pick, nullptr, N, np1, nullptr, &tb2, c->stream));
-    tb = std::max(tb, tb2);
-    if ((size_t)N > c->d_order.cap || tb > c->d_sort_tmp.cap) {   // both at once, as one workspace
-        if ((rc = c->d_order.alloc((size_t)N)) || (rc = c->d_sort_tmp.alloc(tb))) return rc;
-    }
-    if (two && (rc = c->d_sel_key.fit((size_t)N))) return rc;
-    // partials of the chunked selections (small batches: several pool chunks per scenario tile)
-    const int g1 = pool_select_split(N, np1), g2 = two ? pool_refine_split(N, c->pool_ncand) : 1;
-    const size_t pneed = (size_t)std::max(g1, g2) * N;
-    if (std::max(g1, g2) > 1 && ((rc = c->d_sel_pkey.fit(pneed)) || (rc = c->d_sel_ppick.fit(pneed)))) return rc;
-    PoolSelParams S{};
-    S.N = N; S.k = c->k; S.npool = np1; S.dv = d_dv;
-    S.kcoef = c->d_kcoef;
-    S.cinf = c->d_sel_cinf; S.sptr = c->d_sel_ptr; S.send = c->d_sel_end; S.rec = reinterpret_cast<const int2 *>(c->d_sel_code.p);
-    S.pick = d_pick;
-    S.cw = c->sel_cw;
-    S.key = two ? c->d_sel_key : nullptr;
-    S.pkey = g1 > 1 ? c->d_sel_pkey : nullptr;
-    S.ppick = g1 > 1 ? c->d_sel_ppick : nullptr;
-    HIPCHK(launch_pool_select(S, c->stream));
-    if (two && c->cand_pending &&
-        (rc = set_candidates(c, c->cand_pl1, c->cand_pnc, (int)c->cand_p1.size(), c->cand_p1.data(), c->cand_pf.data())))
-        return rc;
-    if (two) {
-        HIPCHK(sort_by_pool(d_pick, c->d_order, N, np1, c->d_sort_tmp, &tb, c->stream));
-        PoolRefineParams Q{};
-        Q.N = N; Q.k = c->k; Q.ncand = c->pool_ncand; Q.dv = d_dv; Q.kcoef = c->d_kcoef;
-        Q.cinf = c->d_sel_cinf; Q.sptr = c->d_sel_ptr; Q.send = c->d_sel_end; Q.rec = S.rec;
-        Q.order = c->d_order; Q.cand = c->d_cand; Q.pick = d_pick; Q.key = c->d_sel_key; Q.cw = c->sel_cw;
-        Q.pkey = g2 > 1 ? c->d_sel_pkey : nullptr;
-        Q.pci = g2 > 1 ? c->d_sel_ppick : nullptr;
-        HIPCHK(launch_pool_refine(Q, c->stream));
-    }
-    HIPCHK(sort_by_pool(d_pick, c->d_order, N, P, c->d_sort_tmp, &tb, c->stream));
-    return TWOSD_OK;
-}
-
-// Launch the LP kernel over N scenarios whose deltas start at d_dv (device); results in
-// c->d_obj / d_pi / d_y / d_status / d_iters [0, N).
-int twosd::run_lp(twosd_ctx *c, const double *x, const double *d_dv, int N, bool want_pi, bool want_y) {
-    LpRun o;
-    o.want_pi = want_pi;
-    o.want_y = want_y;
-    return run_lp_ex(c, x, d_dv, N, o);
-}
-
-// N = scenarios of d_dv addressed by the launch (outputs obj / status / iters / pool picks are
-// indexed by scenario); list mode solves only o.d_list[0, o.nlist) from their recorded picks
-// and writes pi at the list position
-int twosd::run_lp_ex(twosd_ctx *c, const double *x, const double *d_dv, int N, const LpRun &o) {
-    const bool want_pi = o.want_pi, want_y = o.want_y;
-    const bool list = o.d_list != nullptr;
-    const int NL = list ? o.nlist : N;   // scenarios this launch solves
-    int rc;
-    if ((rc = prepare_x(c, x))) return rc;
-    if (list && c->pool.size() > 1 && (size_t)N > c->d_pool_pick.cap) return fail(TWOSD_E_STATE, "LP list mode: no recorded pool picks");
-    const int m = c->L.m, n = c->L.n, MP = c->MP, R = c->R;
-    if (N > c->out_cap) {
-        size_t cap = std::max<size_t>(N, 1024);
-        if ((rc = c->d_obj.alloc(cap)) || (rc = c->d_status.alloc(cap)) || (rc = c->d_iters.alloc(cap)) ||
-            (rc = c->d_ops.alloc(cap)) || (rc = c->d_etan.alloc(cap)))
-            return rc;
-        c->d_pi.release(); c->d_y.release();
-        c->out_cap = (int)cap;
-    }
-    // the optional outputs, out_cap rows each, on their first use at this out_cap
-    if (want_pi && (size_t)NL * m > c->d_pi.cap && (rc = c->d_pi.alloc((size_t)c->out_cap * m))) return rc;
-    if (o.want_key && (size_t)N > c->d_vkey.cap && (rc = c->d_vkey.alloc((size_t)c->out_cap))) return rc;
-    if (o.want_bkey && (size_t)N > c->d_bkey.cap && (rc = c->d_bkey.alloc((size_t)c->out_cap))) return rc;
-    if (want_y && (size_t)N * n > c->d_y.cap && (rc = c->d_y.alloc((size_t)c->out_cap * n))) return rc;
-    if (!c->d_queue && (rc = c->d_queue.alloc((size_t)kMaxQueueGroups * kQueueStride))) return rc;
-    {
-        // eta capacity (pivots per scenario): 2m + 32, at least 64.  256 keeps storm's two 4-wave
-        // blocks per CU within the LDS; past 256 the file grows (up to 1024, in steps of 32) as far as
-        // the LDS keeps the occupancy of 256 -- a scenario that needs more pivots from its pool start
-        // than the file holds is retried from the primary basis (ssn 100k: 11 in 8 steps at 256)
-        const int CH = c->CH;
-        int kmax = c->kmax_override > 0 ? c->kmax_override : std::min(256, std::max(64, 2 * m + 32));
-        if (c->kmax_override <= 0 && 2 * m + 32 > kmax) {
-            const int b0 = hyper_max_blocks_per_cu(R, CH, kmax, c->k);
-            for (int k2 = std::min(1024, (2 * m + 32) & ~31); k2 > kmax; k2 -= 32)
-                if (hyper_max_blocks_per_cu(R, CH, k2, c->k) >= b0) { kmax = k2; break; }
-        }
-        // per-wave eta arena: 32 entries per row, scaled with the file past 256 pivots
-        const int ecap = (int)std::min<long long>(INT32_MAX / 2, (long long)std::max(4096, 32 * MP) * std::max(256, kmax) / 256);
-        int bpc = hyper_max_blocks_per_cu(R, CH, kmax, c->k);
-        if (const char *e = getenv("TWOSD_BPC")) bpc = std::min(bpc, std::max(1, atoi(e)));   // diagnostics: occupancy sweep
-        if (bpc < 1)
-            return fail(TWOSD_E_UNSUPPORTED, "LP kernel: LDS slice too large (m2 = %d, n2 = %d; LP: %d rows, %d columns; k = %d)",
-                        c->m2_user, c->n2_user, m, n, c->k);
-        const int nblocks = std::max(1, std::min((NL + kWavesPerBlock - 1) / kWavesPerBlock, bpc * c->num_cus));
-        const size_t slots = (size_t)nblocks * kWavesPerBlock;
-        if (slots > c->earena_slots || ecap != c->earena_cap) {
-            if ((rc = c->d_eidx.alloc(slots * ecap)) || (rc = c->d_evals.alloc(slots * ecap))) return rc;
-            c->earena_slots = slots;
-            c->earena_cap = ecap;
-        }
-        HIPCHK(hipMemsetAsync(c->d_queue, 0, sizeof(int) * kMaxQueueGroups * kQueueStride, c->stream));
-        HyperParams H{};
-        H.m = m; H.n = n; H.k = c->k; H.N = NL; H.kmax = kmax; H.ecap = ecap;
-        H.kcap = o.kcap > 0 ? std::min(o.kcap, kmax) : kmax;
-        H.retry = o.kcap > 0 ? 0 : 1;
-        H.colptr = c->d_colptr; H.rowidx = c->d_rowidx; H.val = c->d_val; H.q = c->d_q; H.btype = c->d_btype;
-        H.wcp = c->d_wcp; H.wcc = c->d_wcc; H.wcv = c->d_wcv;
-        H.bcp = c->d_bcp; H.bci = c->d_bci; H.bcv = c->d_bcv;
-        H.brptr = c->d_brptr; H.brcol = c->d_brcol; H.brval = c->d_brval;
-        H.kslot = c->d_kslot; H.kix = c->d_kix; H.kv = c->d_kv; H.kcoef = c->d_kcoef;
-        H.xbase = c->d_xbase; H.d0 = c->d_d0; H.hb0 = c->d_hb0;
-        H.basic0 = c->d_basic0; H.fixedmask = c->d_fixedmask; H.ubmask = c->d_ubmask;
-        H.dv = d_dv; H.eidx = c->d_eidx; H.evals = c->d_evals; H.queue = c->d_queue;
-        H.qgroups = std::max(1, std::min(16, nblocks));   // two ranges per XCD (8 / 16 / 32 / 64: 143.6 / 142.7 / 142.8 / 146.3 ms, storm 1M)
-        if (const char *e = getenv("TWOSD_QGROUPS")) H.qgroups = std::max(1, std::min({kMaxQueueGroups, nblocks, atoi(e)}));   // A/B knob
-        H.obj = c->d_obj; H.pi = want_pi ? c->d_pi : nullptr; H.y = want_y ? c->d_y : nullptr;
-        H.vkey = o.want_key ? c->d_vkey : nullptr;
-        H.key_zero = 1e-12;   // = HPI_ZERO of the pi recovery (lp_hyper.hip)
-        if (const char *e = getenv("TWOSD_KEY_ZERO")) H.key_zero = atof(e);   // A/B knob
-        H.bkey = o.want_bkey ? c->d_bkey : nullptr;
-        if (o.want_etas) {   // rows: list positions, or scenarios
-            const size_t need = list ? (size_t)NL : (size_t)N;
-            // eta-file offsets are 32-bit (eo_off, the device pool build): the arena of
-            // 4096 entries per row must stay below 2^31 entries
-            if (need * 4096 > (size_t)INT32_MAX)
-                return fail(TWOSD_E_UNSUPPORTED, "eta files of %zu solves exceed the 2^31-entry arena (at most %d)", need,
-                            INT32_MAX / 4096);
-            // the arena: 4096 entries per row, or what an earlier training run asked for
-            // (refresh_training solves again when the eta files did not fit)
-            const size_t cap_need = std::max(std::max<size_t>(need, 256) * 4096, c->eo_min_cap);
-            if (need > c->eo_rows || c->eo_kmax != kmax || c->eo_cap < cap_need) {
-                const size_t rows = std::max<size_t>(need, 256);
-                if ((rc = c->d_eo_pb.alloc(rows)) || (rc = c->d_eo_K.alloc(rows)) || (rc = c->d_eo_off.alloc(rows)) ||
-                    (rc = c->d_eo_etap.alloc(rows * kmax)) || (rc = c->d_eo_etaoff.alloc(rows * (kmax + 1))) ||
-                    (rc = c->d_eo_eidx.alloc(cap_need)) || (rc = c->d_eo_evals.alloc(cap_need)))
-                    return rc;
-                if (!c->d_eo_used && (rc = c->d_eo_used.alloc(1))) return rc;
-                c->eo_rows = rows;
-                c->eo_cap = cap_need;
-                c->eo_kmax = kmax;
-            }
-            HIPCHK(hipMemsetAsync(c->d_eo_used, 0, sizeof(unsigned long long), c->stream));
-            H.eo_pb = c->d_eo_pb; H.eo_K = c->d_eo_K; H.eo_off = c->d_eo_off; H.eo_etap = c->d_eo_etap;
-            H.eo_etaoff = c->d_eo_etaoff; H.eo_eidx = c->d_eo_eidx; H.eo_evals = c->d_eo_evals; H.eo_used = c->d_eo_used;
-            H.eo_cap = (long long)std::min<size_t>(c->eo_cap, INT32_MAX);
-        }
-        if (o.want_head) {   // rows: list positions, or scenarios
-            const size_t need = list ? (size_t)NL : (size_t)N;
-            if ((rc = c->d_head_out.fit(need * m))) return rc;
-            H.head_out = c->d_head_out;
-        }
-        H.pi_by_pos = list ? 1 : 0;
-        H.status = c->d_status; H.iters = c->d_iters; H.ops = c->d_ops; H.etan = c->d_etan;
-        if (!c->d_lpstats && (rc = c->d_lpstats.alloc(6))) return rc;
-        if (!list) HIPCHK(hipMemsetAsync(c->d_lpstats + 5, 0, sizeof(unsigned long long), c->stream));
-        H.retries = list ? nullptr : c->d_lpstats + 5;   // a list re-solve repeats recorded picks: no retries
-        if (!c->d_stamps) {
-            if ((rc = c->d_stamps.alloc(16))) return rc;
-            HIPCHK(hipMemset(c->d_stamps, 0, sizeof(unsigned long long) * 16));
-        }
-        H.stamps = c->d_stamps;
-        H.npool = (int)c->pool.size();
-        H.bnnz = c->d_bnnz;
-        if (c->want_head && !list) {
-            if ((rc = c->d_head_out.fit((size_t)N * m))) return rc;
-            H.head_out = c->d_head_out;
-        }
-        if (H.npool > 1) {
-            if (!list && (rc = c->d_pool_pick.fit((size_t)N))) return rc;
-            H.pool_pick = c->d_pool_pick;
-        }
-        if (!list && c->d_kslot && getenv("TWOSD_DEBUG")) {
-            // w, the widest ELL slot of a start basis: the x_B warm start walks w columns
-            std::vector<int> ks((size_t)H.npool * (R + 1));
-            HIPCHK(hipMemcpy(ks.data(), c->d_kslot, sizeof(int) * ks.size(), hipMemcpyDeviceToHost));
-            std::vector<int> ws(H.npool);
-            double mean = 0;
-            for (int p = 0; p < H.npool; ++p) {
-                int w = 0;
-                for (int t = 0; t < R; ++t) w = std::max(w, ks[(size_t)p * (R + 1) + t + 1] - ks[(size_t)p * (R + 1) + t]);
-                ws[p] = w;
-                mean += w;
-            }
-            std::sort(ws.begin(), ws.end());
-            fprintf(stderr, "LP start: ELL width w over %d bases: min %d, median %d, mean %.2f, p90 %d, max %d\n", H.npool, ws.front(),
-                    ws[ws.size() / 2], mean / H.npool, ws[ws.size() * 9 / 10], ws.back());
-        }
-        HIPCHK(hipEventRecord(c->ev[0], c->stream));
-        const int *order = nullptr;
-        if (list) {
-            order = o.d_list;
-        } else if (H.npool > 1) {
-            if ((rc = select_pool(c, d_dv, N, c->d_pool_pick, 0))) return rc;
-            order = c->d_order;
-        }
-        HIPCHK(hipEventRecord(c->ev[2], c->stream));
-        // one record per queue position (its scenario and start basis), so that a wave learns both
-        // from its claim in one load; part of the timed LP launch.  Neither an order nor a pool:
-        // position q is scenario q from the primary basis and the kernel reads no record.
-        if (order || H.npool > 1) {
-            if ((rc = c->d_qrec.fit(std::max<size_t>(NL, 1024)))) return rc;
-            HIPCHK(launch_queue_records(order, H.npool > 1 ? c->d_pool_pick : nullptr, c->d_qrec, NL, c->stream));
-            H.qrec = c->d_qrec;
-        }
-        HIPCHK(launch_hyper(R, CH, H, nblocks, hyper_lds_bytes(R, CH, kmax, c->k), c->stream));
-        HIPCHK(hipEventRecord(c->ev[1], c->stream));
-        HIPCHK(hipStreamSynchronize(c->stream));
-        float ms = 0, ms_sel = 0;
-        hipEventElapsedTime(&ms, c->ev[2], c->ev[1]);
-        hipEventElapsedTime(&ms_sel, c->ev[0], c->ev[2]);
-        c->t_us[0] = 1e3 * ms;
-        c->t_us[4] = 1e3 * ms_sel;
-        if (list) return TWOSD_OK;
-        c->last_lp_N = N;
-        c->last_lp_blocks = nblocks;
-        c->last_ops_width = 1;
-        return TWOSD_OK;
-    }
-}
-
-// batch statistics on the device (integer sums: exact, order independent): [0] pivots,
-// [1] executed FMAs, [2] max pivots, [3] non-optimal scenarios
-__global__ void __launch_bounds__(256) lp_stats_kernel(int N, const int *__restrict__ its, const long long *__restrict__ ops,
-                                                      const int *__restrict__ st, const int *__restrict__ etan,
-                                                      unsigned long long *out) {
-    __shared__ unsigned long long red[4][5];
-    unsigned long long a = 0, b = 0, d = 0, e = 0;
-    unsigned long long mx = 0;
-    for (int s = blockIdx.x * blockDim.x + threadIdx.x; s < N; s += gridDim.x * blockDim.x) {
-        a += (unsigned long long)its[s];
-        b += (unsigned long long)ops[s];
-        mx = its[s] > (int)mx ? (unsigned long long)its[s] : mx;
-        d += st[s] != TWOSD_LP_OPTIMAL;
-        e += (unsigned long long)etan[s];
-    }
-    for (int o = 32; o > 0; o >>= 1) {
-        a += __shfl_down(a, o);
-        b += __shfl_down(b, o);
-        d += __shfl_down(d, o);
-        e += __shfl_down(e, o);
-        const unsigned long long m2 = __shfl_down(mx, o);
-        mx = m2 > mx ? m2 : mx;
-    }
-    // one set of atomics per block (per wave they serialised on five addresses: ~0.25 ms at 1M)
-    const int w = threadIdx.x >> 6;
-    if ((threadIdx.x & 63) == 0) {
-        red[w][0] = a; red[w][1] = b; red[w][2] = mx; red[w][3] = d; red[w][4] = e;
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        for (int v = 1; v < (int)(blockDim.x >> 6); ++v) {
-            a += red[v][0]; b += red[v][1]; mx = red[v][2] > mx ? red[v][2] : mx; d += red[v][3]; e += red[v][4];
-        }
-        atomicAdd(&out[0], a);
-        atomicAdd(&out[1], b);
-        atomicMax(&out[2], mx);
-        atomicAdd(&out[3], d);
-        atomicAdd(&out[4], e);
-    }
-}
-
-// incumbent objective of a batch: sum_s w_s obj_s and sum_s w_s (w = 1 without weights), each
-// block over a fixed stride of scenarios, then a fixed tree in the block; the host adds the
-// kObjBlocks partials in block order, so the sums do not depend on scheduling
-constexpr int kObjBlocks = 256;
-__global__ void __launch_bounds__(256) lp_obj_kernel(int N, const double *__restrict__ obj, const double *__restrict__ w,
-                                                     double *__restrict__ part) {
-    __shared__ double sa[256], sb[256];
-    double a = 0.0, b = 0.0;
-    for (int s = blockIdx.x * 256 + threadIdx.x; s < N; s += kObjBlocks * 256) {
-        const double ws = w ? w[s] : 1.0;
-        a = fma(ws, obj[s], a);
-        b += ws;
-    }
-    sa[threadIdx.x] = a;
-    sb[threadIdx.x] = b;
-    __syncthreads();
-    for (int o = 128; o > 0; o >>= 1) {
-        if ((int)threadIdx.x < o) {
-            sa[threadIdx.x] += sa[threadIdx.x + o];
-            sb[threadIdx.x] += sb[threadIdx.x + o];
-        }
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) {
-        part[2 * blockIdx.x] = sa[0];
-        part[2 * blockIdx.x + 1] = sb[0];
-    }
-}
-
-// Sample moments of a batch's objectives (twosd_moments per block): block b owns the contiguous
-// range [b L, min(N, (b + 1) L)), L = ceil(N / kMomBlocks), so a block's record is the moments of
-// a slice of the stream and the host merges the records in block order (twosd_moments_merge).
-// An entry counts when its status is optimal (PAIRED: in both arrays); the value of any other
-// entry is never loaded.  Per block, over its counted entries:
-//   0. the first counted index (each thread stops at its first; tree min) gives the pivot K = v[first]
-//   1. n and S = sum (v - K): mean = K + S / n.  The pivot keeps the sum at the size of the
-//      spread, not of the values, and makes a constant slice exact (S = 0, mean = K, m2 = 0)
-//   2. sum (v - mean)^2, min, max -- the second read of the slice comes from L2
-// never the one-pass sum v^2 - n mean^2, which loses 2 log10(mean / sd) digits.  PAIRED adds the
-// records of b and of the per-scenario difference d = a - b (formed per entry, then reduced like
-// a value): part[3 blk + 0 / 1 / 2] = a, b, d.  Every reduction is the fixed LDS tree of
-// lp_obj_kernel over per-thread partials of a fixed stride: no atomics, the same bits on every run.
-constexpr int kMomBlocks = 256;
-template <typename T, typename Op>
-__device__ __forceinline__ T mom_block_reduce(T v, T *sh, Op op) {
-    __syncthreads();   // sh may still be read as the previous reduction's result
-    sh[threadIdx.x] = v;
-    __syncthreads();
-    for (int o = 128; o > 0; o >>= 1) {
-        if ((int)threadIdx.x < o) sh[threadIdx.x] = op(sh[threadIdx.x], sh[threadIdx.x + o]);
-        __syncthreads();
-    }
-    return sh[0];
-}
-template <bool PAIRED>
-__global__ void __launch_bounds__(256) eval_moments_kernel(long long N, const double *__restrict__ va,
-                                                           const int *__restrict__ sa, const double *__restrict__ vb,
-                                                           const int *__restrict__ sb, twosd_moments *__restrict__ part) {
-    constexpr int R = PAIRED ? 3 : 1;
-    __shared__ double shd[256];
-    __shared__ long long shi[256];
-    const long long L = (N + kMomBlocks - 1) / kMomBlocks;
-    const long long lo0 = (long long)blockIdx.x * L, lo = lo0 < N ? lo0 : N, hi = lo + L < N ? lo + L : N;
-    const auto counted = [&](long long i) {
-        return (!sa || sa[i] == TWOSD_LP_OPTIMAL) && (!PAIRED || !sb || sb[i] == TWOSD_LP_OPTIMAL);
-    };
-    const auto add = [](auto x, auto y) { return x + y; };
-    const long long none = 0x7fffffffffffffffLL;
-    long long first = none;
-    for (long long i = lo + threadIdx.x; i < hi; i += 256)
-        if (counted(i)) { first = i; break; }
-    first = mom_block_reduce(first, shi, [](long long x, long long y) { return x < y ? x : y; });
-    twosd_moments *out = part + (size_t)R * blockIdx.x;
-    if (first == none) {   // an empty slice, or nothing counted: the merge's identity
-        if (threadIdx.x == 0)
-            for (int r = 0; r < R; ++r) out[r] = twosd_moments{0, hi - lo, 0.0, 0.0, HUGE_VAL, -HUGE_VAL};
-        return;
-    }
-    double K[R], S[R], mean[R], q[R], mn[R], mx[R];
-    K[0] = va[first];
-    if (PAIRED) { K[1] = vb[first]; K[2] = K[0] - K[1]; }
-    long long n = 0;
-    for (int r = 0; r < R; ++r) S[r] = 0.0;
-    for (long long i = lo + threadIdx.x; i < hi; i += 256) {
-        if (!counted(i)) continue;
-        ++n;
-        const double a = va[i];
-        S[0] += a - K[0];
-        if (PAIRED) {
-            const double b = vb[i];
-            S[1] += b - K[1];
-            S[2] += (a - b) - K[2];
-        }
-    }
-    n = mom_block_reduce(n, shi, add);
-    for (int r = 0; r < R; ++r) {
-        S[r] = mom_block_reduce(S[r], shd, add);
-        mean[r] = K[r] + S[r] / (double)n;
-        q[r] = 0.0; mn[r] = HUGE_VAL; mx[r] = -HUGE_VAL;
-    }
-    for (long long i = lo + threadIdx.x; i < hi; i += 256) {
-        if (!counted(i)) continue;
-        double v[R];
-        v[0] = va[i];
-        if (PAIRED) { v[1] = vb[i]; v[2] = v[0] - v[1]; }
-        for (int r = 0; r < R; ++r) {
-            const double e = v[r] - mean[r];
-            q[r] = fma(e, e, q[r]);
-            mn[r] = v[r] < mn[r] ? v[r] : mn[r];
-            mx[r] = v[r] > mx[r] ? v[r] : mx[r];
-        }
-    }
-    for (int r = 0; r < R; ++r) {
-        q[r] = mom_block_reduce(q[r], shd, add);
-        mn[r] = mom_block_reduce(mn[r], shd, [](double x, double y) { return x < y ? x : y; });
-        mx[r] = mom_block_reduce(mx[r], shd, [](double x, double y) { return x > y ? x : y; });
-    }
-    if (threadIdx.x == 0)
-        for (int r = 0; r < R; ++r) out[r] = twosd_moments{n, (hi - lo) - n, mean[r], n > 1 ? q[r] : 0.0, mn[r], mx[r]};
-}
-
-// Group means of a variance-reduced stream (twosd_sampling): the members of a
-// group of G consecutive entries are dependent, so the moments are taken over the groups' means.
-// One thread per group: status[b] = optimal iff all G entries are (else the first other status),
-// and only then mean[b] = K + (sum_{i < G} (v[i] - K)) / G with K = v[0], the sum in index order
-// from 0.0 -- a fixed order whatever the launch shape, the pivot keeping the sum at the size of the
-// spread.  The values of a group left out are never loaded (they may be NaN); its mean reads 0.
-// The means are stored relative to the chunk's pivot K0 = v[0] (0 when entry 0 is not optimal or
-// not finite), mean[b] = m_b - K0, and *pivot = K0: the moments kernel's block records then merge
-// at the size of the spread, not of the values (the merge's d d term loses 2^-53 |mean| / sd per
-// step), and the host adds K0 back to mean, min and max.  m_b - K0 is exact, and min / max the
-// means' own bits, whenever m_b / 2 <= K0 <= 2 m_b.
-// The paired form runs it on each array: a group counts when it is optimal in both, which the
-// moments kernel sees from the two group statuses, and it forms the difference of the means itself.
-__global__ void __launch_bounds__(256) group_means_kernel(long long ngroups, int G, const double *__restrict__ v,
-                                                          const int *__restrict__ st, double *__restrict__ mean,
-                                                          int *__restrict__ gst, double *__restrict__ pivot) {
-    const long long b = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (b >= ngroups) return;
-    const double K0 = ((!st || st[0] == TWOSD_LP_OPTIMAL) && isfinite(v[0])) ? v[0] : 0.0;
-    if (b == 0) *pivot = K0;
-    const long long lo = b * G;
-    int bad = TWOSD_LP_OPTIMAL;
-    if (st)
-        for (int i = 0; i < G && bad == TWOSD_LP_OPTIMAL; ++i) bad = st[lo + i];
-    double m = 0.0;
-    if (bad == TWOSD_LP_OPTIMAL) {
-        const double K = v[lo];
-        double s = 0.0;
-        for (int i = 0; i < G; ++i) s = __dadd_rn(s, __dadd_rn(v[lo + i], -K));
-        m = __dadd_rn(__dadd_rn(K, __ddiv_rn(s, (double)G)), -K0);
-    }
-    mean[b] = m;
-    gst[b] = bad;
-}
-
-// Template with general bounds: the LP's outputs back into the caller's space.  yu[s][j] =
-// off[j] + sign[j] * y[s][src[j]] - y[s][src2[j]] (a term with index -1 is absent: fixed columns
-// have no LP column, only free ones a second), one thread per output entry, j fastest, so a wave
-// writes consecutive entries of a row and reads a (nearly) consecutive run of the LP's row; and
-// obj[s] += c0, the constant q.s the shift took out of the LP.  y / yu nullable (objectives only).
-__global__ void __launch_bounds__(256) bounds_backmap_kernel(int N, int n2, int n_lp, const int *__restrict__ src,
-                                                             const int *__restrict__ src2, const double *__restrict__ sign,
-                                                             const double *__restrict__ off, const double *__restrict__ y,
-                                                             double *__restrict__ yu, double c0, double *__restrict__ obj) {
-    const size_t t0 = (size_t)blockIdx.x * blockDim.x + threadIdx.x, step = (size_t)gridDim.x * blockDim.x;
-    for (size_t s = t0; s < (size_t)N; s += step) obj[s] += c0;
-    if (!y) return;
-    const size_t tot = (size_t)N * n2;
-    for (size_t i = t0; i < tot; i += step) {
-        const size_t s = i / n2;
-        const int j = (int)(i - s * n2);
-        const double *row = y + s * n_lp;
-        const int a = src[j], b = src2[j];
-        double v = off[j];
-        if (a >= 0) v = fma(sign[j], row[a], v);
-        if (b >= 0) v -= row[b];
-        yu[i] = v;
-    }
-}
-
-// d_w: the batch's scenario weights (nullable: 1.0), for the objective sum
-static int copy_lp_outputs(twosd_ctx *c, int N, double *obj, double *pi, double *y, int *status, const double *d_w) {
-    if (!c->d_lpstats) {
-        int rc = c->d_lpstats.alloc(6);
-        if (rc) return rc;
-    }
-    if (!c->d_objpart) {
-        int rc = c->d_objpart.alloc((size_t)2 * kObjBlocks);
-        if (rc) return rc;
-    }
-    const double *d_yout = c->d_y;
-    if (c->has_bounds) {   // before the objective sum and the copies: they see the caller's values
-        if (y && (size_t)N * c->n2_user > c->d_yu.cap) {
-            int rc = c->d_yu.alloc((size_t)std::max(N, c->out_cap) * c->n2_user);
-            if (rc) return rc;
-        }
-        const size_t work = y ? (size_t)N * c->n2_user : (size_t)N;
-        hipLaunchKernelGGL(bounds_backmap_kernel, dim3((unsigned)std::min<size_t>(4096, (work + 255) / 256)), dim3(256), 0, c->stream, N,
-                           c->n2_user, c->L.n, c->d_bm_src, c->d_bm_src2, c->d_bm_sign, c->d_bm_off, y ? c->d_y : nullptr,
-                           y ? c->d_yu : nullptr, c->c0, c->d_obj);
-        HIPCHK(hipGetLastError());
-        d_yout = c->d_yu;
-    }
-    HIPCHK(hipMemsetAsync(c->d_lpstats, 0, 5 * sizeof(unsigned long long), c->stream));
-    hipLaunchKernelGGL(lp_stats_kernel, dim3((unsigned)std::min(256, (N + 255) / 256)), dim3(256), 0, c->stream, N,
-                       c->d_iters, c->d_ops, c->d_status, c->d_etan, c->d_lpstats);
-    HIPCHK(hipGetLastError());
-    hipLaunchKernelGGL(lp_obj_kernel, dim3(kObjBlocks), dim3(256), 0, c->stream, N, c->d_obj, d_w, c->d_objpart);
-    HIPCHK(hipGetLastError());
-    unsigned long long stv[6];
-    double part[2 * kObjBlocks];
-    HIPCHK(hipMemcpyAsync(stv, c->d_lpstats, sizeof(stv), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipMemcpyAsync(part, c->d_objpart, sizeof(part), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
-    if (obj) HIPCHK(hipMemcpy(obj, c->d_obj, sizeof(double) * N, hipMemcpyDeviceToHost));
-    if (pi) HIPCHK(hipMemcpy(pi, c->d_pi, sizeof(double) * N * c->L.m, hipMemcpyDeviceToHost));
-    if (y) HIPCHK(hipMemcpy(y, d_yout, sizeof(double) * N * c->n2_user, hipMemcpyDeviceToHost));
-    if (status) HIPCHK(hipMemcpy(status, c->d_status, sizeof(int) * N, hipMemcpyDeviceToHost));
-    c->last_pivots_sum = (int64_t)stv[0]; c->last_ops_sum = (int64_t)stv[1]; c->last_pivots_max = (int)stv[2];
-    c->last_eta_entries = (int64_t)stv[4];
-    c->last_retries = (int64_t)stv[5];
-    if (N >= 4096) {
-        c->piv_mean_ref = (double)stv[0] / N;
-        c->piv_ref_sum = (int64_t)stv[0];
-        c->piv_ref_n = N;
-    }
-    double ow = 0.0, wt = 0.0;
-    for (int b = 0; b < kObjBlocks; ++b) {
-        ow += part[2 * b];
-        wt += part[2 * b + 1];
-    }
-    c->last_obj_wsum = ow;
-    c->last_obj_w = wt;
-    const long long bad = (long long)stv[3];
-    if (bad) return fail(TWOSD_E_LP, "%lld of %d scenario LPs not optimal (see status[])", bad, N);
-    return TWOSD_OK;
-}
-
-extern "C" int twosd_last_objective(twosd_ctx *c, double *weighted_sum, double *weight_sum) {
-    if (!c) return fail(TWOSD_E_ARG, "last_objective: NULL");
-    if (weighted_sum) *weighted_sum = c->last_obj_wsum;
-    if (weight_sum) *weight_sum = c->last_obj_w;
-    return TWOSD_OK;
-}
-
-// ---- out-of-sample moments (twosd_moments_*, twosd_evaluate_moments / _paired / _ci) --------------
-static const twosd_moments kMomentsEmpty = {0, 0, 0.0, 0.0, HUGE_VAL, -HUGE_VAL};
-
-// The pairwise update of Chan, Golub and LeVeque: the one merge of the blocks' records, of the
-// chunks, of the batches and of the ranks.
-extern "C" int twosd_moments_merge(const twosd_moments *a, const twosd_moments *b, twosd_moments *out) {
-    if (!a || !b || !out) return fail(TWOSD_E_ARG, "moments_merge: NULL");
-    const twosd_moments A = *a, B = *b;   // out may alias either
-    if (A.n < 0 || B.n < 0) return fail(TWOSD_E_ARG, "moments_merge: negative count");
-    twosd_moments r;
-    if (B.n == 0) r = A;
-    else if (A.n == 0) r = B;
-    else {
-        const double na = (double)A.n, nb = (double)B.n, n = (double)(A.n + B.n);
-        const double d = B.mean - A.mean;
-        r.n = A.n + B.n;
-        r.mean = A.mean + d * (nb / n);
-        r.m2 = A.m2 + B.m2 + d * d * (na * nb / n);
-        r.min = B.min < A.min ? B.min : A.min;
-        r.max = B.max > A.max ? B.max : A.max;
-    }
-    r.n_bad = A.n_bad + B.n_bad;
-    *out = r;
-    return TWOSD_OK;
-}
-
-// moments of N device-resident values (PAIRED: also of vb and of va - vb) into out[0 .. R): the
-// kernel's kMomBlocks records, one small copy, one stream sync, merged in block order
-static int device_moments(twosd_ctx *c, long long N, const double *d_va, const int *d_sa, const double *d_vb,
-                          const int *d_sb, twosd_moments *out) {
-    const int R = d_vb ? 3 : 1;
-    for (int r = 0; r < R; ++r) out[r] = kMomentsEmpty;
-    if (N <= 0) return TWOSD_OK;
-    if (!c->d_mompart)
-        if (int rc = c->d_mompart.alloc(sizeof(twosd_moments) * 3 * kMomBlocks)) return rc;
-    twosd_moments *d_part = (twosd_moments *)c->d_mompart.p;
-    if (d_vb)
-        hipLaunchKernelGGL(eval_moments_kernel<true>, dim3(kMomBlocks), dim3(256), 0, c->stream, N, d_va, d_sa, d_vb, d_sb, d_part);
-    else
-        hipLaunchKernelGGL(eval_moments_kernel<false>, dim3(kMomBlocks), dim3(256), 0, c->stream, N, d_va, d_sa, d_vb, d_sb, d_part);
-    HIPCHK(hipGetLastError());
-    std::vector<twosd_moments> part((size_t)R * kMomBlocks);
-    HIPCHK(hipMemcpyAsync(part.data(), d_part, sizeof(twosd_moments) * part.size(), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
-    for (int b = 0; b < kMomBlocks; ++b)
-        for (int r = 0; r < R; ++r) twosd_moments_merge(&out[r], &part[(size_t)R * b + r], &out[r]);
-    return TWOSD_OK;
-}
-
-// device_moments over the means of groups of G consecutive entries (N a multiple of G; G = 1: the
-// entries themselves): group_means_kernel into the context's group buffers, then the moments
-// kernel unchanged on the N / G means and group statuses
-static int device_moments_grouped(twosd_ctx *c, long long N, int G, const double *d_va, const int *d_sa, const double *d_vb,
-                                  const int *d_sb, twosd_moments *out) {
-    if (G <= 1 || N <= 0) return device_moments(c, N, d_va, d_sa, d_vb, d_sb, out);
-    const long long ng = N / G;
-    const int R = d_vb ? 2 : 1;
-    int rc;
-    if ((rc = c->d_gm_mean.fit((size_t)R * ng + 2)) || (rc = c->d_gm_st.fit((size_t)R * ng))) return rc;   // + the two pivots
-    double *d_piv = c->d_gm_mean + (size_t)R * ng;
-    const unsigned nb = (unsigned)((ng + 255) / 256);
-    hipLaunchKernelGGL(group_means_kernel, dim3(nb), dim3(256), 0, c->stream, ng, G, d_va, d_sa, c->d_gm_mean.p, c->d_gm_st.p, d_piv);
-    HIPCHK(hipGetLastError());
-    if (d_vb) {
-        hipLaunchKernelGGL(group_means_kernel, dim3(nb), dim3(256), 0, c->stream, ng, G, d_vb, d_sb, c->d_gm_mean + ng,
-                           c->d_gm_st + ng, d_piv + 1);
-        HIPCHK(hipGetLastError());
-    }
-    double piv[2] = {0.0, 0.0};
-    HIPCHK(hipMemcpyAsync(piv, d_piv, sizeof(double) * (d_vb ? 2 : 1), hipMemcpyDeviceToHost, c->stream));   // device_moments drains the stream
-    if ((rc = device_moments(c, ng, c->d_gm_mean, c->d_gm_st, d_vb ? c->d_gm_mean + ng : nullptr, d_vb ? c->d_gm_st + ng : nullptr, out)))
-        return rc;
-    const double back[3] = {piv[0], piv[1], piv[0] - piv[1]};   // the difference record is of (a - K0a) - (b - K0b)
-    for (int r = 0; r < (d_vb ? 3 : 1); ++r)
-        if (out[r].n > 0) { out[r].mean += back[r]; out[r].min += back[r]; out[r].max += back[r]; }
-    return TWOSD_OK;
-}
-
-static int moments_of_values(twosd_ctx *c, int64_t n, int G, const double *obj, const int *status, twosd_moments *out) {
-    if (!c) return fail(TWOSD_E_STATE, "moments_of_values: no context");
-    if (!out || n < 0 || (n > 0 && !obj)) return fail(TWOSD_E_ARG, "moments_of_values: bad arguments");
-    HIPCHK(hipSetDevice(c->device));
-    int rc;
-    if (n > 0) {
-        if ((rc = c->d_ev_obj.grow((size_t)n, 0, c->stream))) return rc;
-        HIPCHK(hipMemcpy(c->d_ev_obj, obj, sizeof(double) * n, hipMemcpyHostToDevice));
-        if (status) {
-            if ((rc = c->d_ev_st.grow((size_t)n, 0, c->stream))) return rc;
-            HIPCHK(hipMemcpy(c->d_ev_st, status, sizeof(int) * n, hipMemcpyHostToDevice));
-        }
-    }
-    return device_moments_grouped(c, n, G, c->d_ev_obj, status ? c->d_ev_st : nullptr, nullptr, nullptr, out);
-}
-
-extern "C" int twosd_moments_of_values(twosd_ctx *c, int64_t n, const double *obj, const int *status, twosd_moments *out) {
-    return moments_of_values(c, n, 1, obj, status, out);
-}
-
-extern "C" int twosd_moments_of_values_grouped(twosd_ctx *c, int64_t n, int G, const double *obj, const int *status,
-                                               twosd_moments *out) {
-    if (G < 1 || G > 256) return fail(TWOSD_E_ARG, "moments_of_values_grouped: need 1 <= G <= 256, not %d", G);
-    if (n > 0 && n % G) return fail(TWOSD_E_ARG, "moments_of_values_grouped: n = %lld is no multiple of G = %d", (long long)n, G);
-    return moments_of_values(c, n, G, obj, status, out);
-}
-
-// scenarios per evaluate chunk; for a plan with G > 1 rounded down to whole groups (at least one)
-static int64_t eval_chunk_size(int G) {
-    int64_t chunk = 1 << 20;
-    if (const char *e = getenv("TWOSD_EVAL_CHUNK")) chunk = std::min<int64_t>(std::max<int64_t>(atoll(e), 1), 1 << 24);   // test hook
-    if (G > 1) chunk = std::max<int64_t>(chunk / G * G, G);
-    return chunk;
-}
-
-// the sampling plan of an evaluate call: (mode, group) of twosd_sampling, i.i.d. by default
-struct EvalPlan { int mode = TWOSD_SAMPLING_IID, G = 1; };
-
-// scenarios [at, at + n) of stream `seed` drawn into d_dvtmp and solved at x; copy_lp_outputs adds
-// the bounds' constant to d_obj and keeps the last-LP statistics current (nothing is copied out).
-// TWOSD_OK, or TWOSD_E_LP with d_obj / d_status still set, or a failure.
-static int eval_solve_chunk(twosd_ctx *c, const double *x, int64_t at, int n, uint64_t seed, const EvalPlan &pl) {
-    const int k = c->k;
-    int rc;
-    if ((rc = c->d_dvtmp.grow((size_t)n * std::max(k, 1), 0, c->stream))) return rc;
-    SampleParams S{};
-    S.N = n; S.k = k; S.seed = seed; S.first_index = (unsigned long long)at;
-    S.kind = c->d_dist_kind; S.off = c->d_dist_off; S.val = c->d_dist_val; S.prob = c->d_dist_prob;
-    S.p0 = c->d_dist_p0; S.p1 = c->d_dist_p1; S.tmpl = c->d_dist_tmpl; S.out = c->d_dvtmp;
-    HIPCHK(launch_sample_plan(S, pl.mode, pl.G, c->stream));
-    if ((rc = run_lp(c, x, c->d_dvtmp, n, false, false))) return rc;
-    return copy_lp_outputs(c, n, nullptr, nullptr, nullptr, nullptr, nullptr);
-}
-
-static int eval_check_state(twosd_ctx *c, const char *who) {
-    if (!c || !c->has_template) return fail(TWOSD_E_STATE, "%s: no template", who);
-    if (!c->has_basis) return fail(TWOSD_E_STATE, "%s: no warm-start basis", who);
-    if (!c->has_dist) return fail(TWOSD_E_STATE, "%s: no distributions (twosd_set_distributions)", who);
-    return TWOSD_OK;
-}
-
-// moments over [first, first + count) at xa (xb: the paired form, out[0 .. 3) = a, b, a - b);
-// *lp_bad: some LP was not optimal (counted in n_bad; not a failure here).  Under a plan with
-// G > 1 (first and count whole groups) the moments are of the group means, n / n_bad in groups.
-static int eval_moments_range(twosd_ctx *c, const double *xa, const double *xb, int64_t first, int64_t count, uint64_t seed,
-                              twosd_moments *out, bool *lp_bad, const EvalPlan &pl = EvalPlan()) {
-    const int R = xb ? 3 : 1;
-    const int64_t chunk = eval_chunk_size(pl.G);
-    for (int r = 0; r < R; ++r) out[r] = kMomentsEmpty;
-    for (int64_t at = 0; at < count; at += chunk) {
-        const int n = (int)std::min(chunk, count - at);
-        int rc = eval_solve_chunk(c, xa, first + at, n, seed, pl);
-        if (rc == TWOSD_E_LP) *lp_bad = true;
-        else if (rc) return rc;
-        twosd_moments m[3];
-        if (xb) {
-            if ((rc = c->d_ev_obj.grow((size_t)n, 0, c->stream)) ||
-                (rc = c->d_ev_st.grow((size_t)n, 0, c->stream)))
-                return rc;
-            HIPCHK(hipMemcpyAsync(c->d_ev_obj, c->d_obj, sizeof(double) * n, hipMemcpyDeviceToDevice, c->stream));
-            HIPCHK(hipMemcpyAsync(c->d_ev_st, c->d_status, sizeof(int) * n, hipMemcpyDeviceToDevice, c->stream));
-            HIPCHK(hipStreamSynchronize(c->stream));   // the next solve may reallocate d_obj / d_status
-            rc = eval_solve_chunk(c, xb, first + at, n, seed, pl);
-            if (rc == TWOSD_E_LP) *lp_bad = true;
-            else if (rc) return rc;
-            if ((rc = device_moments_grouped(c, n, pl.G, c->d_ev_obj, c->d_ev_st, c->d_obj, c->d_status, m))) return rc;
-        } else if ((rc = device_moments_grouped(c, n, pl.G, c->d_obj, c->d_status, nullptr, nullptr, m)))
-            return rc;
-        for (int r = 0; r < R; ++r) twosd_moments_merge(&out[r], &m[r], &out[r]);
-    }
-    return TWOSD_OK;
-}
-
-static int eval_lp_result(bool lp_bad, const twosd_moments &m, const char *who, int G = 1) {
-    if (!lp_bad) return TWOSD_OK;
-    if (G > 1)
-        return fail(TWOSD_E_LP, "%s: %lld of %lld scenario groups hold an LP that is not optimal (left out of the moments, see n_bad)",
-                    who, (long long)m.n_bad, (long long)(m.n + m.n_bad));
-    return fail(TWOSD_E_LP, "%s: %lld of %lld scenario LPs not optimal (left out of the moments, see n_bad)", who,
-                (long long)m.n_bad, (long long)(m.n + m.n_bad));
-}
-
-// the plan of an evaluate call, with `first` and `count` checked for whole groups
-static int eval_plan(const twosd_sampling *plan, const char *who, int64_t first, int64_t count, const char *count_name,
-                     EvalPlan *pl) {
-    int rc;
-    if ((rc = sampling_plan(plan, who, &pl->mode, &pl->G))) return rc;
-    if (first >= 0 && (rc = whole_groups(who, "first", (unsigned long long)first, pl->G))) return rc;
-    if (count >= 0 && (rc = whole_groups(who, count_name, (unsigned long long)count, pl->G))) return rc;
-    return TWOSD_OK;
-}
-
-static int evaluate_moments(twosd_ctx *c, const double *x, int64_t first, int64_t count, uint64_t seed, twosd_moments *out,
-                            const EvalPlan &pl) {
-    int rc = eval_check_state(c, "evaluate_moments");
-    if (rc) return rc;
-    if (!out || first < 0 || count < 0 || (c->n1 > 0 && !x)) return fail(TWOSD_E_ARG, "evaluate_moments: bad arguments");
-    HIPCHK(hipSetDevice(c->device));
-    bool lp_bad = false;
-    if ((rc = eval_moments_range(c, x, nullptr, first, count, seed, out, &lp_bad, pl))) return rc;
-    return eval_lp_result(lp_bad, *out, "evaluate_moments", pl.G);
-}
-
-extern "C" int twosd_evaluate_moments(twosd_ctx *c, const double *x, int64_t first, int64_t count, uint64_t seed,
-                                      twosd_moments *out) {
-    return evaluate_moments(c, x, first, count, seed, out, EvalPlan());
-}
-
-extern "C" int twosd_evaluate_moments_vr(twosd_ctx *c, const double *x, int64_t first, int64_t count, uint64_t seed,
-                                         twosd_moments *out, const twosd_sampling *plan) {
-    EvalPlan pl;
-    if (int rc = eval_plan(plan, "evaluate_moments", first, count, "count", &pl)) return rc;
-    return evaluate_moments(c, x, first, count, seed, out, pl);
-}
-
-static int evaluate_paired(twosd_ctx *c, const double *xa, const double *xb, int64_t first, int64_t count, uint64_t seed,
-                           twosd_moments *a, twosd_moments *b, twosd_moments *diff, const EvalPlan &pl) {
-    int rc = eval_check_state(c, "evaluate_paired");
-    if (rc) return rc;
-    if (!a || !b || !diff || first < 0 || count < 0 || !xa || !xb) return fail(TWOSD_E_ARG, "evaluate_paired: bad arguments");
-    HIPCHK(hipSetDevice(c->device));
-    bool lp_bad = false;
-    twosd_moments m[3];
-    if ((rc = eval_moments_range(c, xa, xb, first, count, seed, m, &lp_bad, pl))) return rc;
-    *a = m[0]; *b = m[1]; *diff = m[2];
-    return eval_lp_result(lp_bad, m[0], "evaluate_paired", pl.G);
-}
-
-extern "C" int twosd_evaluate_paired(twosd_ctx *c, const double *xa, const double *xb, int64_t first, int64_t count,
-                                     uint64_t seed, twosd_moments *a, twosd_moments *b, twosd_moments *diff) {
-    return evaluate_paired(c, xa, xb, first, count, seed, a, b, diff, EvalPlan());
-}
-
-extern "C" int twosd_evaluate_paired_vr(twosd_ctx *c, const double *xa, const double *xb, int64_t first, int64_t count,
-                                        uint64_t seed, twosd_moments *a, twosd_moments *b, twosd_moments *diff,
-                                        const twosd_sampling *plan) {
-    EvalPlan pl;
-    if (int rc = eval_plan(plan, "evaluate_paired", first, count, "count", &pl)) return rc;
-    return evaluate_paired(c, xa, xb, first, count, seed, a, b, diff, pl);
-}
-
-static int evaluate_ci(twosd_ctx *c, const double *x, uint64_t seed, int64_t first, int64_t batch, int64_t n_max, double z,
-                       double rel_tol, double abs_tol, double offset, twosd_moments *out, double *half_width, int *converged,
-                       const EvalPlan &pl) {
-    if (!out || !half_width || !converged || first < 0) return fail(TWOSD_E_ARG, "evaluate_ci: bad arguments");
-    if (batch < 2 || n_max < batch) return fail(TWOSD_E_ARG, "evaluate_ci: need 2 <= batch <= n_max (batch %lld, n_max %lld)", (long long)batch, (long long)n_max);
-    if (!(z > 0.0) || !(rel_tol >= 0.0) || !(abs_tol >= 0.0) || !std::isfinite(offset))
-        return fail(TWOSD_E_ARG, "evaluate_ci: need z > 0, tolerances >= 0 and a finite offset");
-    int rc = eval_check_state(c, "evaluate_ci");
-    if (rc) return rc;
-    if (c->n1 > 0 && !x) return fail(TWOSD_E_ARG, "evaluate_ci: x required");
-    HIPCHK(hipSetDevice(c->device));
-    twosd_moments acc = kMomentsEmpty;
-    bool lp_bad = false;
-    double hw = HUGE_VAL;
-    int conv = 0;
-    for (int64_t done = 0; done < n_max && !conv; ) {
-        const int64_t cnt = std::min(batch, n_max - done);
-        twosd_moments m;
-        if ((rc = eval_moments_range(c, x, nullptr, first + done, cnt, seed, &m, &lp_bad, pl))) return rc;
-        twosd_moments_merge(&acc, &m, &acc);
-        done += cnt;
-        if (acc.n >= 2) {
-            hw = z * std::sqrt(acc.m2 / (double)(acc.n - 1) / (double)acc.n);
-            conv = hw <= std::max(abs_tol, rel_tol * std::fabs(offset + acc.mean));
-        }
-    }
-    *out = acc;
-    *half_width = hw;
-    *converged = conv;
-    return eval_lp_result(lp_bad, acc, "evaluate_ci", pl.G);
-}
-
-extern "C" int twosd_evaluate_ci(twosd_ctx *c, const double *x, uint64_t seed, int64_t first, int64_t batch, int64_t n_max,
-                                 double z, double rel_tol, double abs_tol, double offset, twosd_moments *out,
-                                 double *half_width, int *converged) {
-    return evaluate_ci(c, x, seed, first, batch, n_max, z, rel_tol, abs_tol, offset, out, half_width, converged, EvalPlan());
-}
-
-// the rule of twosd_evaluate_ci on the group moments: its scenario counts (done, n_max, batch) stay
-// in scenarios, acc.n / acc.n_bad are groups
-extern "C" int twosd_evaluate_ci_vr(twosd_ctx *c, const double *x, uint64_t seed, int64_t first, int64_t batch, int64_t n_max,
-                                    double z, double rel_tol, double abs_tol, double offset, twosd_moments *out,
-                                    double *half_width, int *converged, const twosd_sampling *plan) {
-    EvalPlan pl;
-    if (int rc = eval_plan(plan, "evaluate_ci", first, batch, "batch", &pl)) return rc;
-    if (pl.G > 1) {
-        if (batch / pl.G < 2)
-            return fail(TWOSD_E_ARG, "evaluate_ci: batch = %lld holds fewer than 2 groups of %d", (long long)batch, pl.G);
-        n_max = n_max / pl.G * pl.G;
-    }
-    return evaluate_ci(c, x, seed, first, batch, n_max, z, rel_tol, abs_tol, offset, out, half_width, converged, pl);
-}
-
-extern "C" int twosd_solve_batch(twosd_ctx *c, int epi, const double *x, int first, int count, double *obj,
-                                 double *pi, double *y, int *status) {
-    if (!c || !c->has_template) return fail(TWOSD_E_STATE, "solve_batch: no template");
-    if (!c->has_basis) return fail(TWOSD_E_STATE, "solve_batch: no warm-start basis (twosd_compute_basis / twosd_set_basis)");
-    if (epi < 0 || epi >= (int)c->epis.size()) return fail(TWOSD_E_ARG, "solve_batch: epigraph %d does not exist", epi);
-    const EpiDevice &E = c->epis[epi];
-    if (first < 0 || count < 0 || first + count > E.count) return fail(TWOSD_E_ARG, "solve_batch: range [%d,%d) outside %d scenarios", first, first + count, E.count);
-    if (!obj || !status || (c->n1 > 0 && !x)) return fail(TWOSD_E_ARG, "solve_batch: obj/status/x required");
-    if (count == 0) return TWOSD_OK;
-    HIPCHK(hipSetDevice(c->device));
-    int rc = run_lp(c, x, E.d_dv + (size_t)first * c->k, count, pi != nullptr, y != nullptr);
-    if (rc) return rc;
-    return copy_lp_outputs(c, count, obj, pi, y, status, E.d_w + first);
-}
-
-extern "C" int twosd_solve_values(twosd_ctx *c, const double *x, int N, const double *values, double *obj, double *pi,
-                                  double *y, int *status) {
-    if (!c || !c->has_template) return fail(TWOSD_E_STATE, "solve_values: no template");
-    if (!c->has_basis) return fail(TWOSD_E_STATE, "solve_values: no warm-start basis");
-    if (N < 0 || (N > 0 && c->k > 0 && !values) || !obj || !status || (c->n1 > 0 && !x)) return fail(TWOSD_E_ARG, "solve_values: bad arguments");
-    if (N == 0) return TWOSD_OK;
-    HIPCHK(hipSetDevice(c->device));
-    const int k = c->k;
-    std::vector<double> dv((size_t)N * std::max(k, 1), 0.0);
-    for (int s = 0; s < N; ++s)
-        for (int e = 0; e < k; ++e) dv[(size_t)s * k + e] = values[(size_t)s * k + e] - template_value(c, e);
-    int rc;
-    if ((rc = c->d_dvtmp.grow((size_t)N * std::max(k, 1), 0, c->stream))) return rc;
-    HIPCHK(hipMemcpy(c->d_dvtmp, dv.data(), sizeof(double) * dv.size(), hipMemcpyHostToDevice));
-    if ((rc = run_lp(c, x, c->d_dvtmp, N, pi != nullptr, y != nullptr))) return rc;
-    return copy_lp_outputs(c, N, obj, pi, y, status, nullptr);
-}
-
-extern "C" int twosd_last_timings(twosd_ctx *c, double *us5) {
-    if (!c || !us5) return fail(TWOSD_E_ARG, "last_timings: NULL");
-    for (int i = 0; i < 5; ++i) us5[i] = c->t_us[i];
-    return TWOSD_OK;
-}
-
-extern "C" int twosd_last_lp_eta_entries(twosd_ctx *c, int64_t *entries, int64_t *retries) {
-    if (!c || !entries) return fail(TWOSD_E_ARG, "last_lp_eta_entries: NULL");
-    *entries = c->last_eta_entries;
-    if (retries) *retries = c->last_retries;
-    return TWOSD_OK;
-}
-
-extern "C" int twosd_last_lp_stats(twosd_ctx *c, int64_t *sum, int *mx) {
-    if (!c) return fail(TWOSD_E_ARG, "last_lp_stats: NULL");
-    if (sum) *sum = c->last_pivots_sum;
-    if (mx) *mx = c->last_pivots_max;
-    return TWOSD_OK;
-}
-
-extern "C" int twosd_last_lp_iters(twosd_ctx *c, int N, int *iters, int *status) {
-    if (!c || N < 0 || N > c->out_cap || !c->d_iters) return fail(TWOSD_E_ARG, "last_lp_iters: N = %d outside the last batch", N);
-    HIPCHK(hipStreamSynchronize(c->stream));
-    if (iters) HIPCHK(hipMemcpy(iters, c->d_iters, sizeof(int) * N, hipMemcpyDeviceToHost));
-    if (status) HIPCHK(hipMemcpy(status, c->d_status, sizeof(int) * N, hipMemcpyDeviceToHost));
-    return TWOSD_OK;
-}
-
-extern "C" int twosd_debug_stamps(twosd_ctx *c, uint64_t *out10, int reset) {
-    if (!c || !out10) return fail(TWOSD_E_ARG, "debug_stamps: NULL");
-    for (int i = 0; i < 10; ++i) out10[i] = 0;
-    if (!c->d_stamps) return TWOSD_OK;
-    HIPCHK(hipMemcpy(out10, c->d_stamps, sizeof(uint64_t) * 10, hipMemcpyDeviceToHost));
-    if (reset) HIPCHK(hipMemset(c->d_stamps, 0, sizeof(uint64_t) * 16));
-    return TWOSD_OK;
-}
-
-extern "C" int twosd_last_lp_ops(twosd_ctx *c, int64_t *row_ops, int *row_width) {
-    if (!c) return fail(TWOSD_E_ARG, "last_lp_ops: NULL");
-    if (row_ops) *row_ops = c->last_ops_sum;
-    if (row_width) *row_width = c->last_ops_width;
-    return TWOSD_OK;
-}
-
-// rows list[0..U) of pi (m doubles each) gathered in list order (the push of a full-mode solve_push)
-__global__ void gather_rows_kernel(int U, int m, const int *__restrict__ list, const double *__restrict__ pi, double *__restrict__ out) {
-    const size_t tot = (size_t)U * m;
-    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < tot; i += (size_t)gridDim.x * blockDim.x) {
-        const int u = (int)(i / m), r = (int)(i % m);
-        out[i] = pi[(size_t)list[u] * m + r];
-    }
-}
-
-// non-optimal statuses among the scenarios of a list-mode re-solve (status is by scenario)
-__global__ void list_status_kernel(int U, const int *__restrict__ list, const int *__restrict__ st,
-                                   unsigned long long *bad) {
-    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < U; i += gridDim.x * blockDim.x)
-        if (st[list[i]] != TWOSD_LP_OPTIMAL) atomicAdd(bad, 1ull);
-}
-
-extern "C" int twosd_solve_push(twosd_ctx *c, int epi, const double *x, int first, int count, double *obj, int *status,
-                                int *new_size) {
-    if (!c || !c->has_template) return fail(TWOSD_E_STATE, "solve_push: no template");
-    if (!c->has_basis) return fail(TWOSD_E_STATE, "solve_push: no warm-start basis");
-    if (epi < 0 || epi >= (int)c->epis.size()) return fail(TWOSD_E_ARG, "solve_push: epigraph %d does not exist", epi);
-    const EpiDevice &E = c->epis[epi];
-    if (first < 0 || count < 0 || first + count > E.count) return fail(TWOSD_E_ARG, "solve_push: range outside the epigraph");
-    if (c->n1 > 0 && !x) return fail(TWOSD_E_ARG, "solve_push: x is NULL");
-    if (count == 0) { if (new_size) *new_size = c->dvs.size; return TWOSD_OK; }
-    HIPCHK(hipSetDevice(c->device));
-    const double *d_dv = E.d_dv + (size_t)first * c->k;
-    // TWOSD_PUSH_ALL=1: recover and push the dual of every scenario (the pre-key path, kept for
-    // the equivalence test); default: vertex keys, first occurrences, re-solve of those only
-    const bool all = getenv("TWOSD_PUSH_ALL") && atoi(getenv("TWOSD_PUSH_ALL")) != 0;
-    // Full mode: the main pass recovers every scenario's dual (and its key), and the representatives'
-    // rows are gathered from it -- the same rows the re-solve would produce (same start, same pivots,
-    // same recovery), without solving them twice.  Chosen when the last keyed push re-solved more
-    // than a quarter of its scenarios (ssn: ~every scenario its own vertex; storm: < 1 %).
-    // TWOSD_PUSH_MODE: 0 auto (default), 1 always re-solve, 2 always full.
-    const int pmode = getenv("TWOSD_PUSH_MODE") ? atoi(getenv("TWOSD_PUSH_MODE")) : 0;
-    const bool full = !all && (pmode == 2 || (pmode == 0 && c->push_rep_frac > 0.25));
-    c->last_push_full = full ? 1 : 0;
-    LpRun o;
-    o.want_pi = all || full;
-    o.want_key = !all;
-    int rc = run_lp_ex(c, x, d_dv, count, o);
-    if (rc) return rc;
-    const double t_lp = c->t_us[0], t_sel = c->t_us[4];
-    rc = copy_lp_outputs(c, count, obj, nullptr, nullptr, status, E.d_w + first);
-    if (rc) return rc;   // some LP not optimal: nothing pushed
-    const double obj_wsum = c->last_obj_wsum, obj_w = c->last_obj_w;
-    const int64_t piv_sum = c->last_pivots_sum, ops_sum = c->last_ops_sum, eta_sum = c->last_eta_entries;
-    const int64_t retries = c->last_retries;
-    const int piv_max = c->last_pivots_max;
-    float ms = 0, ms_key = 0;
-    if (all) {
-        HIPCHK(hipEventRecord(c->ev[2], c->stream));
-        if ((rc = dvs_push_device(c, count, c->d_pi, nullptr))) return rc;
-        HIPCHK(hipEventRecord(c->ev[3], c->stream));
-        HIPCHK(hipEventSynchronize(c->ev[3]));
-        hipEventElapsedTime(&ms, c->ev[2], c->ev[3]);
-        c->last_push_reps = count;
-    } else {
-        HIPCHK(hipEventRecord(c->ev[5], c->stream));
-        const int *d_list = nullptr;
-        int U = 0;
-        if ((rc = vkey_first_occurrences(c, count, c->d_vkey, c->d_status, &d_list, &U))) return rc;
-        HIPCHK(hipEventRecord(c->ev[6], c->stream));
-        HIPCHK(hipEventSynchronize(c->ev[6]));
-        hipEventElapsedTime(&ms_key, c->ev[5], c->ev[6]);
-        c->last_push_reps = U;
-        c->push_rep_frac = (double)U / count;
-        if (U > 0 && full) {
-            const int m = c->L.m;
-            if ((rc = c->d_pi_rep.fit((size_t)U * m))) return rc;
-            hipLaunchKernelGGL(gather_rows_kernel, dim3((unsigned)std::min<size_t>(4096, ((size_t)U * m + 255) / 256)), dim3(256), 0,
-                               c->stream, U, m, d_list, c->d_pi, c->d_pi_rep);
-            HIPCHK(hipGetLastError());
-            c->t_us[0] = t_lp;
-            HIPCHK(hipEventRecord(c->ev[2], c->stream));
-            if ((rc = dvs_push_device(c, U, c->d_pi_rep, nullptr))) return rc;
-            HIPCHK(hipEventRecord(c->ev[3], c->stream));
-            HIPCHK(hipEventSynchronize(c->ev[3]));
-            hipEventElapsedTime(&ms, c->ev[2], c->ev[3]);
-        } else if (U > 0) {
-            LpRun r;
-            r.want_pi = true;
-            r.d_list = d_list;
-            r.nlist = U;
-            if ((rc = run_lp_ex(c, x, d_dv, count, r))) return rc;
-            // the re-solve starts every representative from its recorded pick and repeats its
-            // optimal solve; should one ever end otherwise, its pi row must not reach V
-            HIPCHK(hipMemsetAsync(c->d_lpstats, 0, sizeof(unsigned long long), c->stream));
-            hipLaunchKernelGGL(list_status_kernel, dim3((unsigned)std::min(256, (U + 255) / 256)), dim3(256), 0, c->stream, U,
-                               d_list, c->d_status, c->d_lpstats);
-            HIPCHK(hipGetLastError());
-            unsigned long long bad = 0;
-            HIPCHK(hipMemcpyAsync(&bad, c->d_lpstats, sizeof(bad), hipMemcpyDeviceToHost, c->stream));
-            HIPCHK(hipStreamSynchronize(c->stream));
-            if (bad) return fail(TWOSD_E_LP, "solve_push: %llu of %d re-solved representatives not optimal; nothing pushed", bad, U);
-            c->t_us[0] += t_lp;   // LP kernel time of the batch: main pass + representatives
-            HIPCHK(hipEventRecord(c->ev[2], c->stream));
-            if ((rc = dvs_push_device(c, U, c->d_pi, nullptr))) return rc;
-            HIPCHK(hipEventRecord(c->ev[3], c->stream));
-            HIPCHK(hipEventSynchronize(c->ev[3]));
-            hipEventElapsedTime(&ms, c->ev[2], c->ev[3]);
-        } else {
-            c->t_us[0] = t_lp;
-        }
-        c->t_us[4] = t_sel;
-        c->last_pivots_sum = piv_sum; c->last_ops_sum = ops_sum; c->last_pivots_max = piv_max;
-        c->last_eta_entries = eta_sum;
-        c->last_retries = retries;
-    }
-    c->last_obj_wsum = obj_wsum; c->last_obj_w = obj_w;   // of the batch, not of the representatives' re-solve
-    c->t_us[1] = 1e3 * (ms + ms_key);
-    if (new_size) *new_size = c->dvs.size;
-    return TWOSD_OK;
-}
-
-extern "C" int twosd_last_push_mode(twosd_ctx *c, int *full) {
-    if (!c || !full) return fail(TWOSD_E_ARG, "last_push_mode: NULL");
-    *full = c->last_push_full;
-    return TWOSD_OK;
-}
-
-extern "C" int twosd_last_push_reps(twosd_ctx *c, int *reps) {
-    if (!c || !reps) return fail(TWOSD_E_ARG, "last_push_reps: NULL");
-    *reps = c->last_push_reps;
     return TWOSD_OK;
 }

@@ -776,16 +776,16 @@ static int reform_cuts_impl(twosd_ctx *c, int epi, int H, const int *handles, in
     if ((rc = reform_whole_groups(c, epi, H, handles, index_offset, G, "reform_cuts"))) return rc;
     HIPCHK(hipSetDevice(c->device));
     if ((rc = c->boot.u64.fit(L.n_u64)) || (rc = c->boot.f64.fit(L.n_f64))) return rc;
-    HIPCHK(hipEventRecord(c->ev[4], c->stream));
+    HIPCHK(hipEventRecord(c->ev[EV_MARK_0], c->stream));
     if ((rc = boot_partial_impl(c, epi, L, handles, M, seed, index_offset, G, E.total_weight, c->boot.u64, c->boot.f64))) return rc;
-    HIPCHK(hipEventRecord(c->ev[5], c->stream));
+    HIPCHK(hipEventRecord(c->ev[EV_MARK_1], c->stream));
     if ((rc = boot_finalize_impl(c, L, handles, E.total_weight, c->boot.u64, c->boot.f64, alpha, beta, weight_mark, total_weight)))
         return rc;
-    HIPCHK(hipEventRecord(c->ev[6], c->stream));
-    HIPCHK(hipEventSynchronize(c->ev[6]));
+    HIPCHK(hipEventRecord(c->ev[EV_MARK_2], c->stream));
+    HIPCHK(hipEventSynchronize(c->ev[EV_MARK_2]));
     float ms1 = 0, ms2 = 0;
-    hipEventElapsedTime(&ms1, c->ev[4], c->ev[5]);
-    hipEventElapsedTime(&ms2, c->ev[5], c->ev[6]);
+    hipEventElapsedTime(&ms1, c->ev[EV_MARK_0], c->ev[EV_MARK_1]);
+    hipEventElapsedTime(&ms2, c->ev[EV_MARK_1], c->ev[EV_MARK_2]);
     c->boot.ms[0] = ms1;
     c->boot.ms[1] = ms2;
     return TWOSD_OK;

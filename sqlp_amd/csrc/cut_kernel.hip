@@ -2368,17 +2368,17 @@ extern "C" int twosd_build_cut(twosd_ctx *c, int epi, const double *x, double ti
         if (weight_mark) *weight_mark = E.total_weight;
         return clear_cut_stats(c);
     }
-    HIPCHK(hipEventRecord(c->ev[4], c->stream));
+    HIPCHK(hipEventRecord(c->ev[EV_MARK_0], c->stream));
     if ((rc = cut_partial_impl(c, epi, x, tie_rel, E.total_weight, w->hist, w->sums))) return rc;
-    HIPCHK(hipEventRecord(c->ev[5], c->stream));
+    HIPCHK(hipEventRecord(c->ev[EV_MARK_1], c->stream));
     if ((rc = cut_finalize_impl(c, x, w->hist, w->sums, alpha, beta))) return rc;
-    HIPCHK(hipEventRecord(c->ev[6], c->stream));
-    HIPCHK(hipEventSynchronize(c->ev[6]));
+    HIPCHK(hipEventRecord(c->ev[EV_MARK_2], c->stream));
+    HIPCHK(hipEventSynchronize(c->ev[EV_MARK_2]));
     float ms1 = 0, ms2 = 0;
-    hipEventElapsedTime(&ms1, c->ev[4], c->ev[5]);
-    hipEventElapsedTime(&ms2, c->ev[5], c->ev[6]);
-    c->t_us[2] = 1e3 * ms1;
-    c->t_us[3] = 1e3 * ms2;
+    hipEventElapsedTime(&ms1, c->ev[EV_MARK_0], c->ev[EV_MARK_1]);
+    hipEventElapsedTime(&ms2, c->ev[EV_MARK_1], c->ev[EV_MARK_2]);
+    c->t_us[T_CUT_PARTIAL] = 1e3 * ms1;
+    c->t_us[T_CUT_FINALIZE] = 1e3 * ms2;
     c->last_cut_epi = epi; c->last_cut_n = E.count; c->last_cut_nv = nv;
     if (weight_mark) *weight_mark = E.total_weight;
     if (max_val) HIPCHK(hipMemcpy(max_val, w->val, sizeof(double) * E.count, hipMemcpyDeviceToHost));
@@ -2498,13 +2498,13 @@ extern "C" int twosd_cut_partial(twosd_ctx *c, int epi, const double *x, double 
         HIPCHK(hipStreamSynchronize(c->stream));
         return clear_cut_stats(c);
     }
-    HIPCHK(hipEventRecord(c->ev[4], c->stream));
+    HIPCHK(hipEventRecord(c->ev[EV_MARK_0], c->stream));
     if ((rc = cut_partial_impl(c, epi, x, tie_rel, total_weight, (unsigned long long *)d_hist, d_sums))) return rc;
-    HIPCHK(hipEventRecord(c->ev[5], c->stream));
-    HIPCHK(hipEventSynchronize(c->ev[5]));
+    HIPCHK(hipEventRecord(c->ev[EV_MARK_1], c->stream));
+    HIPCHK(hipEventSynchronize(c->ev[EV_MARK_1]));
     float ms = 0;
-    hipEventElapsedTime(&ms, c->ev[4], c->ev[5]);
-    c->t_us[2] = 1e3 * ms;
+    hipEventElapsedTime(&ms, c->ev[EV_MARK_0], c->ev[EV_MARK_1]);
+    c->t_us[T_CUT_PARTIAL] = 1e3 * ms;
     c->last_cut_epi = epi; c->last_cut_n = E.count; c->last_cut_nv = c->dvs.size;
     CutWs *w = cws(c);
     if (max_val) HIPCHK(hipMemcpy(max_val, w->val, sizeof(double) * E.count, hipMemcpyDeviceToHost));
@@ -2519,13 +2519,13 @@ extern "C" int twosd_cut_finalize(twosd_ctx *c, const double *x, const uint64_t 
     if (!c || !c->has_template || !d_hist || !d_sums || !alpha || (c->n1 > 0 && !beta))
         return fail(TWOSD_E_ARG, "cut_finalize: bad arguments");
     HIPCHK(hipSetDevice(c->device));
-    HIPCHK(hipEventRecord(c->ev[5], c->stream));
+    HIPCHK(hipEventRecord(c->ev[EV_MARK_1], c->stream));
     int rc = cut_finalize_impl(c, x, (const unsigned long long *)d_hist, d_sums, alpha, beta);
     if (rc) return rc;
-    HIPCHK(hipEventRecord(c->ev[6], c->stream));
-    HIPCHK(hipEventSynchronize(c->ev[6]));
+    HIPCHK(hipEventRecord(c->ev[EV_MARK_2], c->stream));
+    HIPCHK(hipEventSynchronize(c->ev[EV_MARK_2]));
     float ms = 0;
-    hipEventElapsedTime(&ms, c->ev[5], c->ev[6]);
-    c->t_us[3] = 1e3 * ms;
+    hipEventElapsedTime(&ms, c->ev[EV_MARK_1], c->ev[EV_MARK_2]);
+    c->t_us[T_CUT_FINALIZE] = 1e3 * ms;
     return TWOSD_OK;
 }

@@ -307,7 +307,7 @@ extern "C" int twosd_dvs_push(twosd_ctx *c, int count, const double *pis, int *o
         const size_t need = (size_t)count * c->dvs.m;
         if (int rc = w->pis.fit(need)) return rc;
         HIPCHK(hipMemcpy(w->pis, pis, sizeof(double) * need, hipMemcpyHostToDevice));
-        hipEvent_t e0 = c->ev[2], e1 = c->ev[3];
+        hipEvent_t e0 = c->ev[EV_PUSH_BEGIN], e1 = c->ev[EV_PUSH_END];
         HIPCHK(hipEventRecord(e0, c->stream));
         int rc = dvs_push_device(c, count, w->pis, nullptr);
         if (rc) return rc;
@@ -315,7 +315,7 @@ extern "C" int twosd_dvs_push(twosd_ctx *c, int count, const double *pis, int *o
         HIPCHK(hipEventSynchronize(e1));
         float ms = 0;
         hipEventElapsedTime(&ms, e0, e1);
-        c->t_us[1] = 1e3 * ms;
+        c->t_us[T_DEDUP] = 1e3 * ms;
         if (out_index) HIPCHK(hipMemcpy(out_index, w->out, sizeof(int) * count, hipMemcpyDeviceToHost));
     }
     if (new_size) *new_size = c->dvs.size;

@@ -1,7 +1,7 @@
 // pool_refresh.hip -- the warm-start pool refresh at x: twosd_pool_refresh on one GPU, and the
 // twosd_refresh_* family of the distributed refresh (one process per GPU).  Both run the same
 // front end (refresh_front), bind the same source-table type (PgTable) and build the same pool
-// bit for bit.  The pool's own upload and per-x preparation stay in api.hip.
+// bit for bit.  The pool's own upload is api.hip's, the per-x preparation pool_select.hip's.
 #include <hip/hip_runtime.h>
 #include <algorithm>
 #include <chrono>
@@ -209,7 +209,6 @@ static int pg_assemble(twosd_ctx *c, PgArgs &A, const PgHost &H, const std::vect
     }
     c->pool.swap(keep);
     std::thread([old = std::move(keep)]() mutable { old.clear(); }).detach();
-    c->b0_nnz = H.tot[0];
     c->prep_valid = false;
     c->k_valid = true;
     reset_candidates(c);
@@ -285,7 +284,7 @@ static int refresh_training(twosd_ctx *c, const double *x, const double *d_dv, i
     // lasts as long as its slowest scenario: with one scenario per wave the cap bounds it)
     o.kcap = kcap;
     int rc;
-    if ((rc = run_lp_ex(c, x, d_dv, count, o))) return rc;
+    if ((rc = run_lp(c, x, d_dv, count, o))) return rc;
     int opt = count;
     if (o.kcap > 0) {
         std::vector<int> st(count);
@@ -294,7 +293,7 @@ static int refresh_training(twosd_ctx *c, const double *x, const double *d_dv, i
         if (retry && 2 * opt < count) {
             if (dbg) fprintf(stderr, "refresh training: %d of %d optimal under cap %d, solved again uncapped\n", opt, count, o.kcap);
             o.kcap = 0;
-            if ((rc = run_lp_ex(c, x, d_dv, count, o))) return rc;
+            if ((rc = run_lp(c, x, d_dv, count, o))) return rc;
         }
     }
     // The eta files share one arena, claimed through an atomic counter that keeps counting past
@@ -308,7 +307,7 @@ static int refresh_training(twosd_ctx *c, const double *x, const double *d_dv, i
     if (used64 > c->eo_cap && used64 <= (unsigned long long)INT32_MAX) {
         if (dbg) fprintf(stderr, "refresh training: eta files of %llu entries past the arena of %zu, solved again\n", used64, c->eo_cap);
         c->eo_min_cap = (size_t)std::min<unsigned long long>(used64 + used64 / 8, INT32_MAX);
-        if ((rc = run_lp_ex(c, x, d_dv, count, o))) return rc;
+        if ((rc = run_lp(c, x, d_dv, count, o))) return rc;
     }
     c->last_train_opt = opt;
     if (n_opt) *n_opt = opt;
@@ -352,8 +351,9 @@ static int refresh_front(twosd_ctx *c, const char *who, int epi, const double *x
         int h[8] = {0};
         long long itsum = 0;
         for (int s2 = 0; s2 < count; ++s2) { h[std::min(std::max(st[s2], 0), 7)]++; itsum += itv[s2]; }
+        const double piv_mean_ref = c->piv_ref_n ? (double)c->piv_ref_sum / (double)c->piv_ref_n : 0.0;
         fprintf(stderr, "%s training: kcap %d (ref %.2f), pool %zu, statuses 0:%d 1:%d 2:%d 3:%d 4:%d 5+:%d, mean iters %.2f\n", who,
-                kcap, c->piv_mean_ref, c->pool.size(), h[0], h[1], h[2], h[3], h[4], h[5] + h[6] + h[7], (double)itsum / count);
+                kcap, piv_mean_ref, c->pool.size(), h[0], h[1], h[2], h[3], h[4], h[5] + h[6] + h[7], (double)itsum / count);
     }
     F.t_trained = Clock::now();
     // 2. distinct optimal bases in order of first occurrence, with their counts

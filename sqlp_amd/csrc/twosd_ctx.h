@@ -85,6 +85,40 @@ struct BootState {
     double ms[2] = {0, 0};        // device time of the last twosd_reform_cuts: partial sums, finalize (with its copies)
 };
 
+// the slots of twosd_last_timings, in the order the ABI reports them (microseconds)
+enum TimeSlot : int {
+    T_LP = 0,         // LP kernel of the last batch (solve_push in re-solve mode: main pass + representatives)
+    T_DEDUP,          // vertex keys and push of the last solve_push / twosd_dvs_push
+    T_CUT_PARTIAL,
+    T_CUT_FINALIZE,
+    T_POOL_SELECT,    // warm-start selection of the last batch
+    T_COUNT
+};
+
+// twosd_ctx::ev by owner.  Every call is synchronous on the one stream, so an owner's events are
+// free again when its call returns; the push begins after the launch has read its own three.
+enum EventSlot : int {
+    EV_LP_BEGIN = 0, EV_LP_END = 1, EV_LP_SELECTED = 2,   // the LP launch (run_lp): selection = BEGIN..SELECTED, kernel = SELECTED..END
+    EV_PUSH_BEGIN = 2, EV_PUSH_END = 3,                   // the push of solve_push / twosd_dvs_push
+    EV_MARK_0 = 4, EV_MARK_1 = 5, EV_MARK_2 = 6,          // up to three marks of one call: cut, bootstrap, solve_push's keys
+    EV_COUNT = 8                                          // 7 is free
+};
+
+// The last LP batch, as the twosd_last_* getters report it.  The one rule: a non-list launch
+// (run_lp) writes N and the two times, its copy_lp_outputs the rest; a list-mode launch never
+// touches it (it hands its kernel time to LpRun::lp_us_out).  solve_push adds the
+// representatives' re-solve to lp_us and nothing else.
+struct LpBatchRecord {
+    int N = 0;                           // scenarios of the batch
+    double lp_us = 0.0, sel_us = 0.0;    // LP kernel (with its queue records), warm-start selection
+    int64_t pivots_sum = 0;
+    int pivots_max = 0;
+    int64_t ops_sum = 0;                 // executed FMAs
+    int64_t eta_entries = 0;
+    int64_t retries = 0;                 // pool starts retried from the primary basis
+    double obj_wsum = 0.0, obj_w = 0.0;  // sum_s w_s obj_s (fixed-order reduction) and sum_s w_s
+};
+
 struct CutWs;    // cut_kernel.hip
 struct DvsWs;    // dvs_kernel.hip
 struct VkeyWs;   // vkey.hip
@@ -96,10 +130,12 @@ void vkey_free(VkeyWs *w);
 
 // Everything a template re-set clears: twosd_set_template assigns a default-constructed one.
 struct TemplateState {
-    double piv_mean_ref = 0.0;    // mean pivots of the last large batch solve (the auto cap's scale)
-    int64_t piv_ref_sum = 0, piv_ref_n = 0;   // that batch's pivot sum and size (ranks agree on one cap)
+    // pivot sum and size of the last large batch (N >= 4096), the scale of the refresh's auto cap
+    // (ranks agree on one cap).  Not part of `last`: it outlives the smaller batches that follow.
+    int64_t piv_ref_sum = 0, piv_ref_n = 0;
     int last_train_opt = 0;       // optimal training scenarios of the last refresh
-    double t_us[5] = {0, 0, 0, 0, 0};   // LP kernel, dedup, cut partial, cut finalize, pool select
+    twosd::LpBatchRecord last;
+    double t_us[twosd::T_COUNT] = {};   // T_DEDUP and the cut's two; T_LP / T_POOL_SELECT are last.lp_us / last.sel_us
     // template
     bool has_template = false, has_basis = false;
     twosd::HostLP L;              // W CSC, q, sense (host)
@@ -136,7 +172,7 @@ struct TemplateState {
     twosd::DevBuf<double> d_kraw;
     twosd::DevBuf<double> d_xaux;            // per x: b (m), coef (k), box lo (k), box hi (k)
     int64_t sel_cap_total = 0;           // records the static capacity layout holds
-    int64_t sel_nnz = 0, sel_rows = 0;
+    int64_t sel_nnz = 0;
     float sel_cw = 0.0f;                 // pool selection key: sum |infeas| + sel_cw * #infeasible rows (per x)
     std::vector<double> dist_mad;        // mean absolute deviation E|V_e - E V_e| of each random element
     std::vector<double> sel_lo, sel_hi;   // training box of the deltas (empty: no row pruning)
@@ -158,7 +194,6 @@ struct TemplateState {
     twosd::DevBuf<int> d_order;       // LP visiting order grouped by pool basis
     twosd::DevBuf<char> d_sort_tmp;
     twosd::DevBuf<int2> d_qrec;       // LP launch: (scenario, start basis) per queue position
-    bool want_head = false;
     bool prep_valid = false;
     bool k_valid = false;         // K rows / ELL of the pool (depend on the pool and the positions)
     twosd::DevBuf<double> d_kcoef;    // k: coef_e(x) = 1 (RHS element) or -x[col] (T element)
@@ -177,10 +212,7 @@ struct TemplateState {
     twosd::DevBuf<double> d_evals;
     size_t earena_slots = 0;      // eta arena (d_eidx, d_evals): LP slots ...
     int earena_cap = 0;           // ... of this many entries each
-    int64_t last_iterlimit = 0;
-    int64_t b0_nnz = 0;
     twosd::DevBuf<unsigned long long> d_stamps;
-    int last_ops_width = 1;
     // LP workspace + outputs
     twosd::DevBuf<int> d_queue;
     twosd::DevBuf<unsigned long long> d_lpstats;   // lp_stats_kernel output (5 words)
@@ -188,16 +220,8 @@ struct TemplateState {
     twosd::DevBuf<int> d_status, d_iters;
     twosd::DevBuf<long long> d_ops;
     twosd::DevBuf<int> d_etan;
-    int64_t last_eta_entries = 0;
-    int64_t last_retries = 0;     // pool starts of the last batch retried from the primary basis
-    int64_t last_ops_sum = 0;
     int out_cap = 0;              // scenarios the per-scenario LP outputs are sized for (rows of d_pi, d_y, d_vkey, d_bkey)
     twosd::DevBuf<double> d_dvtmp;
-    int last_lp_N = 0, last_lp_blocks = 0;
-    int64_t last_pivots_sum = 0;
-    int last_pivots_max = 0;
-    // weighted objective sum of the last batch (sum_s w_s obj_s, fixed-order reduction) and its weight
-    double last_obj_wsum = 0.0, last_obj_w = 0.0;
     twosd::DevBuf<double> d_objpart;
     // out-of-sample moments (eval_moments_kernel): the blocks' partial records, and a grow-only
     // copy of objectives / statuses (the solve at xa of a paired chunk; moments_of_values' upload)
@@ -278,7 +302,7 @@ struct TemplateState {
 struct twosd_ctx : TemplateState {
     int device = 0;
     hipStream_t stream = nullptr;
-    hipEvent_t ev[8] = {};
+    hipEvent_t ev[twosd::EV_COUNT] = {};   // EventSlot
     int num_cus = 256;
     int kmax_override = 0;
     int train_kcap = 0;           // pivot cap of the refresh training solves (> 0; 0: auto; < 0: none): a caller setting
@@ -292,9 +316,8 @@ struct twosd_ctx : TemplateState {
 
 namespace twosd {
 int fail(int code, const char *fmt, ...);
-int prepare_x(twosd_ctx *c, const double *x);
-int run_lp(twosd_ctx *c, const double *x, const double *d_dv, int N, bool want_pi, bool want_y);
-// options of run_lp_ex: vertex keys instead of pi (solve_push), or a list of scenarios to
+int prepare_x(twosd_ctx *c, const double *x);   // pool_select.hip
+// options of run_lp: vertex keys instead of pi (solve_push), or a list of scenarios to
 // re-solve from their recorded pool picks with pi at the list position
 struct LpRun {
     bool want_pi = false, want_y = false, want_key = false;
@@ -304,12 +327,24 @@ struct LpRun {
     const int *d_list = nullptr;  // list mode: scenarios (indices into d_dv) to solve, no selection
     int nlist = 0;
     int kcap = 0;                 // > 0: pivot cap below kmax, no retry from the primary basis (refresh training)
+    double *lp_us_out = nullptr;  // list mode: the launch's LP kernel time (c->last is not written)
 };
-int run_lp_ex(twosd_ctx *c, const double *x, const double *d_dv, int N, const LpRun &o);
-// the pool's host and device forms (api.hip), as the refresh (pool_refresh.hip) needs them; hidden:
-// they were file-local before the refresh had a file of its own, and the library's dynamic
-// symbols stay what they were
+// Launch the LP kernel over N scenarios whose deltas start at d_dv (device); results in
+// c->d_obj / d_pi / d_y / d_status / d_iters [0, N) (lp_batch.hip).
+int run_lp(twosd_ctx *c, const double *x, const double *d_dv, int N, const LpRun &o = LpRun());
+// what one translation unit of the library needs of another (api.hip: the pool's host and device
+// forms; pool_select.hip; lp_batch.hip); hidden: they were file-local while api.hip held it all, and
+// the library's dynamic symbols stay what they were
 #pragma GCC visibility push(hidden)
+double template_value(const twosd_ctx *c, int e);   // at position e, in the caller's space
+void rhs_at(const twosd_ctx *c, const double *x, const double *dv, std::vector<double> &b);   // b = r - T x + deltas
+// SampleParams of n scenarios from first_index of stream `seed`, drawn from the context's distributions into out
+SampleParams sample_params(const twosd_ctx *c, int n, uint64_t seed, uint64_t first_index, double *out);
+// pick[s] = warm-start basis of scenarios [0, N) at the prepared x, c->d_order = the scenarios grouped by pick
+int select_pool(twosd_ctx *c, const double *d_dv, int N, int *d_pick, int npool_override);
+// statistics and objective sums of the batch into c->last, outputs to the host (each nullable);
+// d_w: the batch's scenario weights (nullable: 1.0).  TWOSD_E_LP when some LP is not optimal.
+int copy_lp_outputs(twosd_ctx *c, int N, double *obj, double *pi, double *y, int *status, const double *d_w);
 int ensure_host_pool(twosd_ctx *c);      // host CSR rows and pi0 of device-built bases
 int upload_pool(twosd_ctx *c);
 int prepare_elements(twosd_ctx *c);

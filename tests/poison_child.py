@@ -1,6 +1,6 @@
 """Child process of tests/test_gpu_poison.py (run as `python -m tests.poison_child OUT.npz`).
 
-The allocation-poison hook (TWOSD_POISON / TWOSD_POISON_FAMILY, api.hip) is read once when the
+The allocation-poison hook (TWOSD_POISON / TWOSD_POISON_FAMILY, devbuf.h) is read once when the
 library first allocates, so the parent sets it in this process's environment before anything
 loads the library.  The workload is the refresh path of the bench on storm: two pool refreshes
 (the second composes from device-built start bases), the two-level candidate lists after each,

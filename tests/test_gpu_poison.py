@@ -27,7 +27,7 @@ def _run(tmp_path, tag, poison):
     r = subprocess.run([sys.executable, "-m", "tests.poison_child", str(out)], cwd=ROOT, env=env,
                        capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, f"{tag} child failed ({r.returncode}):\n{r.stderr[-3000:]}"
-    # the hook announces itself once (api.hip poison_byte): the fill really was active
+    # the hook announces itself once (devbuf.h poison_byte): the fill really was active
     assert ("TWOSD_POISON: new device allocations filled with 0xff" in r.stderr) == poison, r.stderr[-2000:]
     with np.load(out) as d:
         return {k: d[k] for k in d.files}
