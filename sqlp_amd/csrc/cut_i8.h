@@ -1,5 +1,5 @@
 // cut_i8.h -- the fixed-point (int8-limb) operands of the cut's integer MFMA pass: the ONE
-// definition of the quantisation, shared by the device kernels (cut_kernel.hip), the host-side
+// definition of the quantisation, shared by the device kernels (cut_prep.hip, cut_argmax.hip), the host-side
 // check program (tests/native/cut_i8_check.cpp) and, by restatement, the numpy model
 // (tests/cut_i8_model.py).
 //

@@ -119,7 +119,7 @@ struct LpBatchRecord {
     double obj_wsum = 0.0, obj_w = 0.0;  // sum_s w_s obj_s (fixed-order reduction) and sum_s w_s
 };
 
-struct CutWs;    // cut_kernel.hip
+struct CutWs;    // cut_common.h
 struct DvsWs;    // dvs_kernel.hip
 struct VkeyWs;   // vkey.hip
 void cut_free(CutWs *w);
@@ -241,7 +241,7 @@ struct TemplateState {
     // dual vertex set
     twosd::DvsDevice dvs;
     std::unique_ptr<twosd::DvsWs, void (*)(twosd::DvsWs *)> dvs_ws{nullptr, twosd::dvs_free};   // dvs scratch (dvs_kernel.hip)
-    // cut workspace (cut_kernel.hip)
+    // cut workspace (cut_common.h: CutWs)
     std::unique_ptr<twosd::CutWs, void (*)(twosd::CutWs *)> cut_ws{nullptr, twosd::cut_free};
     // the last twosd_build_cut / twosd_cut_partial whose picks still sit in the cut workspace:
     // its epigraph (-1: none, or invalidated since), scenarios (0: the empty-epigraph path), |V|
@@ -378,7 +378,7 @@ int vkey_first_occurrences(twosd_ctx *c, int N, const unsigned long long *d_vkey
 // dual vertex set (dvs_kernel.hip)
 int dvs_init(twosd_ctx *c);
 int dvs_push_device(twosd_ctx *c, int count, const double *d_pis, int *d_out_index);
-// cut (cut_kernel.hip)
+// cut: what other subsystems call (cut_kernel.hip; what the cut's own files share is in cut_common.h)
 void cut_invalidate_pk(twosd_ctx *c);
 void cut_truncate_pk(twosd_ctx *c, int size);   // V truncated to size: PK rows past it are stale
 // for boot_kernel.hip: the picks of the last cut (device, last_cut_n ints), and PK (|V| x k4,

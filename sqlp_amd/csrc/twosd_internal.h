@@ -258,5 +258,4 @@ struct DvsDevice {
     int tcap = 0;                 // slots in use of table: a power of two
 };
 
-// ---- cut kernels (cut_kernel.hip) --------------------------------------------------
 }  // namespace twosd

@@ -84,7 +84,7 @@ def synth_template(m2, ncols, k, seed, senses="EGL", neg_costs=True, amp=1.0):
 
 
 # ---- dispatch values, restated from lp_hyper.hip (hyper_rows_per_lane, hyper_cols_per_lane) and
-# cut_kernel.hip (kb_for); the GPU test asserts that every value and every slot edge is covered
+# cut_common.h / cut_plan.h (kCutKBs, cut_kb_for); the GPU test asserts that every value and every slot edge is covered
 HR = [1, 2, 4, 9, 16]
 HC = [2, 4, 8, 14, 16, 28, 32, 64]
 KBS = [1, 2, 4, 6, 8, 12, 16, 22, 24, 30, 32]

@@ -1,4 +1,4 @@
-"""Where the argmax passes spill: compile cut_kernel.hip to gfx950 assembly once with the given -D
+"""Where the argmax passes spill: compile cut_argmax.hip to gfx950 assembly once with the given -D
 flags, and for each requested instantiation cut_argmax<pass>_kernel<KB> (pass 2 = fp64, 3 = fp32,
 4 = integer) count, per loop (a branch back to an earlier label), the MFMAs, LDS reads, scratch
 loads / stores, VALU-ish and s_barrier instructions.  CPU only.
@@ -14,7 +14,7 @@ import sys
 import tempfile
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SRC = os.path.join(ROOT, "sqlp_amd", "csrc", "cut_kernel.hip")
+SRC = os.path.join(ROOT, "sqlp_amd", "csrc", "cut_argmax.hip")
 KBS = (1, 2, 4, 6, 8, 12, 16, 22, 24, 30, 32)
 
 
