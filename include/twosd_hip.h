@@ -266,6 +266,53 @@ int twosd_add_sampled_scenarios(twosd_ctx *ctx, int epi, int N, uint64_t seed, u
 int twosd_get_scenarios(twosd_ctx *ctx, int epi, int first, int count, double *values);
 
 /*
+ * Joint discrete distributions (SMPS BLOCKS DISCRETE / SCENARIOS DISCRETE).
+ * A block is an ordered list of member elements e_0, e_1, ..., e_{n-1}: indices into the
+ * random-position layout in the order the caller lists them, not necessarily contiguous or
+ * ascending.  It has R >= 1 realisations in the caller's order; realisation r has probability
+ * p_r >= 0 and one value per member, V[r][j].  Realisations are not sorted, not deduplicated and
+ * not normalised (as DISCRETE treats its probabilities).  The block's lead is e_0.
+ *
+ * For global scenario index g all members use the words of Philox counter (g_lo, g_hi, lead, 0)
+ * under key seed; the element word of an element outside a block is its own index, so no two draw
+ * units share a counter.  With u1 = u01(w0, w1), the realisation index is the DISCRETE walk over
+ * the block's probabilities,
+ *     i = 0, cp = p_0; while (cp <= u && i < R - 1) cp = cp + p_{++i}      (plain fp64 additions)
+ * and member e_j stores V[i][j] - template_value(e_j).  Under a sampling plan (below):
+ *   IID         u = u1.
+ *   ANTITHETIC  both members of pair g >> 1 use the words of index 2 (g >> 1); the odd member walks
+ *               at 1 - u1.
+ *   LHS         the permutation is that of (LHS block b, lead), u1 that of (g, lead), and
+ *               u = min((perm[j] + u1) / S, 1 - 2^-53): the LHS formula with lead in place of e.
+ * The library finds i by binary search in the walk's running sums (built with the same sequential
+ * additions): the first i whose sum exceeds u, else R - 1.  The sums never decrease, so this is
+ * the walk's index exactly, also where u equals a sum, across zero-probability realisations and
+ * with total mass below 1.
+ * Consequences: a one-member block whose values ascend is, bit for bit, the DISCRETE stream of
+ * that element under all three plans; and a stream stays a pure function of (seed, global index,
+ * element, plan, tables), so any sharding on group boundaries reproduces it.
+ *
+ * set_distributions_joint: kind / nsupport / values / probs / param0 / param1 as in
+ *   twosd_set_distributions, where kind[e] = TWOSD_DIST_BLOCK marks a block member (nsupport[e] is
+ *   ignored, it owns no entries of values / probs).  Block b has members
+ *   members[member_off[b] .. member_off[b + 1]), nreal[b] realisations, its probabilities
+ *   concatenated in block_probs and its values, realisation-major [nreal][n_members], in
+ *   block_values.  nblocks == 0 is twosd_set_distributions; that call itself still refuses kind 3,
+ *   and a later call of it drops the blocks.  Reset like the other tables (twosd_set_template,
+ *   twosd_set_random_positions).
+ *   TWOSD_E_ARG, leaving the previous tables in use, for: an element of kind 3 that is in no
+ *   block; an element in two blocks or twice in one; a member whose kind is not 3; nreal < 1; an
+ *   empty block; a negative or non-finite probability; a non-finite value; a member index outside
+ *   [0, k).  TWOSD_E_UNSUPPORTED when the probabilities or the values of all blocks together
+ *   exceed 2^31 - 1 entries (table offsets are 32-bit).
+ */
+#define TWOSD_DIST_BLOCK 3
+int twosd_set_distributions_joint(twosd_ctx *ctx, int k, const int *kind, const int *nsupport, const double *values,
+                                  const double *probs, const double *param0, const double *param1, int nblocks,
+                                  const int *member_off, const int *members, const int *nreal, const double *block_probs,
+                                  const double *block_values);
+
+/*
  * Variance-reduced scenario streams (no reference counterpart: the reference's readme lists
  * "Implement SMPS sampling methods (antithetic, stratified)" as open).  A sampling plan makes
  * groups of `group` = G consecutive global scenario indices [G b, G b + G) dependent; a stream

@@ -115,7 +115,10 @@ SIGNATURES = [
     ("twosd_bootstrap_counts_vr", I, [P, I, C.c_uint64, C.c_uint64, C.c_int64, P, P]),
     ("twosd_reform_cuts_vr", I, [P, I, I, P, I, C.c_uint64, C.c_uint64, P, P, P, P, P]),
     ("twosd_reform_partial_vr", I, [P, I, I, P, I, C.c_uint64, C.c_uint64, D, P, P, P]),
+    ("twosd_set_distributions_joint", I, [P, I, P, P, P, P, P, P, I, P, P, P, P, P]),
 ]
+
+DIST_DISCRETE, DIST_NORMAL, DIST_UNIFORM, DIST_BLOCK = 0, 1, 2, 3
 
 SAMPLING_IID, SAMPLING_ANTITHETIC, SAMPLING_LHS = 0, 1, 2
 

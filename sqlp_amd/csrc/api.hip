@@ -394,6 +394,7 @@ extern "C" int twosd_set_random_positions(twosd_ctx *c, int k, const int *row, c
     c->prep_valid = false;
     c->k_valid = false;
     c->has_dist = false;
+    c->has_blocks = false;
     cut_invalidate_pk(c);
     c->boot = twosd::BootState();   // stored picks and the re-formation's template copies
     return TWOSD_OK;
@@ -800,8 +801,11 @@ extern "C" int twosd_add_scenarios(twosd_ctx *c, int epi, int N, const double *v
     return TWOSD_OK;
 }
 
-extern "C" int twosd_set_distributions(twosd_ctx *c, int k, const int *kind, const int *nsupport, const double *values,
-                                       const double *probs, const double *param0, const double *param1) {
+// twosd_set_distributions (nblocks == 0, kind 3 unknown) and twosd_set_distributions_joint: every
+// check runs before the first upload, so a refused call leaves the previous tables in use
+static int set_distributions(twosd_ctx *c, int k, const int *kind, const int *nsupport, const double *values, const double *probs,
+                             const double *param0, const double *param1, bool joint, int nblocks, const int *member_off,
+                             const int *members, const int *nreal, const double *block_probs, const double *block_values) {
     if (!c || !c->has_template) return fail(TWOSD_E_STATE, "set_distributions: no template");
     if (k != c->k) return fail(TWOSD_E_ARG, "set_distributions: %d distributions for %d random elements", k, c->k);
     if (k > 0 && (!kind || !nsupport || !param0 || !param1)) return fail(TWOSD_E_ARG, "set_distributions: NULL argument");
@@ -832,16 +836,31 @@ extern "C" int twosd_set_distributions(twosd_ctx *c, int k, const int *kind, con
         } else if (kind[e] == 2) {   // UNIFORM(left, right)
             p0[e] = param0[e];
             p1[e] = param1[e];
-        } else {
+        } else if (!(joint && kind[e] == TWOSD_DIST_BLOCK)) {   // a block member's values come from its block
             return fail(TWOSD_E_ARG, "set_distributions: element %d has unknown kind %d", e, kind[e]);
         }
         off[e + 1] = (int)val.size();
+    }
+    DistTables B;
+    int where = -1;
+    if (const int err = dist_tables_build(k, kind, joint ? nblocks : 0, member_off, members, nreal, block_probs, block_values, B, &where)) {
+        return fail(err == DT_E_TOO_LARGE ? TWOSD_E_UNSUPPORTED : TWOSD_E_ARG, "set_distributions_joint: %s (%s %d)", dist_err_text(err),
+                    err == DT_E_NO_BLOCK ? "element" : "block", where);
     }
     int rc;
     if ((rc = c->d_dist_kind.upload(kd)) || (rc = c->d_dist_off.upload(off)) || (rc = c->d_dist_val.upload(val)) ||
         (rc = c->d_dist_prob.upload(prob)) || (rc = c->d_dist_p0.upload(p0)) || (rc = c->d_dist_p1.upload(p1)) ||
         (rc = c->d_dist_tmpl.upload(tmpl)))
         return rc;
+    c->has_blocks = false;
+    if (B.block.empty()) {   // a plain call, or a joint one without blocks, drops the block tables
+        c->d_dist_elead.release(); c->d_dist_eblk.release(); c->d_dist_ecol.release();
+        c->d_dist_binfo.release(); c->d_dist_bcum.release(); c->d_dist_bval.release();
+    } else if ((rc = c->d_dist_elead.upload(B.lead)) || (rc = c->d_dist_eblk.upload(B.blk)) || (rc = c->d_dist_ecol.upload(B.col)) ||
+               (rc = c->d_dist_binfo.upload(B.block)) || (rc = c->d_dist_bcum.upload(B.cum)) || (rc = c->d_dist_bval.upload(B.val))) {
+        c->has_dist = false;   // a failed upload leaves no usable tables
+        return rc;
+    }
     // mean absolute deviation E|V_e - E V_e| per element: the spread of the scenarios (the scale
     // of the selection key's count weight)
     c->dist_mad.assign(std::max(k, 1), 0.0);
@@ -855,13 +874,30 @@ extern "C" int twosd_set_distributions(twosd_ctx *c, int k, const int *kind, con
             mad = ps > 0.0 ? mad / ps : 0.0;
         } else if (kd[e] == 1) {   // Normal(mu, sigma): sigma sqrt(2 / pi)
             mad = p1[e] * std::sqrt(2.0 / M_PI);
+        } else if (kd[e] == TWOSD_DIST_BLOCK) {   // the member's marginal over the realisations
+            mad = dist_member_mad(B, B.blk[e], B.col[e]);
         } else {                   // Uniform(a, b): |b - a| / 4
             mad = 0.25 * fabs(p1[e] - p0[e]);
         }
         c->dist_mad[e] = std::isfinite(mad) ? mad : 0.0;
     }
+    c->has_blocks = !B.block.empty();
     c->has_dist = true;
     return TWOSD_OK;
+}
+
+extern "C" int twosd_set_distributions(twosd_ctx *c, int k, const int *kind, const int *nsupport, const double *values,
+                                       const double *probs, const double *param0, const double *param1) {
+    return set_distributions(c, k, kind, nsupport, values, probs, param0, param1, false, 0, nullptr, nullptr, nullptr, nullptr, nullptr);
+}
+
+extern "C" int twosd_set_distributions_joint(twosd_ctx *c, int k, const int *kind, const int *nsupport, const double *values,
+                                             const double *probs, const double *param0, const double *param1, int nblocks,
+                                             const int *member_off, const int *members, const int *nreal,
+                                             const double *block_probs, const double *block_values) {
+    if (nblocks < 0) return fail(TWOSD_E_ARG, "set_distributions_joint: nblocks < 0");
+    return set_distributions(c, k, kind, nsupport, values, probs, param0, param1, true, nblocks, member_off, members, nreal,
+                             block_probs, block_values);
 }
 
 // a caller's sampling plan -> (mode, G); NULL means i.i.d.
@@ -900,6 +936,9 @@ SampleParams twosd::sample_params(const twosd_ctx *c, int n, uint64_t seed, uint
     S.N = n; S.k = c->k; S.seed = seed; S.first_index = first_index;
     S.kind = c->d_dist_kind; S.off = c->d_dist_off; S.val = c->d_dist_val; S.prob = c->d_dist_prob;
     S.p0 = c->d_dist_p0; S.p1 = c->d_dist_p1; S.tmpl = c->d_dist_tmpl; S.out = out;
+    S.blocks = c->has_blocks;
+    S.elead = c->d_dist_elead; S.eblk = c->d_dist_eblk; S.ecol = c->d_dist_ecol;
+    S.binfo = c->d_dist_binfo; S.bcum = c->d_dist_bcum; S.bval = c->d_dist_bval;
     return S;
 }
 

@@ -236,6 +236,12 @@ struct TemplateState {
     bool has_dist = false;
     twosd::DevBuf<int> d_dist_kind, d_dist_off;
     twosd::DevBuf<double> d_dist_val, d_dist_prob, d_dist_p0, d_dist_p1, d_dist_tmpl;
+    // joint discrete blocks (twosd_set_distributions_joint; dist_tables.h): per element lead /
+    // block / column, per block its record, the running sums and the values
+    bool has_blocks = false;
+    twosd::DevBuf<int> d_dist_elead, d_dist_eblk, d_dist_ecol;
+    twosd::DevBuf<twosd::DistBlock> d_dist_binfo;
+    twosd::DevBuf<double> d_dist_bcum, d_dist_bval;
     // epigraphs
     std::vector<twosd::EpiDevice> epis;
     // dual vertex set

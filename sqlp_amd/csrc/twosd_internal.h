@@ -6,6 +6,7 @@
 #include <vector>
 #include "twosd_hip.h"
 #include "devbuf.h"
+#include "dist_tables.h"
 
 namespace twosd {
 
@@ -206,12 +207,17 @@ int hyper_max_blocks_per_cu(int R, int C, int kmax, int k);
 struct SampleParams {
     int N, k;
     unsigned long long seed, first_index;
-    const int *kind;                      // k: 0 DISCRETE, 1 NORMAL, 2 UNIFORM
+    const int *kind;                      // k: 0 DISCRETE, 1 NORMAL, 2 UNIFORM, 3 member of a block
     const int *off;                       // k + 1: DISCRETE support ranges into val / prob
     const double *val, *prob;             // DISCRETE support (ascending) and probabilities
     const double *p0, *p1;                // NORMAL mean / sd, UNIFORM left / right
     const double *tmpl;                   // k template values
     double *out;                          // N x k deltas
+    // joint discrete blocks (dist_tables.h); read by the kBlocks instantiations only
+    bool blocks;                          // the context has blocks: launch the kBlocks kernels
+    const int *elead, *eblk, *ecol;       // k: the element word (a block's lead; e outside one), block, column j
+    const DistBlock *binfo;               // per block: R, n, offsets into bcum / bval
+    const double *bcum, *bval;            // running sums of p_r; values, per block [R][n]
 };
 hipError_t launch_sample(const SampleParams &S, hipStream_t st);
 // the stream of a sampling plan (twosd_sampling: mode, group G); S.first_index and S.N are

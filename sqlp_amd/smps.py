@@ -3,7 +3,8 @@
 Mirrors the reference's reader (names and semantics):
   read_cor                 src/smps/smps_cor.jl:160-194 (tokenizer :26-58, bounds :124-155)
   read_tim                 src/smps/smps_tim.jl:30-64
-  read_sto                 src/smps/smps_sto.jl:41-110
+  read_sto                 src/smps/smps_sto.jl:41-110 (INDEP); BLOCKS DISCRETE and two-stage
+                           SCENARIOS DISCRETE have no reference counterpart (data/smps/README.md)
   get_smps_stage_template  src/smps/smps_prob.jl:14-102
   rand(sto)                src/smps/smps_sto.jl:117-149 (DISCRETE / NORMAL(mean, variance) /
                            UNIFORM), here vectorised with numpy's PCG64 -- Julia's RNG
@@ -52,9 +53,22 @@ class spTimType:
 
 
 @dataclass
+class spStoBlock:
+    """A joint discrete distribution: realisation r has probability probs[r] and gives member
+    positions[j] the value values[r][j].  Realisations keep the file's order; nothing is sorted,
+    merged or normalised."""
+    name: str
+    period: str
+    positions: list          # spSmpsPosition, in first-appearance order
+    probs: list              # R
+    values: list             # R rows of len(positions)
+
+
+@dataclass
 class spStoType:
     problem_name: str
     indep: dict = field(default_factory=dict)   # position -> (kind, a, b); insertion ordered
+    blocks: list = field(default_factory=list)  # spStoBlock, file order
 
 
 def _lines(path):
@@ -138,14 +152,83 @@ def read_tim(path) -> spTimType:
     return spTimType(name, periods)
 
 
-def read_sto(path) -> spStoType:
+def _probability(tok, what):
+    try:
+        p = float(tok)
+    except ValueError:
+        raise ValueError(f"{what}: probability {tok!r} is not a number") from None
+    if not p >= 0.0 or p == float("inf"):
+        raise ValueError(f"{what}: probability {tok!r} is negative or not finite")
+    return p
+
+
+def _template_value(cor, pos):
+    """The core file's value at a random position (RHS entry or matrix coefficient)."""
+    if cor is None:
+        raise ValueError(f"SCENARIOS: {tuple(pos)} inherits from ROOT, which needs the core file (read_sto(path, cor))")
+    i = cor.row_mapping[pos.row_name]
+    if pos.col_name in ("RHS", "rhs"):
+        return float(cor.rhs[i])
+    return float(cor.entries.get((i, cor.col_mapping[pos.col_name]), 0.0))
+
+
+def read_sto(path, cor: spCorType = None) -> spStoType:
+    """INDEP (DISCRETE / NORMAL / UNIFORM), BLOCKS DISCRETE and two-stage SCENARIOS DISCRETE.
+    Several INDEP and BLOCKS sections may follow each other in any order; SCENARIOS stands alone.
+    `cor` supplies the values a SCENARIOS scenario inherits from ROOT."""
     sto = spStoType("")
     section, kw = "", []
+    blocks = {}                 # name -> spStoBlock (BLOCKS)
+    cur = None                  # (block, realisation row) the value lines go to
+    scen, scen_pos, scen_cur = {}, [], None   # SCENARIOS: name -> [parent, prob, period, {pos: value}]
+    seen = set()
     for line in _lines(path):
         if not line or line[0] == '*':
             continue
         t = line.split()
         if line[0] == ' ':
+            if section == "BLOCKS":
+                if t[0] == "BL" and len(t) == 4:
+                    name, period, p = t[1], t[2], _probability(t[3], f"block {t[1]}")
+                    if name not in blocks:
+                        blocks[name] = spStoBlock(name, period, [], [], [])
+                        sto.blocks.append(blocks[name])
+                    b = blocks[name]
+                    if b.period != period:
+                        raise ValueError(f"block {name}: period {period!r} after {b.period!r}")
+                    b.probs.append(p)
+                    b.values.append(list(b.values[0]) if b.values else [])   # omitted members: the first realisation's
+                    cur = b
+                    continue
+                if cur is None:
+                    raise ValueError(f"BLOCKS: value line before the first BL line: {line.strip()!r}")
+                pos, v = spSmpsPosition(t[0], t[1]), float(t[2])
+                if len(cur.values) == 1:          # the first realisation fixes the members and their order
+                    if pos in cur.positions:
+                        raise ValueError(f"block {cur.name}: {tuple(pos)} listed twice in its first realisation")
+                    cur.positions.append(pos)
+                    cur.values[0].append(v)
+                elif pos not in cur.positions:
+                    raise ValueError(f"block {cur.name}: {tuple(pos)} is absent from its first realisation")
+                else:
+                    cur.values[-1][cur.positions.index(pos)] = v
+                continue
+            if section == "SCENARIOS":
+                if t[0] == "SC" and len(t) == 5:
+                    name, parent, p = t[1], t[2].strip("'"), _probability(t[3], f"scenario {t[1]}")
+                    if name in scen:
+                        raise ValueError(f"scenario {name} defined twice")
+                    if parent != "ROOT" and parent not in scen:
+                        raise ValueError(f"scenario {name}: parent {parent!r} is not defined earlier in the file")
+                    scen[name] = scen_cur = [parent, p, t[4], {}]
+                    continue
+                if scen_cur is None:
+                    raise ValueError(f"SCENARIOS: value line before the first SC line: {line.strip()!r}")
+                pos = spSmpsPosition(t[0], t[1])
+                if pos not in scen_pos:
+                    scen_pos.append(pos)
+                scen_cur[3][pos] = float(t[2])
+                continue
             if section != "INDEP":
                 continue
             if len(kw) > 1:
@@ -164,11 +247,40 @@ def read_sto(path) -> spStoType:
                 raise ValueError(f"Unknown or unsupported section_keywords {kw}")
         else:
             section = t[0]
-            if section not in ("STOCH", "INDEP", "ENDATA"):
+            if section not in ("STOCH", "INDEP", "BLOCKS", "SCENARIOS", "ENDATA"):
                 raise AssertionError(f"unsupported STO section {section!r}")
             kw = t[1:]
+            cur = None
+            seen.add(section)
             if section == "STOCH":
                 sto.problem_name = kw[0]
+            elif section in ("BLOCKS", "SCENARIOS") and kw != ["DISCRETE"]:
+                raise ValueError(f"unsupported {section} keywords {kw}: only DISCRETE is read")
+            if "SCENARIOS" in seen and ("INDEP" in seen or "BLOCKS" in seen):
+                raise ValueError("SCENARIOS cannot be combined with INDEP or BLOCKS in one file")
+    if scen:
+        # one block over the union of the positions, one realisation per scenario; a position a
+        # scenario omits takes its parent's value, ROOT's being the core file's
+        rows = {}
+        for name, (parent, _, _, given) in scen.items():
+            base = rows[parent] if parent != "ROOT" else None
+            rows[name] = [given[pos] if pos in given else base[j] if base is not None else _template_value(cor, pos)
+                          for j, pos in enumerate(scen_pos)]
+        periods = {v[2] for v in scen.values()}
+        if len(periods) > 1:
+            raise ValueError(f"SCENARIOS: two-stage files only, found periods {sorted(periods)}")
+        sto.blocks.append(spStoBlock("SCENARIOS", periods.pop(), scen_pos, [v[1] for v in scen.values()],
+                                     [rows[name] for name in scen]))
+    owner = {}
+    for b in sto.blocks:
+        if not b.positions:
+            raise ValueError(f"block {b.name} has no members")
+        for pos in b.positions:
+            if pos in sto.indep:
+                raise ValueError(f"{tuple(pos)} is in block {b.name} and in INDEP")
+            if pos in owner:
+                raise ValueError(f"{tuple(pos)} is in blocks {owner[pos]} and {b.name}")
+            owner[pos] = b.name
     return sto
 
 
@@ -257,16 +369,28 @@ def load_smps(directory, name=None):
     """(cor, tim, sto) of an SMPS triple <dir>/<name>.{cor,tim,sto}."""
     name = name or os.path.basename(os.path.normpath(directory))
     base = os.path.join(directory, name)
-    return read_cor(base + ".cor"), read_tim(base + ".tim"), read_sto(base + ".sto")
+    cor = read_cor(base + ".cor")
+    return cor, read_tim(base + ".tim"), read_sto(base + ".sto", cor)
 
 
 # ---------------------------------------------------------------------- scenarios
+def sto_positions(sto: spStoType) -> list:
+    """The random-element layout of a sto: the INDEP positions, then every block's members in
+    file order (on a file without blocks: the INDEP positions as before)."""
+    return list(sto.indep.keys()) + [p for b in sto.blocks for p in b.positions]
+
+
+def _block_members(sto: spStoType) -> dict:
+    """position -> (block index, member column)"""
+    return {p: (bi, j) for bi, b in enumerate(sto.blocks) for j, p in enumerate(b.positions)}
+
+
 def scenario_positions(sp2: spStageProblem, sto: spStoType):
     """Random-element layout for the C ABI: (positions, row[k], col[k] (-1 = RHS)).
     Row/column lookups raise KeyError like delta_coefficients (subprob.jl:112,116)."""
     rowm = {n: i for i, n in enumerate(sp2.stage_constraints)}
     colm = {n: j for j, n in enumerate(sp2.last_stage_vars)}
-    positions = list(sto.indep.keys())
+    positions = sto_positions(sto)
     rows = np.array([rowm[p.row_name] for p in positions], dtype=np.int32)
     cols = np.array([-1 if p.col_name in ("RHS", "rhs") else colm[p.col_name] for p in positions], dtype=np.int32)
     return positions, rows, cols
@@ -274,10 +398,23 @@ def scenario_positions(sp2: spStageProblem, sto: spStoType):
 
 def sample_values(sto: spStoType, N: int, rng: np.random.Generator, positions=None) -> np.ndarray:
     """N i.i.d. draws of every independent element (rand(sto), smps_sto.jl:140-149):
-    N x k values in `positions` order.  NORMAL uses sqrt(variance) (smps_sto.jl:122-125)."""
-    positions = positions if positions is not None else list(sto.indep.keys())
+    N x k values in `positions` order.  NORMAL uses sqrt(variance) (smps_sto.jl:122-125).
+    A block draws one uniform per scenario (at its first member in `positions`), so every row holds
+    one of its realisations."""
+    positions = positions if positions is not None else sto_positions(sto)
+    members = _block_members(sto) if sto.blocks else {}
+    picks = {}
     out = np.empty((N, len(positions)))
     for e, p in enumerate(positions):
+        if p in members:
+            bi, j = members[p]
+            b = sto.blocks[bi]
+            if bi not in picks:
+                cdf = np.cumsum(np.asarray(b.probs, dtype=np.float64))
+                u = rng.random(N) * cdf[-1]
+                picks[bi] = np.minimum(np.searchsorted(cdf, u, side="right"), len(cdf) - 1)
+            out[:, e] = np.asarray(b.values, dtype=np.float64)[picks[bi], j]
+            continue
         d = sto.indep[p]
         if d[0] == "DISCRETE":
             vals = np.asarray(d[1], dtype=np.float64)
@@ -292,9 +429,16 @@ def sample_values(sto: spStoType, N: int, rng: np.random.Generator, positions=No
 
 
 def mean_values(sto: spStoType, positions=None) -> np.ndarray:
-    positions = positions if positions is not None else list(sto.indep.keys())
+    """Mean of every element; a block member's is sum p v / sum p over the realisations."""
+    positions = positions if positions is not None else sto_positions(sto)
+    members = _block_members(sto) if sto.blocks else {}
     out = []
     for p in positions:
+        if p in members:
+            bi, j = members[p]
+            b = sto.blocks[bi]
+            out.append(float(np.dot(b.probs, np.asarray(b.values, dtype=np.float64)[:, j]) / np.sum(b.probs)))
+            continue
         d = sto.indep[p]
         if d[0] == "DISCRETE":
             out.append(float(np.dot(d[1], d[2]) / np.sum(d[2])))
@@ -303,3 +447,46 @@ def mean_values(sto: spStoType, positions=None) -> np.ndarray:
         else:
             out.append(0.5 * (d[1] + d[2]))
     return np.array(out)
+
+
+def joint_support(sto: spStoType, positions=None, max_points=1 << 20):
+    """(values[R_total, k], probs[R_total]) of an all-discrete sto: the product of the INDEP
+    DISCRETE supports and the blocks' realisations, columns in `positions` order, the first factor
+    (INDEP elements in file order, then the blocks) varying slowest.  A row's probability is the
+    product of its factors' probabilities as the file states them (not normalised), so
+    sum(probs * f(values)) / sum(probs) is an exact expectation.  ValueError for a NORMAL or
+    UNIFORM element, for a position the sto does not hold, and past max_points rows."""
+    positions = positions if positions is not None else sto_positions(sto)
+    index = {p: e for e, p in enumerate(positions)}
+    if len(index) != len(positions):
+        raise ValueError("joint_support: a position is listed twice")
+    factors = []                       # (columns, values[R, n], probs[R])
+    for p, d in sto.indep.items():
+        if d[0] != "DISCRETE":
+            raise ValueError(f"joint_support: {tuple(p)} is {d[0]}, not DISCRETE")
+        factors.append(([p], np.asarray(d[1], dtype=np.float64)[:, None], np.asarray(d[2], dtype=np.float64)))
+    for b in sto.blocks:
+        factors.append((b.positions, np.asarray(b.values, dtype=np.float64).reshape(len(b.probs), len(b.positions)),
+                        np.asarray(b.probs, dtype=np.float64)))
+    known = {p for f in factors for p in f[0]}
+    for p in positions:
+        if p not in known:
+            raise ValueError(f"joint_support: {tuple(p)} is not a random element of this sto")
+    factors = [f for f in factors if all(p in index for p in f[0])]
+    if sum(len(f[0]) for f in factors) != len(positions):
+        raise ValueError("joint_support: positions must hold whole blocks")
+    total = 1
+    for f in factors:
+        total *= len(f[2])
+        if total > max_points:
+            raise ValueError(f"joint_support: more than max_points = {max_points} points")
+    values = np.empty((total, len(positions)))
+    probs = np.ones(total)
+    inner = total
+    for cols, v, p in factors:
+        inner //= len(p)
+        pick = (np.arange(total) // inner) % len(p)
+        probs *= p[pick]
+        for j, pos in enumerate(cols):
+            values[:, index[pos]] = v[pick, j]
+    return values, probs

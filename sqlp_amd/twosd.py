@@ -22,7 +22,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import check, ptr
-from .smps import spStageProblem, spSmpsPosition, scenario_positions
+from .smps import spStageProblem, spSmpsPosition, scenario_positions, sto_positions
 
 MIN_SENSE = "MIN_SENSE"
 # argmax tie rule: 0 = the reference's strict '>' (subprob.jl:156, first maximum in insertion
@@ -146,7 +146,7 @@ class SDContext:
         self.row_lookup = {n: i for i, n in enumerate(sp2.stage_constraints)}
         self.col_lookup = {n: j for j, n in enumerate(sp2.last_stage_vars)}
         if sto is not None and positions is None:
-            positions = list(sto.indep.keys())
+            positions = sto_positions(sto)
         self.set_positions(positions or [])
         self.has_basis = False
 
@@ -397,9 +397,16 @@ class SDContext:
 
     # -- on-device scenario sampler (rand(rng, sto), smps_sto.jl:117-149) ----------
     def set_distributions(self, sto):
-        """Upload the independent distribution of every random element (position order)."""
+        """Upload the distribution of every random element (position order): the independent ones,
+        and the joint discrete blocks of sto.blocks (twosd_set_distributions_joint; every member of
+        a block must be a position of this context)."""
+        blocks = getattr(sto, "blocks", [])
+        member = {p for b in blocks for p in b.positions}
         kinds, nsup, vals, probs, p0, p1 = [], [], [], [], [], []
         for pos in self.positions:
+            if pos in member:
+                kinds.append(_lib.DIST_BLOCK); nsup.append(0); p0.append(0.0); p1.append(0.0)
+                continue
             d = sto.indep[pos]
             if d[0] == "DISCRETE":
                 kinds.append(0); nsup.append(len(d[1])); vals += list(d[1]); probs += list(d[2])
@@ -410,7 +417,19 @@ class SDContext:
                 kinds.append(2); nsup.append(0); p0.append(d[1]); p1.append(d[2])
         a = [np.ascontiguousarray(kinds, dtype=np.int32), np.ascontiguousarray(nsup, dtype=np.int32),
              _f64(vals if vals else [0.0]), _f64(probs if probs else [0.0]), _f64(p0), _f64(p1)]
-        check(self.lib.twosd_set_distributions(self.h, self.k, *[ptr(v) for v in a]))
+        if not blocks:
+            check(self.lib.twosd_set_distributions(self.h, self.k, *[ptr(v) for v in a]))
+            return
+        moff, mem, nreal, bp, bv = [0], [], [], [], []
+        for b in blocks:
+            mem += [self.pos_index[p] for p in b.positions]
+            moff.append(len(mem))
+            nreal.append(len(b.probs))
+            bp += list(b.probs)
+            bv += list(np.asarray(b.values, dtype=np.float64).reshape(len(b.probs), len(b.positions)).ravel())
+        j = [np.ascontiguousarray(moff, dtype=np.int32), np.ascontiguousarray(mem, dtype=np.int32),
+             np.ascontiguousarray(nreal, dtype=np.int32), _f64(bp), _f64(bv)]
+        check(self.lib.twosd_set_distributions_joint(self.h, self.k, *[ptr(v) for v in a], len(blocks), *[ptr(v) for v in j]))
 
     def scenario_values(self, scenario) -> np.ndarray:
         """spSmpsScenario (list of position => value) -> value vector in layout order.
