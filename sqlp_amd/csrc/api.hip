@@ -4,9 +4,10 @@
 //   template (W CSC, q, bound types), shared warm-start basis (B0^{-1}, pi0), per-epigraph
 //   scenario pools (deltas, weights), the dual vertex set, and the LP/cut workspaces.
 // Every call is synchronous on the context's own HIP stream.
-// Here: errors, create / destroy, canonical form, template, positions, the host basis and pool
-// (build, upload), epigraphs, distributions, sampling plans.  The per-x preparation and warm-start
-// selection are in pool_select.hip, the LP launch with its outputs and solve_* in lp_batch.hip,
+// Here: errors, create / destroy, canonical form, template, positions, epigraphs and scenarios,
+// distributions, sampling plans.  The warm-start basis pool (host forms, upload, validity, the
+// basis and pool calls of the ABI) is in basis_pool.hip, the per-x preparation and warm-start
+// selection in pool_select.hip, the LP launch with its outputs and solve_* in lp_batch.hip,
 // out-of-sample evaluation in evaluate.hip, the pool refresh in pool_refresh.hip.
 #include <hip/hip_runtime.h>
 #include <algorithm>
@@ -17,10 +18,7 @@
 #include <cstring>
 #include <string>
 #include <vector>
-#include <map>
 #include <memory>
-#include <thread>
-#include <chrono>
 #include "twosd_internal.h"
 #include "twosd_ctx.h"
 
@@ -57,50 +55,6 @@ extern "C" int twosd_create(int device, twosd_ctx **out) {
     const char *km = getenv("TWOSD_KMAX");
     if (km) c->kmax_override = atoi(km);
     *out = c.release();
-    return TWOSD_OK;
-}
-
-// the pool no longer matches the device arrays (a failed build or head read-back): keep only
-// the primary basis (a host basis) and refuse solves until a basis is installed again
-int twosd::drop_pool(twosd_ctx *c, int code) {
-    if (c->pool.size() > 1) c->pool.resize(1);
-    c->has_basis = false;
-    c->prep_valid = false;
-    c->k_valid = false;
-    c->pool_hb_valid = false;
-    reset_candidates(c);
-    return code;
-}
-
-// head of pool basis p into *h (materialised from c->pool_hb for a device-built basis on first
-// use: a refresh of 4096 bases would otherwise spend ~2 ms building host heads nobody reads).
-// A failed device read-back drops the pool (drop_pool) and returns TWOSD_E_DEVICE.
-static int head_of(twosd_ctx *c, int p, const std::vector<int> **h) {
-    PoolBasis &B = c->pool[p];
-    if (B.hb_row >= 0 && !c->pool_hb_valid) {
-        // the heads of a device-built pool are fetched on the first host use, not by the refresh
-        // (at N = 8 every rank would copy 9 MB per step that only tests and the CPU baseline read)
-        const size_t need = c->pool.size() * (size_t)c->MP;
-        if (!c->pool_hb.reserve<int>(need))
-            return drop_pool(c, fail(TWOSD_E_DEVICE, "pool heads: pinned allocation of %zu ints failed", need));
-        hipError_t e = hipMemcpyAsync(c->pool_hb.p, c->d_hb0, sizeof(int) * need, hipMemcpyDeviceToHost, c->stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-        if (e != hipSuccess) return drop_pool(c, fail(TWOSD_E_DEVICE, "pool heads: read-back failed: %s", hipGetErrorString(e)));
-        c->pool_hb_valid = true;
-    }
-    if (B.hb_row >= 0) {
-        const int m = c->L.m;
-        const int *r = c->pool_hb.as<int>() + (size_t)B.hb_row * c->MP;
-        B.head.resize(m);
-        for (int i = 0; i < m; ++i) B.head[i] = r[i] >> 2;
-        B.hb_row = -1;
-    }
-    if (h) *h = &B.head;
-    return TWOSD_OK;
-}
-static int materialize_heads(twosd_ctx *c) {
-    for (int p = 0; p < (int)c->pool.size(); ++p)
-        if (int rc = head_of(c, p, nullptr)) return rc;
     return TWOSD_OK;
 }
 
@@ -391,8 +345,7 @@ extern "C" int twosd_set_random_positions(twosd_ctx *c, int k, const int *row, c
     }
     c->pos_row.swap(pr); c->pos_col.swap(pc);
     c->k = k;
-    c->prep_valid = false;
-    c->k_valid = false;
+    pool_positions_changed(c);
     c->has_dist = false;
     c->has_blocks = false;
     cut_invalidate_pk(c);
@@ -422,349 +375,6 @@ void twosd::rhs_at(const twosd_ctx *c, const double *x, const double *dv, std::v
             const int cc = c->pos_col[e];
             b[c->pos_row[e]] += cc < 0 ? dv[e] : -dv[e] * (x ? x[cc] : 0.0);
         }
-}
-
-// validate a basis head (valid distinct columns, nonsingular, dual feasible for q) and
-// compute its inverse; thread-safe, returns nullptr or the reason it was rejected
-static const char *compute_pool_basis(const twosd_ctx *c, const std::vector<int> &head, PoolBasis &pb) {
-    const HostLP &L = c->L;
-    const int m = L.m, n = L.n;
-    std::vector<char> seen(n + m, 0);
-    for (int i = 0; i < m; ++i) {
-        if (head[i] < 0 || head[i] >= n + m || seen[head[i]]) return "basis head has an invalid or duplicate column";
-        seen[head[i]] = 1;
-    }
-    std::vector<double> B;
-    basis_matrix(L, head, B);
-    if (!dense_inverse(m, B, pb.Binv)) return "basis matrix is singular";
-    const double dinf = basis_dual_infeasibility(L, head, pb.Binv, pb.pi0);
-    if (dinf > 1e-7) return "basis is not dual feasible";
-    pb.head = head;
-    double amax = 0.0;
-    for (double v : pb.Binv) amax = std::max(amax, std::fabs(v));
-    const double drop = 1e-14 * amax;
-    pb.rptr.assign(1, 0);
-    pb.rcol.clear(); pb.rval.clear();
-    for (int i = 0; i < m; ++i) {
-        for (int cc = 0; cc < m; ++cc) {
-            const double v = pb.Binv[(size_t)i * m + cc];
-            if (std::fabs(v) > drop) { pb.rcol.push_back(cc); pb.rval.push_back(v); }
-        }
-        pb.rptr.push_back((int)pb.rcol.size());
-    }
-    return nullptr;
-}
-static int make_pool_basis(twosd_ctx *c, const std::vector<int> &head, PoolBasis &pb) {
-    const char *why = compute_pool_basis(c, head, pb);
-    return why ? fail(TWOSD_E_ARG, "%s", why) : TWOSD_OK;
-}
-
-// pi0 = c_B' B^{-1} from the CSR rows (rows ascending)
-void twosd::pi0_from_rows(const twosd_ctx *c, PoolBasis &B) {
-    const HostLP &L = c->L;
-    const int m = L.m, n = L.n;
-    B.pi0.assign(m, 0.0);
-    for (int i = 0; i < m; ++i) {
-        const int j = B.head[i];
-        const double cb = j < n ? L.q[j] : 0.0;
-        if (cb == 0.0) continue;
-        for (int q = B.rptr[i]; q < B.rptr[i + 1]; ++q) B.pi0[B.rcol[q]] += cb * B.rval[q];
-    }
-}
-
-// host CSR rows and pi0 of the bases a device refresh built (dev_only), read back from the
-// pool arrays: upload_pool, prepare_elements and the host compose work on the host forms
-int twosd::ensure_host_pool(twosd_ctx *c) {
-    if (int rc = materialize_heads(c)) return rc;
-    const int P = (int)c->pool.size(), MP = c->MP, m = c->L.m;
-    int last = -1;
-    for (int p = 0; p < P; ++p)
-        if (c->pool[p].dev_only) last = p;
-    if (last < 0) return TWOSD_OK;
-    const int Pd = last + 1;
-    std::vector<int> rp((size_t)Pd * (MP + 1));
-    HIPCHK(hipStreamSynchronize(c->stream));
-    HIPCHK(hipMemcpy(rp.data(), c->d_brptr, sizeof(int) * rp.size(), hipMemcpyDeviceToHost));
-    size_t nz = 0;
-    for (int p = 0; p < Pd; ++p) nz = std::max(nz, (size_t)rp[(size_t)p * (MP + 1) + m]);
-    std::vector<int> col(std::max<size_t>(nz, 1));
-    std::vector<double> val(std::max<size_t>(nz, 1));
-    if (nz) {
-        HIPCHK(hipMemcpy(col.data(), c->d_brcol, sizeof(int) * nz, hipMemcpyDeviceToHost));
-        HIPCHK(hipMemcpy(val.data(), c->d_brval, sizeof(double) * nz, hipMemcpyDeviceToHost));
-    }
-    parallel_for(Pd, [&](int p) {
-        PoolBasis &B = c->pool[p];
-        if (!B.dev_only) return;
-        const int *r = rp.data() + (size_t)p * (MP + 1);
-        B.rptr.resize(m + 1);
-        for (int i = 0; i <= m; ++i) B.rptr[i] = r[i] - r[0];
-        B.rcol.assign(col.begin() + r[0], col.begin() + r[m]);
-        B.rval.assign(val.begin() + r[0], val.begin() + r[m]);
-        pi0_from_rows(c, B);
-        B.dev_only = false;
-    });
-    return TWOSD_OK;
-}
-
-// Upload the hypersparse-kernel form of every pool basis, pool-strided (pool[0] first, so
-// the leading MP / 64 / 64C entries are the primary basis): hb0 (MP), basic0 (64),
-// d0 (64C), B^{-1} columns as CSC (bcp absolute into the concatenated bci/bcv),
-// B^{-1} rows as CSR (brptr absolute into the concatenated brcol/brval).
-int twosd::upload_pool(twosd_ctx *c) {
-    const auto t_up0 = std::chrono::steady_clock::now();
-    if (int rc0 = ensure_host_pool(c)) return rc0;
-    const HostLP &L = c->L;
-    const int m = L.m, n = L.n, MP = c->MP, P = (int)c->pool.size();
-    std::vector<int8_t> bt(n + m);
-    HIPCHK(hipMemcpy(bt.data(), c->d_btype, n + m, hipMemcpyDeviceToHost));
-    std::vector<int> hb((size_t)P * MP, -1), bnnz(P, 0);
-    std::vector<uint64_t> basic((size_t)P * 64, 0);
-    // B^{-1} of every basis by rows (CSR) and by columns (CSC, rows ascending), both at the same
-    // per-basis offset ro[p]; offsets are known up front, so every basis fills its part of the
-    // concatenated arrays directly (default-initialised buffers, first touch in parallel)
-    std::vector<size_t> ro(P + 1, 0);
-    for (int p = 0; p < P; ++p) ro[p + 1] = ro[p] + c->pool[p].rcol.size();
-    if (ro[P] > INT32_MAX) return fail(TWOSD_E_UNSUPPORTED, "basis pool too large (> 2^31 entries)");
-    const size_t nz = std::max<size_t>(ro[P], 1);
-    std::vector<int> rp_all((size_t)P * (MP + 1)), cp_all((size_t)P * (MP + 1));
-    int *rc_all = c->stage[STG_POOL_RCOL].reserve<int>(nz), *ci_all = c->stage[STG_POOL_CROW].reserve<int>(nz);
-    double *rv_all = c->stage[STG_POOL_RVAL].reserve<double>(nz), *cv_all = c->stage[STG_POOL_CVAL].reserve<double>(nz);
-    double *d0_all = c->stage[STG_POOL_D0].reserve<double>((size_t)P * 64 * std::max(c->CH, 1));
-    if (!rc_all || !ci_all || !rv_all || !cv_all || !d0_all) return fail(TWOSD_E_DEVICE, "pool upload: pinned staging allocation failed");
-    parallel_for(P, [&](int p) {
-        const PoolBasis &B = c->pool[p];
-        std::vector<char> isb(n + m, 0);
-        for (int i = 0; i < m; ++i) {
-            hb[(size_t)p * MP + i] = B.head[i] * 4 + bt[B.head[i]];
-            basic[(size_t)p * 64 + (B.head[i] & 63)] |= 1ull << (B.head[i] >> 6);
-            isb[B.head[i]] = 1;
-        }
-        bnnz[p] = (int)B.rcol.size();
-        const int base = (int)ro[p];
-        for (int i = 0; i <= MP; ++i) rp_all[(size_t)p * (MP + 1) + i] = base + B.rptr[std::min(i, m)];
-        std::copy(B.rcol.begin(), B.rcol.end(), rc_all + base);
-        std::copy(B.rval.begin(), B.rval.end(), rv_all + base);
-        // columns: counting sort of the row CSR (rows ascending within a column)
-        std::vector<int> pos(m + 1, 0);
-        for (int cc : B.rcol) ++pos[cc + 1];
-        for (int cc = 0; cc < m; ++cc) pos[cc + 1] += pos[cc];
-        for (int cc = 0; cc <= MP; ++cc) cp_all[(size_t)p * (MP + 1) + cc] = base + pos[std::min(cc, m)];
-        for (int i = 0; i < m; ++i)
-            for (int q = B.rptr[i]; q < B.rptr[i + 1]; ++q) {
-                const int at = base + pos[B.rcol[q]]++;
-                ci_all[at] = i;
-                cv_all[at] = B.rval[q];
-            }
-        if (c->CH <= 0) return;
-        double *d0 = d0_all + (size_t)p * 64 * c->CH;
-        for (int j = 0; j < 64 * c->CH; ++j) {
-            if (j >= n + m || isb[j]) { d0[j] = 0.0; continue; }
-            double sum = 0.0;
-            if (j >= n) sum = B.pi0[j - n];
-            else
-                for (int q = L.colptr[j]; q < L.colptr[j + 1]; ++q) sum += B.pi0[L.rowidx[q]] * L.val[q];
-            d0[j] = (j < n ? L.q[j] : 0.0) - sum;
-        }
-    });
-    const auto tc = std::chrono::steady_clock::now();
-    int rc;
-    if ((rc = c->d_hb0.upload_reserve(hb)) || (rc = c->d_basic0.upload_reserve(basic)) || (rc = c->d_bnnz.upload_reserve(bnnz))) return rc;
-    if (c->CH > 0 &&
-        ((rc = c->d_bcp.upload_reserve(cp_all)) || (rc = c->d_bci.upload_reserve(ci_all, ro[P])) ||
-         (rc = c->d_bcv.upload_reserve(cv_all, ro[P])) || (rc = c->d_brptr.upload_reserve(rp_all)) ||
-         (rc = c->d_brcol.upload_reserve(rc_all, ro[P])) || (rc = c->d_brval.upload_reserve(rv_all, ro[P])) ||
-         (rc = c->d_d0.upload_reserve(d0_all, (size_t)P * 64 * c->CH))))
-        return rc;
-    if (getenv("TWOSD_DEBUG")) {
-        const auto td = std::chrono::steady_clock::now();
-        auto ms = [](auto a, auto b) { return std::chrono::duration<double, std::milli>(b - a).count(); };
-        fprintf(stderr, "upload_pool P=%d: build %.1f ms, upload %.1f ms (%.1f MB, %zu nonzeros)\n", P, ms(t_up0, tc), ms(tc, td),
-                (ro[P] * 24.0 + (size_t)P * 64 * std::max(c->CH, 0) * 8.0) / 1e6, ro[P]);
-    }
-    c->prep_valid = false;
-    c->k_valid = false;
-    reset_candidates(c);   // candidate lists refer to pool indices: rebuild after a change
-    return TWOSD_OK;
-}
-
-static int install_basis(twosd_ctx *c, const std::vector<int> &head) {
-    PoolBasis pb;
-    int rc = make_pool_basis(c, head, pb);
-    if (rc) return rc;
-    c->head0 = head;
-    c->pool.clear();
-    c->sel_lo.clear();
-    c->sel_hi.clear();
-    c->sel_box = BoxCache{};
-    c->pool.push_back(std::move(pb));
-    if ((rc = upload_pool(c))) return rc;
-    c->has_basis = true;
-    return TWOSD_OK;
-}
-
-static bool same_basis(const std::vector<int> &a, const std::vector<int> &b) {
-    std::vector<int> sa(a), sb(b);
-    std::sort(sa.begin(), sa.end());
-    std::sort(sb.begin(), sb.end());
-    return sa == sb;
-}
-
-// append a basis to the pool; returns 1 if added, 0 if already present, < 0 on error
-static int pool_add(twosd_ctx *c, const std::vector<int> &head, bool upload_now) {
-    if (int rc = materialize_heads(c)) return rc;
-    for (const PoolBasis &B : c->pool)
-        if (same_basis(B.head, head)) return 0;
-    PoolBasis pb;
-    int rc = make_pool_basis(c, head, pb);
-    if (rc) return rc;
-    std::vector<double>().swap(pb.Binv);
-    c->pool.push_back(std::move(pb));
-    if (upload_now && (rc = upload_pool(c))) return rc;
-    return 1;
-}
-
-extern "C" int twosd_compute_basis(twosd_ctx *c, const double *x, const double *values) {
-    if (!c || !c->has_template) return fail(TWOSD_E_STATE, "compute_basis: no template");
-    HIPCHK(hipSetDevice(c->device));
-    std::vector<double> dv(c->k, 0.0);
-    if (values)
-        for (int e = 0; e < c->k; ++e) dv[e] = values[e] - template_value(c, e);
-    std::vector<double> b;
-    rhs_at(c, x, values ? dv.data() : nullptr, b);
-    std::vector<int> head;
-    double obj = 0;
-    int iters = 0;
-    std::string err;
-    const int st = setup_solve(c->L, b, head, obj, iters, err);
-    if (st != TWOSD_LP_OPTIMAL) return fail(TWOSD_E_LP, "compute_basis: %s (status %d)", err.c_str(), st);
-    return install_basis(c, head);
-}
-
-extern "C" int twosd_set_basis(twosd_ctx *c, const int *head) {
-    if (!c || !c->has_template || !head) return fail(TWOSD_E_STATE, "set_basis: no template / NULL head");
-    HIPCHK(hipSetDevice(c->device));
-    return install_basis(c, std::vector<int>(head, head + c->L.m));
-}
-
-extern "C" int twosd_get_basis(twosd_ctx *c, int *head) {
-    if (!c || !c->has_basis || !head) return fail(TWOSD_E_STATE, "get_basis: no basis");
-    std::copy(c->head0.begin(), c->head0.end(), head);
-    return TWOSD_OK;
-}
-
-extern "C" int twosd_pool_add_basis(twosd_ctx *c, const int *head, int *added) {
-    if (!c || !c->has_basis || !head) return fail(TWOSD_E_STATE, "pool_add_basis: no primary basis / NULL head");
-    HIPCHK(hipSetDevice(c->device));
-    const int rc = pool_add(c, std::vector<int>(head, head + c->L.m), true);
-    if (rc < 0) return rc;
-    if (added) *added = rc;
-    return TWOSD_OK;
-}
-
-extern "C" int twosd_pool_size(twosd_ctx *c, int *size) {
-    if (!c || !size) return fail(TWOSD_E_ARG, "pool_size: NULL argument");
-    *size = (int)c->pool.size();
-    return TWOSD_OK;
-}
-
-extern "C" int twosd_pool_get(twosd_ctx *c, int p, int *head) {
-    if (c && !c->has_basis) return fail(TWOSD_E_STATE, "pool_get: no basis");
-    if (!c || !head || p < 0 || p >= (int)c->pool.size()) return fail(TWOSD_E_ARG, "pool_get: basis %d of %zu", p, c ? c->pool.size() : 0);
-    const std::vector<int> *h = nullptr;
-    if (int rc = head_of(c, p, &h)) return rc;
-    std::copy(h->begin(), h->end(), head);
-    return TWOSD_OK;
-}
-
-static int64_t pivots_of_last_lp(twosd_ctx *c, int N) {
-    std::vector<int> its(N);
-    if (hipMemcpy(its.data(), c->d_iters, sizeof(int) * N, hipMemcpyDeviceToHost) != hipSuccess) return -1;
-    int64_t sum = 0;
-    for (int v : its) sum += v;
-    return sum;
-}
-
-// Grow the pool from training scenarios [first, first + count) of epigraph epi at x.  The
-// first half harvests: solved from the current pool, its optimal bases are added in order
-// of decreasing frequency (ties: first occurrence) up to max_pool bases.  The second half
-// validates: the grown pool is kept only if it solves those scenarios in fewer pivots.
-extern "C" int twosd_pool_build(twosd_ctx *c, int epi, const double *x, int first, int count, int max_pool,
-                                int *pool_size) {
-    if (!c || !c->has_basis) return fail(TWOSD_E_STATE, "pool_build: no primary basis");
-    if (epi < 0 || epi >= (int)c->epis.size()) return fail(TWOSD_E_ARG, "pool_build: epigraph %d does not exist", epi);
-    const EpiDevice &E = c->epis[epi];
-    if (first < 0 || count < 0 || first + count > E.count || max_pool < 1 || (c->n1 > 0 && !x))
-        return fail(TWOSD_E_ARG, "pool_build: bad arguments");
-    if (pool_select_lds_bytes(c->k) + 17 * 1024 > 160 * 1024)   // + the selection kernels' static LDS
-        return fail(TWOSD_E_UNSUPPORTED, "pool_build: k = %d random elements too many for pool selection", c->k);
-    HIPCHK(hipSetDevice(c->device));
-    const int m = c->L.m;
-    const int nh = count / 2, nv = count - nh;
-    if (count > 0 && c->k > 0) {   // training box of the deltas (selection row pruning)
-        if (int rc = training_box(c, E, epi, first, count, c->sel_lo, c->sel_hi, nullptr)) return rc;
-        c->sel_box = BoxCache{};   // the refresh's cached box no longer applies
-        c->prep_valid = false;
-    }
-    if (nh > 0 && (int)c->pool.size() < max_pool) {
-        const double *dh = E.d_dv + (size_t)first * c->k, *dval = dh + (size_t)nh * c->k;
-        int rc;
-        if ((rc = run_lp(c, x, dval, nv))) return rc;
-        const int64_t piv0 = pivots_of_last_lp(c, nv);
-        LpRun harvest;
-        harvest.want_head = true;
-        if ((rc = run_lp(c, x, dh, nh, harvest))) return rc;
-        std::vector<int> heads((size_t)nh * m), st(nh);
-        HIPCHK(hipMemcpy(heads.data(), c->d_head_out, sizeof(int) * heads.size(), hipMemcpyDeviceToHost));
-        HIPCHK(hipMemcpy(st.data(), c->d_status, sizeof(int) * nh, hipMemcpyDeviceToHost));
-        std::map<std::vector<int>, std::pair<int, int>> freq;   // sorted head -> (count, first scenario)
-        if ((rc = materialize_heads(c))) return rc;
-        for (const PoolBasis &B : c->pool) {
-            std::vector<int> key(B.head);
-            std::sort(key.begin(), key.end());
-            freq[key] = {0, -1};                                 // already in the pool
-        }
-        for (int s = 0; s < nh; ++s) {
-            if (st[s] != TWOSD_LP_OPTIMAL) continue;
-            std::vector<int> key(heads.begin() + (size_t)s * m, heads.begin() + (size_t)(s + 1) * m);
-            std::sort(key.begin(), key.end());
-            auto it = freq.find(key);
-            if (it == freq.end()) freq.emplace(std::move(key), std::make_pair(1, s));
-            else if (it->second.second >= 0) ++it->second.first;
-        }
-        std::vector<std::pair<int, int>> order;   // (-count, first scenario)
-        for (auto &kv : freq)
-            if (kv.second.second >= 0) order.push_back({-kv.second.first, kv.second.second});
-        std::sort(order.begin(), order.end());
-        const size_t old_size = c->pool.size();
-        // candidates are distinct and new; their inverses are computed in parallel, and a
-        // candidate that fails validation (numerically singular / dual infeasible) is skipped
-        const size_t want = std::min(order.size(), (size_t)max_pool - old_size);
-        std::vector<PoolBasis> cand(want);
-        std::vector<int> ok(want, 0);
-        parallel_for((int)want, [&](int a) {   // threaded at any size: a dense m x m inverse each
-            const int s = order[a].second;
-            std::vector<int> head(heads.begin() + (size_t)s * m, heads.begin() + (size_t)(s + 1) * m);
-            ok[a] = compute_pool_basis(c, head, cand[a]) == nullptr;
-            std::vector<double>().swap(cand[a].Binv);   // sparse forms kept; dense m x m only for the primary
-        }, 1);
-        for (size_t a = 0; a < want; ++a)
-            if (ok[a]) c->pool.push_back(std::move(cand[a]));
-        if (c->pool.size() > old_size) {
-            if ((rc = upload_pool(c))) return rc;
-            if ((rc = run_lp(c, x, dval, nv))) return rc;
-            const int64_t piv1 = pivots_of_last_lp(c, nv);
-            std::vector<int> st2(nv);
-            HIPCHK(hipMemcpy(st2.data(), c->d_status, sizeof(int) * nv, hipMemcpyDeviceToHost));
-            const bool all_ok = std::all_of(st2.begin(), st2.end(), [](int v) { return v == TWOSD_LP_OPTIMAL; });
-            if (piv1 < 0 || piv0 < 0 || piv1 >= piv0 || !all_ok) {   // no gain: back to the old pool
-                c->pool.resize(old_size);
-                if ((rc = upload_pool(c))) return rc;
-            }
-        }
-    }
-    if (pool_size) *pool_size = (int)c->pool.size();
-    return TWOSD_OK;
 }
 
 extern "C" int twosd_epigraph_create(twosd_ctx *c, int *epi_out) {

@@ -270,7 +270,7 @@ static int eval_solve_chunk(twosd_ctx *c, const double *x, int64_t at, int n, ui
 
 static int eval_check_state(twosd_ctx *c, const char *who) {
     if (!c || !c->has_template) return fail(TWOSD_E_STATE, "%s: no template", who);
-    if (!c->has_basis) return fail(TWOSD_E_STATE, "%s: no warm-start basis", who);
+    if (!c->bp.has_basis) return fail(TWOSD_E_STATE, "%s: no warm-start basis", who);
     if (!c->has_dist) return fail(TWOSD_E_STATE, "%s: no distributions (twosd_set_distributions)", who);
     return TWOSD_OK;
 }
@@ -436,7 +436,7 @@ extern "C" int twosd_evaluate_ci_vr(twosd_ctx *c, const double *x, uint64_t seed
 extern "C" int twosd_evaluate_sampled(twosd_ctx *c, const double *x, int64_t N_total, int64_t first, int64_t count,
                                       uint64_t seed, double *s2) {
     if (!c || !c->has_template) return fail(TWOSD_E_STATE, "evaluate_sampled: no template");
-    if (!c->has_basis) return fail(TWOSD_E_STATE, "evaluate_sampled: no warm-start basis");
+    if (!c->bp.has_basis) return fail(TWOSD_E_STATE, "evaluate_sampled: no warm-start basis");
     if (!c->has_dist) return fail(TWOSD_E_STATE, "evaluate_sampled: no distributions (twosd_set_distributions)");
     if (!s2 || N_total <= 0 || first < 0 || count < 0 || (c->n1 > 0 && !x)) return fail(TWOSD_E_ARG, "evaluate_sampled: bad arguments");
     HIPCHK(hipSetDevice(c->device));

@@ -23,7 +23,7 @@ int twosd::run_lp(twosd_ctx *c, const double *x, const double *d_dv, int N, cons
     const int NL = list ? o.nlist : N;   // scenarios this launch solves
     int rc;
     if ((rc = prepare_x(c, x))) return rc;
-    if (list && c->pool.size() > 1 && (size_t)N > c->d_pool_pick.cap) return fail(TWOSD_E_STATE, "LP list mode: no recorded pool picks");
+    if (list && c->bp.bases.size() > 1 && (size_t)N > c->d_pool_pick.cap) return fail(TWOSD_E_STATE, "LP list mode: no recorded pool picks");
     const int m = c->L.m, n = c->L.n, MP = c->MP, R = c->R;
     if (N > c->out_cap) {
         size_t cap = std::max<size_t>(N, 1024);
@@ -72,11 +72,12 @@ int twosd::run_lp(twosd_ctx *c, const double *x, const double *d_dv, int N, cons
         H.retry = o.kcap > 0 ? 0 : 1;
         H.colptr = c->d_colptr; H.rowidx = c->d_rowidx; H.val = c->d_val; H.q = c->d_q; H.btype = c->d_btype;
         H.wcp = c->d_wcp; H.wcc = c->d_wcc; H.wcv = c->d_wcv;
-        H.bcp = c->d_bcp; H.bci = c->d_bci; H.bcv = c->d_bcv;
-        H.brptr = c->d_brptr; H.brcol = c->d_brcol; H.brval = c->d_brval;
-        H.kslot = c->d_kslot; H.kix = c->d_kix; H.kv = c->d_kv; H.kcoef = c->d_kcoef;
-        H.xbase = c->d_xbase; H.d0 = c->d_d0; H.hb0 = c->d_hb0;
-        H.basic0 = c->d_basic0; H.fixedmask = c->d_fixedmask; H.ubmask = c->d_ubmask;
+        const PoolArrays pa = pool_arrays(c);
+        H.bcp = pa.bcp; H.bci = pa.bci; H.bcv = pa.bcv;
+        H.brptr = pa.brptr; H.brcol = pa.brcol; H.brval = pa.brval;
+        H.kslot = pa.kslot; H.kix = pa.kix; H.kv = pa.kv; H.kcoef = c->d_kcoef;
+        H.xbase = c->d_xbase; H.d0 = pa.d0; H.hb0 = pa.hb0;
+        H.basic0 = pa.basic0; H.fixedmask = c->d_fixedmask; H.ubmask = c->d_ubmask;
         H.dv = d_dv; H.eidx = c->d_eidx; H.evals = c->d_evals; H.queue = c->d_queue;
         H.qgroups = std::max(1, std::min(16, nblocks));   // two ranges per XCD (8 / 16 / 32 / 64: 143.6 / 142.7 / 142.8 / 146.3 ms, storm 1M)
         if (const char *e = getenv("TWOSD_QGROUPS")) H.qgroups = std::max(1, std::min({kMaxQueueGroups, nblocks, atoi(e)}));   // A/B knob
@@ -126,16 +127,16 @@ int twosd::run_lp(twosd_ctx *c, const double *x, const double *d_dv, int N, cons
             HIPCHK(hipMemset(c->d_stamps, 0, sizeof(unsigned long long) * 16));
         }
         H.stamps = c->d_stamps;
-        H.npool = (int)c->pool.size();
-        H.bnnz = c->d_bnnz;
+        H.npool = (int)c->bp.bases.size();
+        H.bnnz = pa.bnnz;
         if (H.npool > 1) {
             if (!list && (rc = c->d_pool_pick.fit((size_t)N))) return rc;
             H.pool_pick = c->d_pool_pick;
         }
-        if (!list && c->d_kslot && getenv("TWOSD_DEBUG")) {
+        if (!list && pa.kslot && getenv("TWOSD_DEBUG")) {
             // w, the widest ELL slot of a start basis: the x_B warm start walks w columns
             std::vector<int> ks((size_t)H.npool * (R + 1));
-            HIPCHK(hipMemcpy(ks.data(), c->d_kslot, sizeof(int) * ks.size(), hipMemcpyDeviceToHost));
+            HIPCHK(hipMemcpy(ks.data(), pa.kslot, sizeof(int) * ks.size(), hipMemcpyDeviceToHost));
             std::vector<int> ws(H.npool);
             double mean = 0;
             for (int p = 0; p < H.npool; ++p) {
@@ -345,7 +346,7 @@ extern "C" int twosd_last_objective(twosd_ctx *c, double *weighted_sum, double *
 extern "C" int twosd_solve_batch(twosd_ctx *c, int epi, const double *x, int first, int count, double *obj,
                                  double *pi, double *y, int *status) {
     if (!c || !c->has_template) return fail(TWOSD_E_STATE, "solve_batch: no template");
-    if (!c->has_basis) return fail(TWOSD_E_STATE, "solve_batch: no warm-start basis (twosd_compute_basis / twosd_set_basis)");
+    if (!c->bp.has_basis) return fail(TWOSD_E_STATE, "solve_batch: no warm-start basis (twosd_compute_basis / twosd_set_basis)");
     if (epi < 0 || epi >= (int)c->epis.size()) return fail(TWOSD_E_ARG, "solve_batch: epigraph %d does not exist", epi);
     const EpiDevice &E = c->epis[epi];
     if (first < 0 || count < 0 || first + count > E.count) return fail(TWOSD_E_ARG, "solve_batch: range [%d,%d) outside %d scenarios", first, first + count, E.count);
@@ -363,7 +364,7 @@ extern "C" int twosd_solve_batch(twosd_ctx *c, int epi, const double *x, int fir
 extern "C" int twosd_solve_values(twosd_ctx *c, const double *x, int N, const double *values, double *obj, double *pi,
                                   double *y, int *status) {
     if (!c || !c->has_template) return fail(TWOSD_E_STATE, "solve_values: no template");
-    if (!c->has_basis) return fail(TWOSD_E_STATE, "solve_values: no warm-start basis");
+    if (!c->bp.has_basis) return fail(TWOSD_E_STATE, "solve_values: no warm-start basis");
     if (N < 0 || (N > 0 && c->k > 0 && !values) || !obj || !status || (c->n1 > 0 && !x)) return fail(TWOSD_E_ARG, "solve_values: bad arguments");
     if (N == 0) return TWOSD_OK;
     HIPCHK(hipSetDevice(c->device));
@@ -446,7 +447,7 @@ __global__ void list_status_kernel(int U, const int *__restrict__ list, const in
 extern "C" int twosd_solve_push(twosd_ctx *c, int epi, const double *x, int first, int count, double *obj, int *status,
                                 int *new_size) {
     if (!c || !c->has_template) return fail(TWOSD_E_STATE, "solve_push: no template");
-    if (!c->has_basis) return fail(TWOSD_E_STATE, "solve_push: no warm-start basis");
+    if (!c->bp.has_basis) return fail(TWOSD_E_STATE, "solve_push: no warm-start basis");
     if (epi < 0 || epi >= (int)c->epis.size()) return fail(TWOSD_E_ARG, "solve_push: epigraph %d does not exist", epi);
     const EpiDevice &E = c->epis[epi];
     if (first < 0 || count < 0 || first + count > E.count) return fail(TWOSD_E_ARG, "solve_push: range outside the epigraph");

@@ -1,7 +1,8 @@
 // pool_refresh.hip -- the warm-start pool refresh at x: twosd_pool_refresh on one GPU, and the
 // twosd_refresh_* family of the distributed refresh (one process per GPU).  Both run the same
 // front end (refresh_front), bind the same source-table type (PgTable) and build the same pool
-// bit for bit.  The pool's own upload is api.hip's, the per-x preparation pool_select.hip's.
+// bit for bit.  The pool itself (arrays, upload, validity) is basis_pool.hip's, the per-x preparation
+// pool_select.hip's.
 #include <hip/hip_runtime.h>
 #include <algorithm>
 #include <chrono>
@@ -9,7 +10,6 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
-#include <thread>
 #include <vector>
 #include "twosd_internal.h"
 #include "twosd_ctx.h"
@@ -67,15 +67,16 @@ static int pg_args(twosd_ctx *c, int nsrc, PgArgs &A) {
         (rc = c->d_pg_valid.reserve((size_t)nsrc)) || (rc = c->d_pg_head0.reserve((size_t)m)) ||
         (rc = c->d_pg_d0p.reserve((size_t)64 * c->CH)) || (rc = c->d_pg_ioff.reserve((size_t)nsrc)))
         return rc;
-    HIPCHK(hipMemcpyAsync(c->d_pg_head0, c->head0.data(), sizeof(int) * m, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(hipMemcpyAsync(c->d_pg_d0p, c->d_d0, sizeof(double) * 64 * c->CH, hipMemcpyDeviceToDevice, c->stream));
+    const PoolArrays pa = pool_arrays(c);   // the start pool
+    HIPCHK(hipMemcpyAsync(c->d_pg_head0, c->bp.head0.data(), sizeof(int) * m, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(hipMemcpyAsync(c->d_pg_d0p, pa.d0, sizeof(double) * 64 * c->CH, hipMemcpyDeviceToDevice, c->stream));
     if (c->k) HIPCHK(hipMemcpyAsync(c->d_pg_pos, c->pos_row.data(), sizeof(int) * c->k, hipMemcpyHostToDevice, c->stream));
     A = PgArgs{};
     A.m = m; A.n = L.n; A.MP = c->MP; A.CH = c->CH; A.R9 = c->R; A.k = c->k; A.kmax = c->eo_kmax;
-    A.npool_old = (int)c->pool.size();
+    A.npool_old = (int)c->bp.bases.size();
     A.colptr = c->d_colptr; A.rowidx = c->d_rowidx; A.val = c->d_val; A.q = c->d_q; A.btype = c->d_btype;
     A.pos_row = c->d_pg_pos;
-    A.bcp0 = c->d_bcp; A.bci0 = c->d_bci; A.bcv0 = c->d_bcv;
+    A.bcp0 = pa.bcp; A.bci0 = pa.bci; A.bcv0 = pa.bcv;
     A.eo_pb = c->d_eo_pb; A.eo_K = c->d_eo_K; A.eo_off = c->d_eo_off; A.eo_etap = c->d_eo_etap;
     A.eo_etaoff = c->d_eo_etaoff; A.eo_eidx = c->d_eo_eidx; A.eo_evals = c->d_eo_evals;
     A.head0 = c->d_pg_head0; A.heads = c->d_head_out; A.src_row = c->d_refresh_sel;
@@ -147,8 +148,6 @@ static int pg_compute(twosd_ctx *c, int nsrc, PgArgs &A, PgHost &H, bool dbg) {
 // assemble phase: pool = the sources of `order` (order[0] = 0, the primary) that passed, in
 // order; A describes the source table (compute output or the gathered table)
 static int pg_assemble(twosd_ctx *c, PgArgs &A, const PgHost &H, const std::vector<int> &order, bool dbg) {
-    const HostLP &L = c->L;
-    const int m = L.m, MP = c->MP;
     int rc;
     if (order.empty() || order[0] != 0 || !H.valid[0]) return 1;   // the primary failed the device checks: host path
     std::vector<int> map, off;
@@ -167,51 +166,32 @@ static int pg_assemble(twosd_ctx *c, PgArgs &A, const PgHost &H, const std::vect
     const auto t0 = Clock::now();
     if ((rc = c->d_pg_map.reserve((size_t)P)) || (rc = c->d_pg_off.reserve((size_t)4 * P))) return rc;
     // From here the live pool arrays are grown in place (a grown array does not keep its
-    // contents) and then overwritten: a failure past this point leaves c->pool describing
-    // arrays that no longer hold it.  The context then drops its basis, so every later solve
-    // fails cleanly (TWOSD_E_STATE) until twosd_compute_basis / twosd_set_basis installs one.
-    // the device-built bases read their heads lazily from pool_hb, which the failing path may
-    // have reallocated or overwritten: keep only the primary (a host basis)
-    auto broken = [c](int code) { return drop_pool(c, code); };
+    // contents) and then overwritten: a failure past this point leaves the pool's bases describing
+    // arrays that no longer hold them.  The context then drops its basis (pool_dropped), so every
+    // later solve fails cleanly (TWOSD_E_STATE) until twosd_compute_basis / twosd_set_basis
+    // installs one.
+    auto broken = [c](int code) { return pool_dropped(c, code); };
     if (const char *inj = getenv("TWOSD_INJECT_FAIL"); inj && !strcmp(inj, "refresh_fill"))   // test hook
         return broken(fail(TWOSD_E_DEVICE, "pool refresh: injected failure after the pool-array reservation"));
     HIPCHK(hipMemcpyAsync(c->d_pg_map, map.data(), sizeof(int) * P, hipMemcpyHostToDevice, c->stream));
     HIPCHK(hipMemcpyAsync(c->d_pg_off, off.data(), sizeof(int) * 4 * P, hipMemcpyHostToDevice, c->stream));
     const size_t nz = (size_t)acc[0], kz = (size_t)acc[1], ez = (size_t)acc[2] * 64;
-    if ((rc = c->d_brptr.reserve((size_t)P * (MP + 1))) || (rc = c->d_brcol.reserve(nz)) ||
-        (rc = c->d_brval.reserve(nz)) || (rc = c->d_bcp.reserve((size_t)P * (MP + 1))) ||
-        (rc = c->d_bci.reserve(nz)) || (rc = c->d_bcv.reserve(nz)) ||
-        (rc = c->d_kp.reserve((size_t)P * (m + 1))) || (rc = c->d_ke.reserve(kz)) ||
-        (rc = c->d_kraw.reserve(kz)) || (rc = c->d_kslot.reserve((size_t)P * (c->R + 1))) ||
-        (rc = c->d_kix.reserve(ez)) || (rc = c->d_kv.reserve(ez)) ||
-        (rc = c->d_hb0.reserve((size_t)P * MP)) || (rc = c->d_basic0.reserve((size_t)P * 64)) ||
-        (rc = c->d_bnnz.reserve((size_t)P)) || (rc = c->d_d0.reserve((size_t)P * 64 * c->CH)) ||
-        (rc = c->d_sel_ptr.reserve((size_t)P + 1)) || (rc = reserve_selection(c, P, (int)acc[3])))
+    if ((rc = pool_reserve(c, P, nz, kz, ez)) || (rc = c->d_sel_ptr.reserve((size_t)P + 1)) ||
+        (rc = reserve_selection(c, P, (int)acc[3])))
         return broken(rc);
     // (a grown array is reallocated: the start pool's CSC was read only by the FTRAN passes)
     PgFill F{};
     F.P = P; F.map = c->d_pg_map; F.off = c->d_pg_off; F.sel_total = (int)acc[3]; F.d0_primary = c->d_pg_d0p;
-    F.brptr = c->d_brptr; F.brcol = c->d_brcol; F.brval = c->d_brval; F.bcp = c->d_bcp; F.bci = c->d_bci; F.bcv = c->d_bcv;
-    F.kp = c->d_kp; F.ke = c->d_ke; F.kraw = c->d_kraw; F.kslot = c->d_kslot; F.kix = c->d_kix; F.kv = c->d_kv;
-    F.hb0 = c->d_hb0; F.basic0 = c->d_basic0; F.bnnz = c->d_bnnz; F.d0 = c->d_d0; F.sel_ptr = c->d_sel_ptr;
+    const PoolArrays pa = pool_arrays(c);   // as reserved just now
+    F.brptr = pa.brptr; F.brcol = pa.brcol; F.brval = pa.brval; F.bcp = pa.bcp; F.bci = pa.bci; F.bcv = pa.bcv;
+    F.kp = pa.kp; F.ke = pa.ke; F.kraw = pa.kraw; F.kslot = pa.kslot; F.kix = pa.kix; F.kv = pa.kv;
+    F.hb0 = pa.hb0; F.basic0 = pa.basic0; F.bnnz = pa.bnnz; F.d0 = pa.d0; F.sel_ptr = c->d_sel_ptr;
     F.P0 = 0;
     if (pg_launch_fill(A, F, P, c->stream) != hipSuccess) return broken(fail(TWOSD_E_DEVICE, "pool refresh: fill launch failed"));
     // the pool's heads (hb0 = 4 head + type) stay on the device; a host head is fetched on first
-    // use (head_of in api.hip)
-    c->pool_hb_valid = false;
+    // use (pool_head)
     const auto t1 = Clock::now();
-    // host pool: the primary keeps its host forms; the new bases refer to their head rows
-    std::vector<PoolBasis> keep(P);
-    keep[0] = std::move(c->pool[0]);
-    for (int p = 1; p < P; ++p) {
-        keep[p].hb_row = p;
-        keep[p].dev_only = true;
-    }
-    c->pool.swap(keep);
-    std::thread([old = std::move(keep)]() mutable { old.clear(); }).detach();
-    c->prep_valid = false;
-    c->k_valid = true;
-    reset_candidates(c);
+    pool_installed_from_device(c, P);
     if (dbg) fprintf(stderr, "pg_assemble: P=%d fill + heads %.2f ms, host pool %.2f ms\n", P, ms_between(t0, t1), ms_between(t1, Clock::now()));
     return TWOSD_OK;
 }
@@ -330,7 +310,7 @@ struct RefreshFront {
 }  // namespace
 static int refresh_front(twosd_ctx *c, const char *who, int epi, const double *x, int first, int count, bool args_ok, int kcap,
                          bool retry, int *n_opt, bool *untrained, bool dbg, RefreshFront &F) {
-    if (!c || !c->has_basis) return fail(TWOSD_E_STATE, "%s: no primary basis", who);
+    if (!c || !c->bp.has_basis) return fail(TWOSD_E_STATE, "%s: no primary basis", who);
     if (epi < 0 || epi >= (int)c->epis.size()) return fail(TWOSD_E_ARG, "%s: epigraph %d does not exist", who, epi);
     const EpiDevice &E = c->epis[epi];
     if (first < 0 || count < 1 || first + count > E.count || !args_ok || (c->n1 > 0 && !x)) return fail(TWOSD_E_ARG, "%s: bad arguments", who);
@@ -353,7 +333,7 @@ static int refresh_front(twosd_ctx *c, const char *who, int epi, const double *x
         for (int s2 = 0; s2 < count; ++s2) { h[std::min(std::max(st[s2], 0), 7)]++; itsum += itv[s2]; }
         const double piv_mean_ref = c->piv_ref_n ? (double)c->piv_ref_sum / (double)c->piv_ref_n : 0.0;
         fprintf(stderr, "%s training: kcap %d (ref %.2f), pool %zu, statuses 0:%d 1:%d 2:%d 3:%d 4:%d 5+:%d, mean iters %.2f\n", who,
-                kcap, piv_mean_ref, c->pool.size(), h[0], h[1], h[2], h[3], h[4], h[5] + h[6] + h[7], (double)itsum / count);
+                kcap, piv_mean_ref, c->bp.bases.size(), h[0], h[1], h[2], h[3], h[4], h[5] + h[6] + h[7], (double)itsum / count);
     }
     F.t_trained = Clock::now();
     // 2. distinct optimal bases in order of first occurrence, with their counts
@@ -399,7 +379,7 @@ extern "C" int twosd_pool_refresh(twosd_ctx *c, int epi, const double *x, int fi
     }
     if (R > 0 && !device_built) {
         // 3'. host path: compose on the host threads, then upload_pool + prepare_elements
-        if ((rc = ensure_host_pool(c))) return rc;   // start bases in host form
+        if ((rc = pool_host_rows(c))) return rc;   // start bases in host form
         const int kmax = c->eo_kmax;
         std::vector<int> pb(count), K(count), off(count), etap((size_t)count * kmax), etaoff((size_t)count * (kmax + 1)),
             heads((size_t)count * m);
@@ -424,24 +404,17 @@ extern "C" int twosd_pool_refresh(twosd_ctx *c, int epi, const double *x, int fi
         std::vector<char> ok(R, 0);
         parallel_for(R, [&](int a) {   // threaded at any R: a compose is milliseconds of work
             const int l = sel[a];   // eta-file row: the training scenario
-            if (K[l] < 0 || pb[l] < 0 || pb[l] >= (int)c->pool.size()) return;
+            if (K[l] < 0 || pb[l] < 0 || pb[l] >= (int)c->bp.bases.size()) return;
             PoolBasis &B = fresh[a];
             B.head.assign(heads.begin() + (size_t)l * m, heads.begin() + (size_t)(l + 1) * m);
             const int *eo = etaoff.data() + (size_t)l * (kmax + 1);
-            const PoolBasis &B0 = c->pool[pb[l]];
+            const PoolBasis &B0 = c->bp.bases[pb[l]];
             compose_binv(m, B0.rptr, B0.rcol, B0.rval, K[l], etap.data() + (size_t)l * kmax, eo, ei.data() + off[l],
                          ev.data() + off[l], B.rptr, B.rcol, B.rval);
             ok[a] = finish_composed(c, B) == nullptr;
         }, 1);
         c->last_refresh_ms[2] = ms_between(t2, Clock::now());
-        std::vector<PoolBasis> keep;
-        keep.reserve(R + 1);
-        keep.push_back(std::move(c->pool[0]));   // the primary basis stays pool[0]
-        for (int a = 0; a < R; ++a)
-            if (ok[a]) keep.push_back(std::move(fresh[a]));
-        c->pool.swap(keep);
-        // the old pool's host data is released on a helper thread (thousands of vectors)
-        std::thread([old = std::move(keep)]() mutable { old.clear(); }).detach();
+        pool_replace_host_bases(c, fresh, ok);
     }
     // R == 0 (no training scenario optimal): the current pool stays (any pool basis is a valid
     // start; dropping to the primary basis alone would cost ~90 pivots a scenario)
@@ -462,7 +435,7 @@ extern "C" int twosd_pool_refresh(twosd_ctx *c, int epi, const double *x, int fi
     c->last_refresh_ms[0] = ms_between(F.t0, F.t_trained);
     c->last_refresh_ms[3] = ms_between(tu, t3);
     c->last_refresh_ms[4] = ms_between(F.t0, t3);
-    if (pool_size) *pool_size = (int)c->pool.size();
+    if (pool_size) *pool_size = (int)c->bp.bases.size();
     return TWOSD_OK;
 }
 
@@ -735,7 +708,7 @@ extern "C" int twosd_refresh_assemble(twosd_ctx *c, int G, const void *d_packs, 
     const double ms = ms_between(t0, Clock::now());
     c->last_refresh_ms[3] = ms;
     c->last_refresh_ms[4] = c->last_refresh_ms[0] + c->last_refresh_ms[1] + c->last_refresh_ms[2] + ms;
-    if (pool_size) *pool_size = (int)c->pool.size();
+    if (pool_size) *pool_size = (int)c->bp.bases.size();
     return TWOSD_OK;
 }
 

@@ -1,7 +1,8 @@
 // pool_select.hip -- warm-start selection from the basis pool: the x-independent element rows of
 // the pool (prepare_elements), the per-x preparation (prepare_x: x_B of every basis and the
 // selection stream), the flat and two-level selection of a batch (select_pool) and the candidate
-// lists of the two-level form.  The pool itself (host forms, upload) is api.hip's.
+// lists of the two-level form.  The pool itself (host forms, device arrays, upload, validity) is
+// basis_pool.hip's; this file reads it through pool_host_rows and pool_arrays.
 #include <hip/hip_runtime.h>
 #include <algorithm>
 #include <cmath>
@@ -57,11 +58,11 @@ int twosd::training_box(twosd_ctx *c, const EpiDevice &E, int epi, int first, in
 // into kix/kv).  The kernels multiply the scenario deltas by coef_e(x) (d_kcoef) themselves.
 int twosd::prepare_elements(twosd_ctx *c) {
     const auto t_pe0 = std::chrono::steady_clock::now();
-    if (int rc0 = ensure_host_pool(c)) return rc0;
+    if (int rc0 = pool_host_rows(c)) return rc0;
     const int m = c->L.m, k = c->k, R = c->R;
     std::vector<std::vector<int>> bycol(m);   // random elements on each row
     for (int e = 0; e < k; ++e) bycol[c->pos_row[e]].push_back(e);
-    const int P = (int)c->pool.size();
+    const int P = (int)c->bp.bases.size();
     std::vector<int8_t> bt(c->L.n + m);
     HIPCHK(hipMemcpy(bt.data(), c->d_btype, bt.size(), hipMemcpyDeviceToHost));
     // pass 1: per basis and row the number of element entries; CSR / ELL / record sizes
@@ -69,7 +70,7 @@ int twosd::prepare_elements(twosd_ctx *c) {
     std::vector<size_t> kcnt(P + 1, 0), ecnt(P + 1, 0);
     std::vector<int64_t> ccnt(P + 1, 0);
     parallel_for(P, [&](int p) {
-        const PoolBasis &B = c->pool[p];
+        const PoolBasis &B = c->bp.bases[p];
         int *rc = rowcnt.data() + (size_t)p * m;
         size_t tot = 0;
         int64_t cp = 0;   // selection records: every row active; rows of fixed (E) basics twice
@@ -103,7 +104,7 @@ int twosd::prepare_elements(twosd_ctx *c) {
     if (!ke || !ki || !kr || !kv) return fail(TWOSD_E_DEVICE, "pool elements: pinned staging allocation failed");
     for (int p = 0; p <= P; ++p) cap[p] = (int)ccnt[p];
     parallel_for(P, [&](int p) {
-        const PoolBasis &B = c->pool[p];
+        const PoolBasis &B = c->bp.bases[p];
         const int *rc = rowcnt.data() + (size_t)p * m;
         std::vector<std::pair<int, double>> row;
         size_t at = kcnt[p];
@@ -139,18 +140,19 @@ int twosd::prepare_elements(twosd_ctx *c) {
     });
     const auto t_pe1 = std::chrono::steady_clock::now();
     int rc;
-    if (c->CH > 0 && ((rc = c->d_kslot.upload_reserve(ks)) || (rc = c->d_kix.upload_reserve(ki, ecnt[P])) ||
-                      (rc = c->d_kv.upload_reserve(kv, ecnt[P]))))
+    PoolDev &d = c->bp.d;
+    if (c->CH > 0 && ((rc = d.kslot.upload_reserve(ks)) || (rc = d.kix.upload_reserve(ki, ecnt[P])) ||
+                      (rc = d.kv.upload_reserve(kv, ecnt[P]))))
         return rc;
     const auto t_pe2 = std::chrono::steady_clock::now();
     if (c->CH > 0 && P > 1) {
         // device selection-stream inputs: CSR rows of every basis, and a static record capacity
         // per basis (every row active: m row starts + all its entries)
-        if ((rc = c->d_kp.upload_reserve(kp)) || (rc = c->d_ke.upload_reserve(ke, kz)) || (rc = c->d_kraw.upload_reserve(kr, kz)) ||
+        if ((rc = d.kp.upload_reserve(kp)) || (rc = d.ke.upload_reserve(ke, kz)) || (rc = d.kraw.upload_reserve(kr, kz)) ||
             (rc = c->d_sel_ptr.upload_reserve(cap)) || (rc = reserve_selection(c, P, cap[P])))
             return rc;
     }
-    c->k_valid = true;
+    pool_elements_ready(c);
     if (getenv("TWOSD_DEBUG")) {
         auto ms = [](auto a, auto b) { return std::chrono::duration<double, std::milli>(b - a).count(); };
         fprintf(stderr, "prepare_elements P=%d: build %.1f ms, upload ell %.1f ms (%zu entries), selection inputs %.1f ms\n",
@@ -332,10 +334,10 @@ int twosd::prepare_x(twosd_ctx *c, const double *x) {
         return TWOSD_OK;
     int rc;
     const auto t_start = std::chrono::steady_clock::now();
-    if (!c->k_valid && (rc = prepare_elements(c))) return rc;
+    if (!c->bp.k_valid && (rc = prepare_elements(c))) return rc;
     std::vector<double> b;
     rhs_at(c, x, nullptr, b);
-    const int P = (int)c->pool.size();
+    const int P = (int)c->bp.bases.size();
     std::vector<double> coef(std::max(k, 1), 1.0);
     for (int e = 0; e < k; ++e) coef[e] = c->pos_col[e] < 0 ? 1.0 : -x[c->pos_col[e]];
     if ((rc = c->d_xbase.fit((size_t)P * MP))) return rc;
@@ -356,8 +358,9 @@ int twosd::prepare_x(twosd_ctx *c, const double *x) {
             (rc = c->d_kcoef.fit(coef.size())) || (rc = c->d_kcoef.copy_from(coef.data(), coef.size())))
             return rc;
         const size_t tot = (size_t)P * MP;
-        hipLaunchKernelGGL(pool_xbase_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, c->stream, P, MP, c->d_brptr,
-                           c->d_brcol, c->d_brval, c->d_xaux, c->d_xbase);
+        const PoolArrays pa = pool_arrays(c);
+        hipLaunchKernelGGL(pool_xbase_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, c->stream, P, MP, pa.brptr,
+                           pa.brcol, pa.brval, c->d_xaux, c->d_xbase);
         HIPCHK(hipGetLastError());
         if (sel) {
             if (MP > kSelStreamRows) return fail(TWOSD_E_UNSUPPORTED, "pool selection: m = %d rows > %d", m, kSelStreamRows);
@@ -373,7 +376,7 @@ int twosd::prepare_x(twosd_ctx *c, const double *x) {
             if (const char *e = getenv("TWOSD_SEL_CW")) c->sel_cw = (float)atof(e);   // selection-key experiments
             static const bool sel_order = !getenv("TWOSD_SEL_ROWORDER") || atoi(getenv("TWOSD_SEL_ROWORDER")) != 0;   // A/B knob
             hipLaunchKernelGGL(pool_selstream_kernel, dim3(P), dim3(kSelStreamThreads), 0, c->stream, m, MP, k, c->d_xbase,
-                               c->d_hb0, c->d_kp, c->d_ke, c->d_kraw, c->d_xaux, box ? 1 : 0, sel_order ? 1 : 0,
+                               pa.hb0, pa.kp, pa.ke, pa.kraw, c->d_xaux, box ? 1 : 0, sel_order ? 1 : 0,
                                c->sel_cw, c->d_sel_ptr, reinterpret_cast<int2 *>(c->d_sel_code.p), c->d_sel_end, c->d_sel_cinf);
             HIPCHK(hipGetLastError());
         }
@@ -432,7 +435,7 @@ static int set_candidates(twosd_ctx *c, int level1, int ncand, int n, const int 
         for (int s = 0; s < n; ++s) diff += pf[s] != p1[s];
         for (int v : cand) filled += v >= 0;
         fprintf(stderr, "pool candidates: P=%zu level1=%d: %d of %d training picks change, %d candidate slots filled\n",
-                c->pool.size(), level1, diff, n, filled);
+                c->bp.bases.size(), level1, diff, n, filled);
     }
     int rc;
     int *h = c->stage[STG_CAND].reserve<int>(cand.size());
@@ -451,7 +454,7 @@ static int set_candidates(twosd_ctx *c, int level1, int ncand, int n, const int 
 // Two-level (pool_l1 > 0): least key over pool[0, pool_l1), then over the candidates of that
 // pick.  npool_override > 0: flat over pool[0, npool_override) (candidate training).
 int twosd::select_pool(twosd_ctx *c, const double *d_dv, int N, int *d_pick, int npool_override) {
-    const int P = (int)c->pool.size();
+    const int P = (int)c->bp.bases.size();
     const bool two = npool_override <= 0 && c->pool_l1 > 0 && c->pool_l1 < P && c->pool_ncand > 0 && (c->d_cand || c->cand_pending);
     const int np1 = npool_override > 0 ? npool_override : two ? c->pool_l1 : P;
     int rc;
@@ -510,7 +513,7 @@ static int candidate_picks(twosd_ctx *c, const EpiDevice &E, const double *x, in
         return r;
     };
     rc = picks(level1, p1);
-    if (!rc) rc = picks((int)c->pool.size(), pf);
+    if (!rc) rc = picks((int)c->bp.bases.size(), pf);
     return rc;
 }
 
@@ -529,10 +532,10 @@ static int defer_candidates(twosd_ctx *c, int level1, int ncand, std::vector<int
 
 extern "C" int twosd_pool_candidate_picks(twosd_ctx *c, int epi, const double *x, int first, int count, int level1, int *p1,
                                           int *pf) {
-    if (!c || !c->has_basis) return fail(TWOSD_E_STATE, "pool_candidate_picks: no primary basis");
+    if (!c || !c->bp.has_basis) return fail(TWOSD_E_STATE, "pool_candidate_picks: no primary basis");
     if (epi < 0 || epi >= (int)c->epis.size()) return fail(TWOSD_E_ARG, "pool_candidate_picks: epigraph %d does not exist", epi);
     const EpiDevice &E = c->epis[epi];
-    const int P = (int)c->pool.size();
+    const int P = (int)c->bp.bases.size();
     if (first < 0 || count < 1 || first + count > E.count || level1 < 1 || level1 >= P || !p1 || !pf || (c->n1 > 0 && !x) ||
         c->CH <= 0)
         return fail(TWOSD_E_ARG, "pool_candidate_picks: bad arguments");
@@ -542,8 +545,8 @@ extern "C" int twosd_pool_candidate_picks(twosd_ctx *c, int epi, const double *x
 }
 
 extern "C" int twosd_pool_set_candidates(twosd_ctx *c, int level1, int ncand, int n, const int *p1, const int *pf) {
-    if (!c || !c->has_basis) return fail(TWOSD_E_STATE, "pool_set_candidates: no primary basis");
-    const int P = (int)c->pool.size();
+    if (!c || !c->bp.has_basis) return fail(TWOSD_E_STATE, "pool_set_candidates: no primary basis");
+    const int P = (int)c->bp.bases.size();
     if (level1 < 1 || level1 >= P || ncand < 1 || ncand > 1024 || n < 0 || (n > 0 && (!p1 || !pf)))
         return fail(TWOSD_E_ARG, "pool_set_candidates: bad arguments");
     for (int s = 0; s < n; ++s)
@@ -558,10 +561,10 @@ extern "C" int twosd_pool_set_candidates(twosd_ctx *c, int level1, int ncand, in
 // scenarios whose level-1 pick is p (ties: lower index).  level1 = 0 back to flat selection.
 extern "C" int twosd_pool_build_candidates(twosd_ctx *c, int epi, const double *x, int first, int count, int level1,
                                            int ncand) {
-    if (!c || !c->has_basis) return fail(TWOSD_E_STATE, "pool_build_candidates: no primary basis");
+    if (!c || !c->bp.has_basis) return fail(TWOSD_E_STATE, "pool_build_candidates: no primary basis");
     if (epi < 0 || epi >= (int)c->epis.size()) return fail(TWOSD_E_ARG, "pool_build_candidates: epigraph %d does not exist", epi);
     const EpiDevice &E = c->epis[epi];
-    const int P = (int)c->pool.size();
+    const int P = (int)c->bp.bases.size();
     if (first < 0 || count < 1 || first + count > E.count || level1 < 0 || ncand < 0 || ncand > 1024 || (c->n1 > 0 && !x))
         return fail(TWOSD_E_ARG, "pool_build_candidates: bad arguments");
     reset_candidates(c);
@@ -575,7 +578,7 @@ extern "C" int twosd_pool_build_candidates(twosd_ctx *c, int epi, const double *
 
 extern "C" int twosd_last_pool_picks(twosd_ctx *c, int N, int *picks) {
     if (!c || !picks || N < 0 || N > c->last.N) return fail(TWOSD_E_ARG, "last_pool_picks: bad arguments");
-    if (c->pool.size() <= 1 || !c->d_pool_pick) {
+    if (c->bp.bases.size() <= 1 || !c->d_pool_pick) {
         std::fill(picks, picks + N, 0);
         return TWOSD_OK;
     }

@@ -8,6 +8,7 @@
 #include <vector>
 #include "devbuf.h"
 #include "twosd_internal.h"
+#include "basis_pool.h"
 
 // a failed HIP call ends the enclosing function with TWOSD_E_DEVICE and the call's text
 #define HIPCHK(expr)                                                                                      \
@@ -46,18 +47,6 @@ struct EpiDevice {
     int count = 0;
     double total_weight = 0.0;    // epigraph.jl:89, accumulated in insertion order
     std::vector<double> w_host;
-};
-
-// one warm-start basis of the pool (pool[0] is the primary basis head0)
-struct PoolBasis {
-    std::vector<int> head;        // m basic columns (0-based over [y; slacks])
-    std::vector<double> Binv;     // m x m row-major
-    std::vector<double> pi0;      // c_B' B^{-1}
-    std::vector<int> rptr, rcol;  // B^{-1} rows, CSR (|v| > 1e-14 max|B^{-1}|)
-    std::vector<double> rval;
-    bool dev_only = false;        // built on the device (refresh): rptr / rcol / rval / pi0 are
-                                  // fetched from the pool arrays when the host needs them
-    int hb_row = -1;              // >= 0: head not materialised yet; row of c->pool_hb (4 head + type)
 };
 
 // stored picks of one cut (twosd_picks_keep): the argmax's vertex index of each of the n scenarios
@@ -137,7 +126,7 @@ struct TemplateState {
     twosd::LpBatchRecord last;
     double t_us[twosd::T_COUNT] = {};   // T_DEDUP and the cut's two; T_LP / T_POOL_SELECT are last.lp_us / last.sel_us
     // template
-    bool has_template = false, has_basis = false;
+    bool has_template = false;
     twosd::HostLP L;              // W CSC, q, sense (host)
     int n1 = 0, R = 0, MP = 0, C = 0, k = 0;
     std::vector<double> r, T;     // the LP's r (L.m), dense T (L.m x n1, row-major)
@@ -156,27 +145,19 @@ struct TemplateState {
     twosd::DevBuf<double> d_val, d_q;
     twosd::DevBuf<int8_t> d_btype;
     twosd::DevBuf<uint64_t> d_fixedmask, d_ubmask;
-    // basis
-    std::vector<int> head0;
-    twosd::DevBuf<int> d_hb0;
-    twosd::DevBuf<uint64_t> d_basic0;
-    twosd::DevBuf<double> d_xbase;
-    std::vector<twosd::PoolBasis> pool;   // warm-start basis pool, pool[0] = head0
+    // warm-start basis pool (basis_pool.h): host forms, pool-strided device arrays, validity
+    twosd::BasisPool bp;
+    twosd::DevBuf<double> d_xbase;       // per x: x_B of every pool basis (prepare_x)
     // pool selection data (per x, prepare_x): constant-row infeasibility, active rows, entries
     twosd::DevBuf<float> d_sel_cinf;
     twosd::DevBuf<int> d_sel_ptr, d_sel_code;   // code: (code, float bits) record pairs
     twosd::DevBuf<int> d_sel_end;            // npool: end of each basis's records (begin = d_sel_ptr, static capacity)
-    // x-independent element rows of the pool on the device (CSR, pool-strided kp: npool x (m+1)
-    // absolute offsets into ke / kraw), inputs of the device selection-stream build
-    twosd::DevBuf<int> d_kp, d_ke;
-    twosd::DevBuf<double> d_kraw;
     twosd::DevBuf<double> d_xaux;            // per x: b (m), coef (k), box lo (k), box hi (k)
     int64_t sel_cap_total = 0;           // records the static capacity layout holds
     int64_t sel_nnz = 0;
     float sel_cw = 0.0f;                 // pool selection key: sum |infeas| + sel_cw * #infeasible rows (per x)
     std::vector<double> dist_mad;        // mean absolute deviation E|V_e - E V_e| of each random element
     std::vector<double> sel_lo, sel_hi;   // training box of the deltas (empty: no row pruning)
-    twosd::DevBuf<int> d_bnnz;        // npool: nnz of each pool B^{-1} (FMA accounting)
     twosd::DevBuf<int> d_head_out, d_pool_pick;   // optional LP outputs (pool building)
     // two-level pool selection (twosd_pool_build_candidates): level 1 over pool[0, pool_l1),
     // level 2 over the candidate bases of the level-1 pick (d_cand: pool_l1 x pool_ncand)
@@ -194,20 +175,13 @@ struct TemplateState {
     twosd::DevBuf<int> d_order;       // LP visiting order grouped by pool basis
     twosd::DevBuf<char> d_sort_tmp;
     twosd::DevBuf<int2> d_qrec;       // LP launch: (scenario, start basis) per queue position
-    bool prep_valid = false;
-    bool k_valid = false;         // K rows / ELL of the pool (depend on the pool and the positions)
+    bool prep_valid = false;      // the per-x preparation (d_xbase, d_sel_*) matches the pool and prep_x
     twosd::DevBuf<double> d_kcoef;    // k: coef_e(x) = 1 (RHS element) or -x[col] (T element)
     std::vector<double> prep_x;
     // hypersparse kernel data
     int CH = 0;                   // column slots per lane of the hypersparse kernel
-    twosd::DevBuf<int> d_kslot, d_kix;
-    twosd::DevBuf<double> d_kv, d_d0;
-    twosd::DevBuf<int> d_bcp, d_bci;
-    twosd::DevBuf<double> d_bcv;
     twosd::DevBuf<int> d_wcp, d_wcc;   // W by rows (CSR) for the segmented pricing scatter
     twosd::DevBuf<double> d_wcv;
-    twosd::DevBuf<int> d_brptr, d_brcol;
-    twosd::DevBuf<double> d_brval;
     twosd::DevBuf<int> d_eidx;
     twosd::DevBuf<double> d_evals;
     size_t earena_slots = 0;      // eta arena (d_eidx, d_evals): LP slots ...
@@ -294,10 +268,6 @@ struct TemplateState {
     twosd::DevBuf<long long> d_gs_ioff;
     twosd::DevBuf<double> d_gs_ival;
     twosd::DevBuf<char> d_gs_seg;             // copy-segment list of the gather unpack
-    // pinned host staging buffers of the pool upload, kept across uploads (no page faults,
-    // no unmapping per refresh, page-locked copies)
-    twosd::PinnedBuf pool_hb;     // the heads of the last device-built pool (P x MP ints, 4 head + type)
-    bool pool_hb_valid = false;   // pool_hb holds d_hb0 of the current pool
     int last_push_reps = 0;       // representatives re-solved by the last solve_push
     double push_rep_frac = 0.0;   // representatives / scenarios of the last keyed solve_push (push mode choice)
     int last_push_full = 0;       // 1: the last solve_push recovered every dual in its main pass
@@ -338,8 +308,8 @@ struct LpRun {
 // Launch the LP kernel over N scenarios whose deltas start at d_dv (device); results in
 // c->d_obj / d_pi / d_y / d_status / d_iters [0, N) (lp_batch.hip).
 int run_lp(twosd_ctx *c, const double *x, const double *d_dv, int N, const LpRun &o = LpRun());
-// what one translation unit of the library needs of another (api.hip: the pool's host and device
-// forms; pool_select.hip; lp_batch.hip); hidden: they were file-local while api.hip held it all, and
+// what one translation unit of the library needs of another (api.hip; pool_select.hip; lp_batch.hip;
+// the pool's own are in basis_pool.h); hidden: they were file-local while api.hip held it all, and
 // the library's dynamic symbols stay what they were
 #pragma GCC visibility push(hidden)
 double template_value(const twosd_ctx *c, int e);   // at position e, in the caller's space
@@ -351,13 +321,9 @@ int select_pool(twosd_ctx *c, const double *d_dv, int N, int *d_pick, int npool_
 // statistics and objective sums of the batch into c->last, outputs to the host (each nullable);
 // d_w: the batch's scenario weights (nullable: 1.0).  TWOSD_E_LP when some LP is not optimal.
 int copy_lp_outputs(twosd_ctx *c, int N, double *obj, double *pi, double *y, int *status, const double *d_w);
-int ensure_host_pool(twosd_ctx *c);      // host CSR rows and pi0 of device-built bases
-int upload_pool(twosd_ctx *c);
 int prepare_elements(twosd_ctx *c);
 int reserve_selection(twosd_ctx *c, int P, int records);
-int drop_pool(twosd_ctx *c, int code);   // keep the primary only, refuse solves; returns code
 void reset_candidates(twosd_ctx *c);
-void pi0_from_rows(const twosd_ctx *c, PoolBasis &B);
 // box [lo, hi] of the deltas of training scenarios [first, first + count) of epigraph epi (E): the
 // selection's row pruning.  With a cache, recomputed only when the range differs from the cached one.
 int training_box(twosd_ctx *c, const EpiDevice &E, int epi, int first, int count, std::vector<double> &lo,

@@ -7,6 +7,7 @@
 #include "twosd_hip.h"
 #include "devbuf.h"
 #include "dist_tables.h"
+#include "pool_pack.h"
 
 namespace twosd {
 
@@ -225,12 +226,7 @@ hipError_t launch_sample(const SampleParams &S, hipStream_t st);
 hipError_t launch_sample_plan(const SampleParams &S, int mode, int G, hipStream_t st);
 
 // ---- host-side setup (host_basis.cpp) --------------------------------------------
-struct HostLP {
-    int m = 0, n = 0;
-    std::vector<int> colptr, rowidx;   // W CSC, 0-based
-    std::vector<double> val, q;
-    std::vector<char> sense;           // 'G','L','E'
-};
+// (HostLP itself is in pool_pack.h: the pool's packing step reads it without HIP)
 // dense inverse (row-major m x m), partial pivoting; false if singular
 bool dense_inverse(int m, const std::vector<double> &A, std::vector<double> &Ainv);
 void basis_matrix(const HostLP &L, const std::vector<int> &head, std::vector<double> &B);

@@ -282,3 +282,70 @@ def test_pool_build_single_ftran_pass_identical(monkeypatch, capfd, mode):
     np.testing.assert_array_equal(st_a, st_b)
     np.testing.assert_array_equal(o_a, o_b)
     np.testing.assert_array_equal(it_a, it_b)
+
+
+def test_pool_add_over_device_built_pool(monkeypatch, capfd):
+    """pool_add_basis straight after a device-built refresh, with no pool_get in between: the
+    duplicate check has to materialise the heads of the device-built bases itself, and the append
+    has to read their rows back and upload the whole pool from the host over the device-built
+    arrays.  The result solves like a context that reached the same pool, in the same order, by
+    set_basis + pool_add_basis on the host path alone."""
+    from sqlp_amd import smps, twosd
+    inst = I.load("lands")
+    x_ev = I.x_ev("lands")
+    x2 = x_ev * 1.07 + 0.01
+    mean = smps.mean_values(inst["sto"])
+    train = I.sample("lands", 512, seed=32)
+    vals = I.sample("lands", 256, seed=33)
+
+    def refreshed():
+        c = twosd.SDContext(inst["sp2"], inst["sto"])
+        # a primary that is optimal for no scenario at x2: the refresh does not compare its bases
+        # with the primary, and pool_add_basis could not rebuild a pool that holds one twice
+        c.compute_basis(x_ev * 2.5, mean)
+        tr = twosd.sdEpigraph(c, 1.0, 0.0)
+        twosd.add_scenarios(tr, train)
+        return c, c.pool_refresh(tr, x2, 0, 512, 32)
+
+    twin, P = refreshed()                       # the same pool, read here so that `ctx` below is not
+    heads = [twin.pool_get(p) for p in range(P)]
+    assert P >= 3 and len({frozenset(h.tolist()) for h in heads}) == P
+    # an optimal head the pool does not hold: the setup solve of another scenario at another x
+    known = {frozenset(h.tolist()) for h in heads}
+    helper = twosd.SDContext(inst["sp2"], inst["sto"])
+    fresh = None
+    for scale, s in ((1.6, 0), (2.5, 1), (4.0, 2), (1.2, 3), (1.6, 4), (2.5, 5), (4.0, 6), (1.2, 7)):   # capacity to spare: feasible
+        helper.compute_basis(x_ev * scale, train[s])
+        h = helper.get_basis()
+        if frozenset(h.tolist()) not in known:
+            fresh = h
+            break
+    assert fresh is not None
+    monkeypatch.setenv("TWOSD_DEBUG", "1")
+    capfd.readouterr()
+    ctx, P2 = refreshed()
+    assert "pg_assemble:" in capfd.readouterr().err     # built on the device
+    monkeypatch.delenv("TWOSD_DEBUG")
+    assert P2 == P
+    assert not ctx.pool_add_basis(heads[2][::-1])        # present: found among lazily materialised heads
+    assert ctx.pool_add_basis(fresh)                     # host rows read back, full host upload
+    assert ctx.pool_size() == P + 1
+    host = twosd.SDContext(inst["sp2"], inst["sto"])
+    host.set_basis(heads[0])
+    for h in heads[1:]:
+        assert host.pool_add_basis(h)
+    assert host.pool_add_basis(fresh)
+    out = []
+    for c in (ctx, host):
+        ev = twosd.sdEpigraph(c, 1.0, 0.0)
+        twosd.add_scenarios(ev, vals)
+        o, _, _, st = twosd.solve_batch(ev, x2, 0, len(vals), want_pi=False)
+        out.append((o, st))
+    (o_d, st_d), (o_h, st_h) = out
+    for p in range(P + 1):
+        np.testing.assert_array_equal(ctx.pool_get(p), host.pool_get(p))
+    print(f"statuses {np.bincount(st_d)} / {np.bincount(st_h)}")
+    print(f"pool {P + 1}: bit-equal {np.array_equal(o_d, o_h)}, max rel diff {np.max(np.abs(o_d - o_h) / (1 + np.abs(o_h))):.3e}")
+    assert (st_h == 0).all()
+    np.testing.assert_array_equal(st_d, st_h)
+    np.testing.assert_array_equal(o_d, o_h)
