@@ -313,6 +313,72 @@ int twosd_set_distributions_joint(twosd_ctx *ctx, int k, const int *kind, const 
                                   const double *block_values);
 
 /*
+ * Correlated continuous elements (SMPS BLOCKS LINTR).  Every member of a LINTR
+ * block is an affine function of a few independent latent variables, v = c + H xi:
+ *   - n >= 1 member elements e_0 .. e_{n-1}: indices into the random-position layout in the
+ *     caller's order, not necessarily contiguous or ascending; one constant c_j per member;
+ *   - q >= 1 latent variables, each DISCRETE, NORMAL(mean, variance) or UNIFORM(left, right) with
+ *     the parameters and the validation of twosd_set_distributions;
+ *   - a sparse n x q matrix H in CSR, latent indices ascending within a row, entries kept as
+ *     given (explicit zeros included).
+ * Latent words.  The latents of all LINTR blocks are numbered 0 .. Q-1 in block order, and latent
+ * l draws as if it were element k + l of an independent layout of k + Q elements: scenario words
+ * from Philox counter (g_lo, g_hi, k + l, 0), LHS permutation words from (b_lo, b_hi, k + l,
+ * 2 + (i >> 2)), and the plan's inversion of an element (Box-Muller under IID and ANTITHETIC with
+ * z negated for the odd member, the inverse normal CDF under LHS, the DISCRETE walk, the
+ * two-rounding UNIFORM).  Its values are bit for bit those of columns k .. k+Q-1 of such a
+ * layout.  Elements and block leads are below k, so no latent shares a counter with them.
+ * Member value.  v = c_j; for each CSR entry (l, h) of row j, in order: v = v + (h * xi_l), every
+ * product and every sum rounded to nearest, no fused multiply-add.  Stored delta = v -
+ * template_value(e_j).
+ * A stream stays a pure function of (seed, global index, element, plan, tables): any sharding on
+ * group boundaries reproduces it, and the library's internal chunking of the latent pass (a
+ * scratch of at most 64 MiB; TWOSD_LINTR_CHUNK = scenarios per chunk is a test hook) is invisible.
+ * INDEP elements, discrete blocks (kind 3) and LINTR blocks coexist in one layout; a context
+ * without LINTR blocks launches what it launched before them, with the same bits.
+ *
+ * set_distributions_lintr: the arguments of twosd_set_distributions_joint, where kind[e] =
+ *   TWOSD_DIST_LINTR marks a LINTR member (it owns no entries of values / probs), plus the LINTR
+ *   blocks.  lintr == NULL or lintr->nblocks == 0 is twosd_set_distributions_joint.  Block b has
+ *   members members[member_off[b] .. member_off[b + 1]) with constants[] alongside, and latents
+ *   latent_off[b] .. latent_off[b + 1]) of the global numbering; latent_kind / latent_nsupport /
+ *   latent_param0 / latent_param1 have one entry per latent and latent_values / latent_probs the
+ *   concatenated supports of the DISCRETE ones, all as twosd_set_distributions reads an element.
+ *   row_ptr (one entry per member of all blocks, plus one) / col / val are one CSR over the member
+ *   rows in members[] order; col is the latent's index within its block, in [0, q).
+ *   Reset like the other tables; twosd_set_distributions and twosd_set_distributions_joint drop
+ *   the LINTR tables.  TWOSD_E_ARG, naming the block, element or latent and leaving the previous
+ *   tables in use, for: an element of kind 4 that is in no LINTR block; a member in two blocks or
+ *   twice in one; a member whose kind is not 4; a member index outside [0, k); an empty block;
+ *   q < 1; a column outside [0, q) or columns not strictly ascending within a row; a non-finite
+ *   constant or coefficient; latent parameters twosd_set_distributions would refuse.
+ *   TWOSD_E_UNSUPPORTED for k + Q >= 2^31 or latent supports past 2^31 - 1 entries.
+ *   The selection key's spread of a member is sqrt(2 / pi) sqrt(sum_l h^2 Var xi_l): a scale (the
+ *   mean absolute deviation of a normal variable of that variance), not a bound.
+ */
+#define TWOSD_DIST_LINTR 4
+typedef struct twosd_lintr {
+    int nblocks;
+    const int *member_off;        /* nblocks + 1 */
+    const int *members;           /* M = member_off[nblocks] */
+    const double *constants;      /* M */
+    const int *latent_off;        /* nblocks + 1 */
+    const int *latent_kind;       /* Q = latent_off[nblocks] */
+    const int *latent_nsupport;   /* Q */
+    const double *latent_values;  /* sum of nsupport over the DISCRETE latents */
+    const double *latent_probs;
+    const double *latent_param0;  /* Q */
+    const double *latent_param1;  /* Q */
+    const int *row_ptr;           /* M + 1 */
+    const int *col;               /* row_ptr[M] */
+    const double *val;            /* row_ptr[M] */
+} twosd_lintr;
+int twosd_set_distributions_lintr(twosd_ctx *ctx, int k, const int *kind, const int *nsupport, const double *values,
+                                  const double *probs, const double *param0, const double *param1, int nblocks,
+                                  const int *member_off, const int *members, const int *nreal, const double *block_probs,
+                                  const double *block_values, const twosd_lintr *lintr);
+
+/*
  * Variance-reduced scenario streams (no reference counterpart: the reference's readme lists
  * "Implement SMPS sampling methods (antithetic, stratified)" as open).  A sampling plan makes
  * groups of `group` = G consecutive global scenario indices [G b, G b + G) dependent; a stream

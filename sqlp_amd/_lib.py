@@ -116,9 +116,10 @@ SIGNATURES = [
     ("twosd_reform_cuts_vr", I, [P, I, I, P, I, C.c_uint64, C.c_uint64, P, P, P, P, P]),
     ("twosd_reform_partial_vr", I, [P, I, I, P, I, C.c_uint64, C.c_uint64, D, P, P, P]),
     ("twosd_set_distributions_joint", I, [P, I, P, P, P, P, P, P, I, P, P, P, P, P]),
+    ("twosd_set_distributions_lintr", I, [P, I, P, P, P, P, P, P, I, P, P, P, P, P, P]),
 ]
 
-DIST_DISCRETE, DIST_NORMAL, DIST_UNIFORM, DIST_BLOCK = 0, 1, 2, 3
+DIST_DISCRETE, DIST_NORMAL, DIST_UNIFORM, DIST_BLOCK, DIST_LINTR = 0, 1, 2, 3, 4
 
 SAMPLING_IID, SAMPLING_ANTITHETIC, SAMPLING_LHS = 0, 1, 2
 
@@ -127,6 +128,13 @@ class SamplingPlan(C.Structure):
     """struct twosd_sampling (include/twosd_hip.h)."""
     _fields_ = [("mode", I), ("group", I)]
 
+
+
+class Lintr(C.Structure):
+    """struct twosd_lintr (include/twosd_hip.h): the arrays of the LINTR blocks."""
+    _fields_ = [("nblocks", I), ("member_off", P), ("members", P), ("constants", P), ("latent_off", P), ("latent_kind", P),
+                ("latent_nsupport", P), ("latent_values", P), ("latent_probs", P), ("latent_param0", P), ("latent_param1", P),
+                ("row_ptr", P), ("col", P), ("val", P)]
 
 
 class Moments(C.Structure):

@@ -348,6 +348,7 @@ extern "C" int twosd_set_random_positions(twosd_ctx *c, int k, const int *row, c
     pool_positions_changed(c);
     c->has_dist = false;
     c->has_blocks = false;
+    c->has_lintr = false;
     cut_invalidate_pk(c);
     c->boot = twosd::BootState();   // stored picks and the re-formation's template copies
     return TWOSD_OK;
@@ -411,11 +412,13 @@ extern "C" int twosd_add_scenarios(twosd_ctx *c, int epi, int N, const double *v
     return TWOSD_OK;
 }
 
-// twosd_set_distributions (nblocks == 0, kind 3 unknown) and twosd_set_distributions_joint: every
-// check runs before the first upload, so a refused call leaves the previous tables in use
+// twosd_set_distributions (nblocks == 0, kind 3 unknown), twosd_set_distributions_joint and
+// twosd_set_distributions_lintr (lintr with blocks: kind 4 known): every check runs before the
+// first upload, so a refused call leaves the previous tables in use
 static int set_distributions(twosd_ctx *c, int k, const int *kind, const int *nsupport, const double *values, const double *probs,
                              const double *param0, const double *param1, bool joint, int nblocks, const int *member_off,
-                             const int *members, const int *nreal, const double *block_probs, const double *block_values) {
+                             const int *members, const int *nreal, const double *block_probs, const double *block_values,
+                             const twosd_lintr *lintr = nullptr) {
     if (!c || !c->has_template) return fail(TWOSD_E_STATE, "set_distributions: no template");
     if (k != c->k) return fail(TWOSD_E_ARG, "set_distributions: %d distributions for %d random elements", k, c->k);
     if (k > 0 && (!kind || !nsupport || !param0 || !param1)) return fail(TWOSD_E_ARG, "set_distributions: NULL argument");
@@ -446,7 +449,7 @@ static int set_distributions(twosd_ctx *c, int k, const int *kind, const int *ns
         } else if (kind[e] == 2) {   // UNIFORM(left, right)
             p0[e] = param0[e];
             p1[e] = param1[e];
-        } else if (!(joint && kind[e] == TWOSD_DIST_BLOCK)) {   // a block member's values come from its block
+        } else if (!(joint && kind[e] == TWOSD_DIST_BLOCK) && !(lintr && kind[e] == TWOSD_DIST_LINTR)) {   // a member's values come from its block
             return fail(TWOSD_E_ARG, "set_distributions: element %d has unknown kind %d", e, kind[e]);
         }
         off[e + 1] = (int)val.size();
@@ -456,6 +459,15 @@ static int set_distributions(twosd_ctx *c, int k, const int *kind, const int *ns
     if (const int err = dist_tables_build(k, kind, joint ? nblocks : 0, member_off, members, nreal, block_probs, block_values, B, &where)) {
         return fail(err == DT_E_TOO_LARGE ? TWOSD_E_UNSUPPORTED : TWOSD_E_ARG, "set_distributions_joint: %s (%s %d)", dist_err_text(err),
                     err == DT_E_NO_BLOCK ? "element" : "block", where);
+    }
+    LintrTables LT;
+    if (lintr) {
+        const LintrSpec spec{lintr->nblocks, lintr->member_off, lintr->members, lintr->constants, lintr->latent_off,
+                             lintr->latent_kind, lintr->latent_nsupport, lintr->latent_values, lintr->latent_probs,
+                             lintr->latent_param0, lintr->latent_param1, lintr->row_ptr, lintr->col, lintr->val};
+        if (const int err = lintr_tables_build(k, kind, spec, LT, &where))
+            return fail(err == LT_E_TOO_LARGE ? TWOSD_E_UNSUPPORTED : TWOSD_E_ARG, "set_distributions_lintr: %s (%s %d)", lintr_err_text(err),
+                        err == LT_E_NO_BLOCK ? "element" : err >= LT_E_LATENT_KIND ? "latent" : "LINTR block", where);
     }
     int rc;
     if ((rc = c->d_dist_kind.upload(kd)) || (rc = c->d_dist_off.upload(off)) || (rc = c->d_dist_val.upload(val)) ||
@@ -469,6 +481,10 @@ static int set_distributions(twosd_ctx *c, int k, const int *kind, const int *ns
     } else if ((rc = c->d_dist_elead.upload(B.lead)) || (rc = c->d_dist_eblk.upload(B.blk)) || (rc = c->d_dist_ecol.upload(B.col)) ||
                (rc = c->d_dist_binfo.upload(B.block)) || (rc = c->d_dist_bcum.upload(B.cum)) || (rc = c->d_dist_bval.upload(B.val))) {
         c->has_dist = false;   // a failed upload leaves no usable tables
+        return rc;
+    }
+    if ((rc = upload_lintr(c, LT))) {   // without LINTR blocks: drops their tables
+        c->has_dist = false;
         return rc;
     }
     // mean absolute deviation E|V_e - E V_e| per element: the spread of the scenarios (the scale
@@ -486,6 +502,8 @@ static int set_distributions(twosd_ctx *c, int k, const int *kind, const int *ns
             mad = p1[e] * std::sqrt(2.0 / M_PI);
         } else if (kd[e] == TWOSD_DIST_BLOCK) {   // the member's marginal over the realisations
             mad = dist_member_mad(B, B.blk[e], B.col[e]);
+        } else if (kd[e] == TWOSD_DIST_LINTR) {   // the normal-scale heuristic of lintr_tables.h
+            mad = lintr_member_mad(LT, LT.row[e]);
         } else {                   // Uniform(a, b): |b - a| / 4
             mad = 0.25 * fabs(p1[e] - p0[e]);
         }
@@ -508,6 +526,16 @@ extern "C" int twosd_set_distributions_joint(twosd_ctx *c, int k, const int *kin
     if (nblocks < 0) return fail(TWOSD_E_ARG, "set_distributions_joint: nblocks < 0");
     return set_distributions(c, k, kind, nsupport, values, probs, param0, param1, true, nblocks, member_off, members, nreal,
                              block_probs, block_values);
+}
+
+extern "C" int twosd_set_distributions_lintr(twosd_ctx *c, int k, const int *kind, const int *nsupport, const double *values,
+                                             const double *probs, const double *param0, const double *param1, int nblocks,
+                                             const int *member_off, const int *members, const int *nreal,
+                                             const double *block_probs, const double *block_values, const twosd_lintr *lintr) {
+    if (nblocks < 0) return fail(TWOSD_E_ARG, "set_distributions_lintr: nblocks < 0");
+    if (lintr && lintr->nblocks < 0) return fail(TWOSD_E_ARG, "set_distributions_lintr: lintr->nblocks < 0");
+    return set_distributions(c, k, kind, nsupport, values, probs, param0, param1, true, nblocks, member_off, members, nreal,
+                             block_probs, block_values, lintr && lintr->nblocks > 0 ? lintr : nullptr);
 }
 
 // a caller's sampling plan -> (mode, G); NULL means i.i.d.
@@ -589,7 +617,7 @@ static int add_sampled(twosd_ctx *c, int epi, int N, uint64_t seed, uint64_t fir
     int rc;
     if ((rc = E.d_dv.grow((size_t)(E.count + N) * k, (size_t)E.count * k, c->stream))) return rc;
     if ((rc = E.d_w.grow((size_t)(E.count + N), (size_t)E.count, c->stream))) return rc;
-    HIPCHK(launch_sample_plan(sample_params(c, N, seed, first_index, E.d_dv + (size_t)E.count * k), mode, G, c->stream));
+    if ((rc = draw_scenarios(c, N, seed, first_index, E.d_dv + (size_t)E.count * k, mode, G))) return rc;
     HIPCHK(hipMemcpyAsync(E.d_w + E.count, w.data(), sizeof(double) * N, hipMemcpyHostToDevice, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
     E.w_host.insert(E.w_host.end(), w.begin(), w.end());

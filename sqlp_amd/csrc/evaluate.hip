@@ -263,7 +263,7 @@ static int eval_solve_chunk(twosd_ctx *c, const double *x, int64_t at, int n, ui
                             double *obj = nullptr) {
     int rc;
     if ((rc = c->d_dvtmp.grow((size_t)n * std::max(c->k, 1), 0, c->stream))) return rc;
-    HIPCHK(launch_sample_plan(sample_params(c, n, seed, (uint64_t)at, c->d_dvtmp), pl.mode, pl.G, c->stream));
+    if ((rc = draw_scenarios(c, n, seed, (uint64_t)at, c->d_dvtmp, pl.mode, pl.G))) return rc;
     if ((rc = run_lp(c, x, c->d_dvtmp, n))) return rc;
     return copy_lp_outputs(c, n, obj, nullptr, nullptr, nullptr, nullptr);
 }

@@ -216,6 +216,16 @@ struct TemplateState {
     twosd::DevBuf<int> d_dist_elead, d_dist_eblk, d_dist_ecol;
     twosd::DevBuf<twosd::DistBlock> d_dist_binfo;
     twosd::DevBuf<double> d_dist_bcum, d_dist_bval;
+    // LINTR blocks (twosd_set_distributions_lintr; lintr_tables.h, lintr.hip): the M member rows
+    // (element, constant, CSR over global latent numbers), the Q latents as an independent layout
+    // (their zero template among them), and the grow-only scratch of the latent pass
+    bool has_lintr = false;
+    int lintr_M = 0, lintr_Q = 0;
+    twosd::DevBuf<int> d_lt_elem, d_lt_rptr, d_lt_col;
+    twosd::DevBuf<double> d_lt_c, d_lt_h;
+    twosd::DevBuf<int> d_lt_kind, d_lt_off, d_lt_word;
+    twosd::DevBuf<double> d_lt_val, d_lt_prob, d_lt_p0, d_lt_p1, d_lt_zero;
+    twosd::DevBuf<double> d_lt_xi;
     // epigraphs
     std::vector<twosd::EpiDevice> epis;
     // dual vertex set
@@ -316,6 +326,10 @@ double template_value(const twosd_ctx *c, int e);   // at position e, in the cal
 void rhs_at(const twosd_ctx *c, const double *x, const double *dv, std::vector<double> &b);   // b = r - T x + deltas
 // SampleParams of n scenarios from first_index of stream `seed`, drawn from the context's distributions into out
 SampleParams sample_params(const twosd_ctx *c, int n, uint64_t seed, uint64_t first_index, double *out);
+// n scenarios from first_index of stream `seed` under the plan (mode, G) into out (n x k deltas), on
+// the context's stream: launch_sample_plan, then the LINTR blocks' latent and apply passes (lintr.hip)
+int draw_scenarios(twosd_ctx *c, int n, uint64_t seed, uint64_t first_index, double *out, int mode, int G);
+int upload_lintr(twosd_ctx *c, const LintrTables &T);   // T.M == 0 drops the LINTR tables
 // pick[s] = warm-start basis of scenarios [0, N) at the prepared x, c->d_order = the scenarios grouped by pick
 int select_pool(twosd_ctx *c, const double *d_dv, int N, int *d_pick, int npool_override);
 // statistics and objective sums of the batch into c->last, outputs to the host (each nullable);

@@ -7,6 +7,7 @@
 #include "twosd_hip.h"
 #include "devbuf.h"
 #include "dist_tables.h"
+#include "lintr_tables.h"
 #include "pool_pack.h"
 
 namespace twosd {
@@ -208,7 +209,8 @@ int hyper_max_blocks_per_cu(int R, int C, int kmax, int k);
 struct SampleParams {
     int N, k;
     unsigned long long seed, first_index;
-    const int *kind;                      // k: 0 DISCRETE, 1 NORMAL, 2 UNIFORM, 3 member of a block
+    const int *kind;                      // k: 0 DISCRETE, 1 NORMAL, 2 UNIFORM, 3 member of a block; 4 (LINTR member) is drawn
+                                          //   as UNIFORM(p0 = 0, p1 = 0), a don't-care that lintr_apply_kernel overwrites
     const int *off;                       // k + 1: DISCRETE support ranges into val / prob
     const double *val, *prob;             // DISCRETE support (ascending) and probabilities
     const double *p0, *p1;                // NORMAL mean / sd, UNIFORM left / right
@@ -224,6 +226,19 @@ hipError_t launch_sample(const SampleParams &S, hipStream_t st);
 // the stream of a sampling plan (twosd_sampling: mode, group G); S.first_index and S.N are
 // multiples of G (the caller checks).  IID launches sample_kernel itself.
 hipError_t launch_sample_plan(const SampleParams &S, int mode, int G, hipStream_t st);
+
+// ---- LINTR blocks (lintr.hip; lintr_tables.h)
+struct LintrParams {
+    int N, k, M, Q;                       // scenarios of this chunk, elements, member rows, latents
+    const int *elem;                      // M: the row's element
+    const double *c;                      // M: its constant
+    const int *rptr, *col;                // M + 1, nnz: CSR over global latent numbers
+    const double *h;                      // nnz
+    const double *tmpl;                   // k template values
+    const double *xi;                     // N x Q latent values of the chunk
+    double *out;                          // N x k deltas: the chunk's rows
+};
+hipError_t launch_lintr_apply(const LintrParams &P, hipStream_t st);
 
 // ---- host-side setup (host_basis.cpp) --------------------------------------------
 // (HostLP itself is in pool_pack.h: the pool's packing step reads it without HIP)

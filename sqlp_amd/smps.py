@@ -3,8 +3,9 @@
 Mirrors the reference's reader (names and semantics):
   read_cor                 src/smps/smps_cor.jl:160-194 (tokenizer :26-58, bounds :124-155)
   read_tim                 src/smps/smps_tim.jl:30-64
-  read_sto                 src/smps/smps_sto.jl:41-110 (INDEP); BLOCKS DISCRETE and two-stage
-                           SCENARIOS DISCRETE have no reference counterpart (data/smps/README.md)
+  read_sto                 src/smps/smps_sto.jl:41-110 (INDEP); BLOCKS DISCRETE, BLOCKS LINTR and
+                           two-stage SCENARIOS DISCRETE have no reference counterpart
+                           (data/smps/README.md)
   get_smps_stage_template  src/smps/smps_prob.jl:14-102
   rand(sto)                src/smps/smps_sto.jl:117-149 (DISCRETE / NORMAL(mean, variance) /
                            UNIFORM), here vectorised with numpy's PCG64 -- Julia's RNG
@@ -65,10 +66,26 @@ class spStoBlock:
 
 
 @dataclass
+class spStoLintr:
+    """A LINTR block: member positions[j] = constants[j] + sum_l H[j][l] xi_l over independent
+    latent variables.  latents[l] is ("DISCRETE", values, probs) / ("NORMAL", mean, variance) /
+    ("UNIFORM", left, right), an entry of spStoType.indep; rows[j] lists the entries (l, h) of row j
+    of H with l ascending, kept as the file gives them (explicit zeros included)."""
+    name: str
+    period: str
+    positions: list          # spSmpsPosition, in the order of the first BL line's member lines
+    constants: list          # n
+    latent_names: list       # q
+    latents: list            # q
+    rows: list               # n lists of (latent index, coefficient)
+
+
+@dataclass
 class spStoType:
     problem_name: str
     indep: dict = field(default_factory=dict)   # position -> (kind, a, b); insertion ordered
     blocks: list = field(default_factory=list)  # spStoBlock, file order
+    lintr: list = field(default_factory=list)   # spStoLintr, file order
 
 
 def _lines(path):
@@ -162,21 +179,110 @@ def _probability(tok, what):
     return p
 
 
-def _template_value(cor, pos):
+def _template_value(cor, pos, who="SCENARIOS"):
     """The core file's value at a random position (RHS entry or matrix coefficient)."""
     if cor is None:
-        raise ValueError(f"SCENARIOS: {tuple(pos)} inherits from ROOT, which needs the core file (read_sto(path, cor))")
+        raise ValueError(f"{who}: {tuple(pos)} takes the core file's value, which needs the core file (read_sto(path, cor))"
+                         if who != "SCENARIOS" else
+                         f"SCENARIOS: {tuple(pos)} inherits from ROOT, which needs the core file (read_sto(path, cor))")
     i = cor.row_mapping[pos.row_name]
     if pos.col_name in ("RHS", "rhs"):
         return float(cor.rhs[i])
     return float(cor.entries.get((i, cor.col_mapping[pos.col_name]), 0.0))
 
 
+def _number(tok, what):
+    try:
+        return float(tok)
+    except ValueError:
+        raise ValueError(f"{what}: {tok!r} is not a number") from None
+
+
+def _read_lintr_line(st, t, line, cor):
+    """One data line of a BLOCKS LINTR section (grammar: data/smps/README.md).  st: the section's
+    state, {"blocks": name -> spStoLintr, "cur": the open block, "rv": its open latent index or None,
+    "members_open": member lines still allowed}."""
+    if t[0] == "BL" and len(t) == 3:
+        name, period = t[1], t[2]
+        new = name not in st["blocks"]
+        if new:
+            st["blocks"][name] = spStoLintr(name, period, [], [], [], [], [])
+            st["order"].append(st["blocks"][name])
+        b = st["blocks"][name]
+        if b.period != period:
+            raise ValueError(f"LINTR block {name}: period {period!r} after {b.period!r}")
+        st.update(cur=b, rv=None, members_open=new)    # the first BL line of a block fixes its members
+        return
+    b = st["cur"]
+    if b is None:
+        raise ValueError(f"BLOCKS LINTR: line before the first BL line: {line.strip()!r}")
+    if t[0] == "RV" and len(t) >= 3 and t[2] in ("NORMAL", "UNIFORM", "DISCRETE"):
+        name, kind = t[1], t[2]
+        if not b.positions:
+            raise ValueError(f"LINTR block {b.name}: RV {name} before any member line")
+        if name in b.latent_names:
+            raise ValueError(f"LINTR block {b.name}: RV {name} defined twice")
+        if kind == "DISCRETE":
+            if len(t) != 3:
+                raise ValueError(f"LINTR block {b.name}: RV {name} DISCRETE takes no parameters: {line.strip()!r}")
+            b.latents.append(("DISCRETE", [], []))
+        else:
+            if len(t) != 5:
+                raise ValueError(f"LINTR block {b.name}: RV {name} {kind} needs two parameters: {line.strip()!r}")
+            b.latents.append((kind, _number(t[3], f"RV {name}"), _number(t[4], f"RV {name}")))
+        b.latent_names.append(name)
+        st.update(rv=len(b.latents) - 1, members_open=False)
+        return
+    if t[0] == "SP" and len(t) == 3:
+        if st["rv"] is None or b.latents[st["rv"]][0] != "DISCRETE":
+            raise ValueError(f"LINTR block {b.name}: SP line outside a DISCRETE RV: {line.strip()!r}")
+        if any(st["rv"] == l for row in b.rows for l, _ in row):
+            raise ValueError(f"LINTR block {b.name}: SP line after the coefficient lines of RV {b.latent_names[st['rv']]}")
+        b.latents[st["rv"]][1].append(_number(t[1], f"RV {b.latent_names[st['rv']]}"))
+        b.latents[st["rv"]][2].append(_probability(t[2], f"RV {b.latent_names[st['rv']]}"))
+        return
+    if len(t) not in (2, 3):
+        raise ValueError(f"BLOCKS LINTR: cannot read {line.strip()!r}")
+    pos = spSmpsPosition(t[0], t[1])
+    if st["rv"] is None:                               # a member line
+        if not st["members_open"]:
+            raise ValueError(f"LINTR block {b.name}: member line {tuple(pos)} after the block's first BL line was closed")
+        if pos in b.positions:
+            raise ValueError(f"LINTR block {b.name}: member {tuple(pos)} listed twice")
+        b.positions.append(pos)
+        b.constants.append(_number(t[2], f"member {tuple(pos)}") if len(t) == 3 else _template_value(cor, pos, "BLOCKS LINTR"))
+        b.rows.append([])
+        return
+    if pos not in b.positions:                         # a coefficient line of the open RV
+        raise ValueError(f"LINTR block {b.name}: coefficient of {tuple(pos)}, which is no member")
+    if len(t) != 3:
+        raise ValueError(f"LINTR block {b.name}: coefficient line without a value: {line.strip()!r}")
+    row = b.rows[b.positions.index(pos)]
+    if row and row[-1][0] == st["rv"]:
+        raise ValueError(f"LINTR block {b.name}: {tuple(pos)} listed twice under RV {b.latent_names[st['rv']]}")
+    row.append((st["rv"], _number(t[2], f"coefficient of {tuple(pos)}")))
+
+
+def _check_lintr(b):
+    if not b.positions:
+        raise ValueError(f"LINTR block {b.name} has no members")
+    if not b.latents:
+        raise ValueError(f"LINTR block {b.name} has no RV")
+    used = {l for row in b.rows for l, _ in row}
+    for l, (name, d) in enumerate(zip(b.latent_names, b.latents)):
+        if l not in used:
+            raise ValueError(f"LINTR block {b.name}: RV {name} has no coefficient lines")
+        if d[0] == "DISCRETE" and not d[1]:
+            raise ValueError(f"LINTR block {b.name}: DISCRETE RV {name} has no SP lines")
+
+
 def read_sto(path, cor: spCorType = None) -> spStoType:
-    """INDEP (DISCRETE / NORMAL / UNIFORM), BLOCKS DISCRETE and two-stage SCENARIOS DISCRETE.
-    Several INDEP and BLOCKS sections may follow each other in any order; SCENARIOS stands alone.
-    `cor` supplies the values a SCENARIOS scenario inherits from ROOT."""
+    """INDEP (DISCRETE / NORMAL / UNIFORM), BLOCKS DISCRETE, BLOCKS LINTR and two-stage SCENARIOS
+    DISCRETE.  Several INDEP and BLOCKS sections may follow each other in any order; SCENARIOS stands
+    alone.  `cor` supplies the values a SCENARIOS scenario inherits from ROOT and the constant of a
+    LINTR member line that gives none."""
     sto = spStoType("")
+    lintr = {"blocks": {}, "order": sto.lintr, "cur": None, "rv": None, "members_open": False}
     section, kw = "", []
     blocks = {}                 # name -> spStoBlock (BLOCKS)
     cur = None                  # (block, realisation row) the value lines go to
@@ -187,6 +293,9 @@ def read_sto(path, cor: spCorType = None) -> spStoType:
             continue
         t = line.split()
         if line[0] == ' ':
+            if section == "BLOCKS" and kw == ["LINTR"]:
+                _read_lintr_line(lintr, t, line, cor)
+                continue
             if section == "BLOCKS":
                 if t[0] == "BL" and len(t) == 4:
                     name, period, p = t[1], t[2], _probability(t[3], f"block {t[1]}")
@@ -246,18 +355,26 @@ def read_sto(path, cor: spCorType = None) -> spStoType:
             else:
                 raise ValueError(f"Unknown or unsupported section_keywords {kw}")
         else:
+            if section == "BLOCKS" and kw == ["LINTR"] and lintr["cur"] is None:
+                # a LINTR section must state a block: a bare keyword line says nothing that can be read
+                raise ValueError(f"BLOCKS keywords {kw}: the section holds no BL line")
             section = t[0]
             if section not in ("STOCH", "INDEP", "BLOCKS", "SCENARIOS", "ENDATA"):
                 raise AssertionError(f"unsupported STO section {section!r}")
             kw = t[1:]
             cur = None
+            lintr.update(cur=None, rv=None, members_open=False)
             seen.add(section)
             if section == "STOCH":
                 sto.problem_name = kw[0]
+            elif section == "BLOCKS" and kw == ["LINTR"]:
+                pass
             elif section in ("BLOCKS", "SCENARIOS") and kw != ["DISCRETE"]:
-                raise ValueError(f"unsupported {section} keywords {kw}: only DISCRETE is read")
+                raise ValueError(f"unsupported {section} keywords {kw}: only DISCRETE{' and LINTR are' if section == 'BLOCKS' else ' is'} read")
             if "SCENARIOS" in seen and ("INDEP" in seen or "BLOCKS" in seen):
                 raise ValueError("SCENARIOS cannot be combined with INDEP or BLOCKS in one file")
+    if section == "BLOCKS" and kw == ["LINTR"] and lintr["cur"] is None:      # a file that ends without ENDATA
+        raise ValueError(f"BLOCKS keywords {kw}: the section holds no BL line")
     if scen:
         # one block over the union of the positions, one realisation per scenario; a position a
         # scenario omits takes its parent's value, ROOT's being the core file's
@@ -278,6 +395,14 @@ def read_sto(path, cor: spCorType = None) -> spStoType:
         for pos in b.positions:
             if pos in sto.indep:
                 raise ValueError(f"{tuple(pos)} is in block {b.name} and in INDEP")
+            if pos in owner:
+                raise ValueError(f"{tuple(pos)} is in blocks {owner[pos]} and {b.name}")
+            owner[pos] = b.name
+    for b in sto.lintr:
+        _check_lintr(b)
+        for pos in b.positions:
+            if pos in sto.indep:
+                raise ValueError(f"{tuple(pos)} is in LINTR block {b.name} and in INDEP")
             if pos in owner:
                 raise ValueError(f"{tuple(pos)} is in blocks {owner[pos]} and {b.name}")
             owner[pos] = b.name
@@ -376,13 +501,65 @@ def load_smps(directory, name=None):
 # ---------------------------------------------------------------------- scenarios
 def sto_positions(sto: spStoType) -> list:
     """The random-element layout of a sto: the INDEP positions, then every block's members in
-    file order (on a file without blocks: the INDEP positions as before)."""
-    return list(sto.indep.keys()) + [p for b in sto.blocks for p in b.positions]
+    file order, then every LINTR block's members (on a file without blocks: the INDEP positions as
+    before; without LINTR blocks: the layout as before them)."""
+    return (list(sto.indep.keys()) + [p for b in sto.blocks for p in b.positions] +
+            [p for b in getattr(sto, "lintr", []) for p in b.positions])
 
 
 def _block_members(sto: spStoType) -> dict:
     """position -> (block index, member column)"""
     return {p: (bi, j) for bi, b in enumerate(sto.blocks) for j, p in enumerate(b.positions)}
+
+
+def _lintr_members(sto: spStoType) -> dict:
+    """position -> (LINTR block index, member row)"""
+    return {p: (bi, j) for bi, b in enumerate(getattr(sto, "lintr", [])) for j, p in enumerate(b.positions)}
+
+
+def lintr_apply(b: spStoLintr, xi: np.ndarray) -> np.ndarray:
+    """Member values (N, n) of a LINTR block at latent values xi (N, q): v = c_j, then
+    v = v + (h * xi_l) for the entries of row j in order -- elementwise numpy, so every product and
+    every sum is one fp64 rounding, as on the device."""
+    xi = np.asarray(xi, dtype=np.float64)
+    out = np.empty((xi.shape[0], len(b.positions)))
+    for j, row in enumerate(b.rows):
+        v = np.full(xi.shape[0], float(b.constants[j]))
+        for l, h in row:
+            v = v + float(h) * xi[:, l]
+        out[:, j] = v
+    return out
+
+
+def _latent_moments(d):
+    """(mean, variance) of a latent."""
+    if d[0] == "DISCRETE":
+        v, p = np.asarray(d[1], dtype=np.float64), np.asarray(d[2], dtype=np.float64)
+        mu = float(np.dot(p, v) / np.sum(p))
+        return mu, float(np.dot(p, (v - mu) ** 2) / np.sum(p))
+    if d[0] == "NORMAL":
+        return float(d[1]), float(d[2])
+    return 0.5 * (d[1] + d[2]), (d[2] - d[1]) ** 2 / 12.0
+
+
+def mvnormal_lintr(name, period, positions, mean, cov) -> spStoLintr:
+    """A multivariate normal N(mean, cov) over `positions` as a LINTR block: q = n standard-normal
+    latents, H = the lower Cholesky factor of cov (all entries on and below the diagonal), c = mean.
+    ValueError if cov is not symmetric positive definite."""
+    mean = np.asarray(mean, dtype=np.float64)
+    cov = np.asarray(cov, dtype=np.float64)
+    n = len(positions)
+    if mean.shape != (n,) or cov.shape != (n, n):
+        raise ValueError(f"mvnormal_lintr: mean {mean.shape} / cov {cov.shape} do not fit {n} positions")
+    if not np.isfinite(cov).all() or not np.isfinite(mean).all() or not np.array_equal(cov, cov.T):
+        raise ValueError("mvnormal_lintr: cov must be finite and symmetric, mean finite")
+    try:
+        Lc = np.linalg.cholesky(cov)
+    except np.linalg.LinAlgError:
+        raise ValueError("mvnormal_lintr: cov is not positive definite") from None
+    return spStoLintr(name, period, [spSmpsPosition(*p) for p in positions], [float(v) for v in mean],
+                      [f"Z{l + 1}" for l in range(n)], [("NORMAL", 0.0, 1.0) for _ in range(n)],
+                      [[(l, float(Lc[j, l])) for l in range(j + 1)] for j in range(n)])
 
 
 def scenario_positions(sp2: spStageProblem, sto: spStoType):
@@ -403,9 +580,18 @@ def sample_values(sto: spStoType, N: int, rng: np.random.Generator, positions=No
     one of its realisations."""
     positions = positions if positions is not None else sto_positions(sto)
     members = _block_members(sto) if sto.blocks else {}
-    picks = {}
+    lmembers = _lintr_members(sto)
+    picks, lvalues = {}, {}
     out = np.empty((N, len(positions)))
     for e, p in enumerate(positions):
+        if p in lmembers:                 # a LINTR block draws its latents once, at its first member in `positions`
+            bi, j = lmembers[p]
+            if bi not in lvalues:
+                b = sto.lintr[bi]
+                xi = sample_values(spStoType("", dict(enumerate(b.latents))), N, rng)
+                lvalues[bi] = lintr_apply(b, xi)
+            out[:, e] = lvalues[bi][:, j]
+            continue
         if p in members:
             bi, j = members[p]
             b = sto.blocks[bi]
@@ -429,11 +615,18 @@ def sample_values(sto: spStoType, N: int, rng: np.random.Generator, positions=No
 
 
 def mean_values(sto: spStoType, positions=None) -> np.ndarray:
-    """Mean of every element; a block member's is sum p v / sum p over the realisations."""
+    """Mean of every element; a block member's is sum p v / sum p over the realisations, a LINTR
+    member's c + sum_l h E xi_l."""
     positions = positions if positions is not None else sto_positions(sto)
     members = _block_members(sto) if sto.blocks else {}
+    lmembers = _lintr_members(sto)
     out = []
     for p in positions:
+        if p in lmembers:
+            bi, j = lmembers[p]
+            b = sto.lintr[bi]
+            out.append(float(b.constants[j] + sum(h * _latent_moments(b.latents[l])[0] for l, h in b.rows[j])))
+            continue
         if p in members:
             bi, j = members[p]
             b = sto.blocks[bi]
@@ -452,7 +645,8 @@ def mean_values(sto: spStoType, positions=None) -> np.ndarray:
 def joint_support(sto: spStoType, positions=None, max_points=1 << 20):
     """(values[R_total, k], probs[R_total]) of an all-discrete sto: the product of the INDEP
     DISCRETE supports and the blocks' realisations, columns in `positions` order, the first factor
-    (INDEP elements in file order, then the blocks) varying slowest.  A row's probability is the
+    (INDEP elements in file order, then the blocks, then the LINTR blocks whose latents must all be
+    DISCRETE) varying slowest.  A row's probability is the
     product of its factors' probabilities as the file states them (not normalised), so
     sum(probs * f(values)) / sum(probs) is an exact expectation.  ValueError for a NORMAL or
     UNIFORM element, for a position the sto does not hold, and past max_points rows."""
@@ -468,6 +662,23 @@ def joint_support(sto: spStoType, positions=None, max_points=1 << 20):
     for b in sto.blocks:
         factors.append((b.positions, np.asarray(b.values, dtype=np.float64).reshape(len(b.probs), len(b.positions)),
                         np.asarray(b.probs, dtype=np.float64)))
+    for b in getattr(sto, "lintr", []):
+        # the product of the latents' supports (file order, the first latent slowest), the members by lintr_apply
+        for name, d in zip(b.latent_names, b.latents):
+            if d[0] != "DISCRETE":
+                raise ValueError(f"joint_support: latent {name} of LINTR block {b.name} is {d[0]}, not DISCRETE")
+        R = 1
+        for d in b.latents:
+            R *= len(d[1])
+            if R > max_points:
+                raise ValueError(f"joint_support: more than max_points = {max_points} points")
+        xi, pr, inner = np.empty((R, len(b.latents))), np.ones(R), R
+        for l, d in enumerate(b.latents):
+            inner //= len(d[1])
+            pick = (np.arange(R) // inner) % len(d[1])
+            xi[:, l] = np.asarray(d[1], dtype=np.float64)[pick]
+            pr *= np.asarray(d[2], dtype=np.float64)[pick]
+        factors.append((b.positions, lintr_apply(b, xi), pr))
     known = {p for f in factors for p in f[0]}
     for p in positions:
         if p not in known:

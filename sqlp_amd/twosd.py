@@ -399,11 +399,17 @@ class SDContext:
     def set_distributions(self, sto):
         """Upload the distribution of every random element (position order): the independent ones,
         and the joint discrete blocks of sto.blocks (twosd_set_distributions_joint; every member of
-        a block must be a position of this context)."""
+        a block must be a position of this context), and the LINTR blocks of sto.lintr
+        (twosd_set_distributions_lintr: members affine in a few independent latent variables)."""
         blocks = getattr(sto, "blocks", [])
+        lintr = getattr(sto, "lintr", [])
         member = {p for b in blocks for p in b.positions}
+        lmember = {p for b in lintr for p in b.positions}
         kinds, nsup, vals, probs, p0, p1 = [], [], [], [], [], []
         for pos in self.positions:
+            if pos in lmember:
+                kinds.append(_lib.DIST_LINTR); nsup.append(0); p0.append(0.0); p1.append(0.0)
+                continue
             if pos in member:
                 kinds.append(_lib.DIST_BLOCK); nsup.append(0); p0.append(0.0); p1.append(0.0)
                 continue
@@ -417,7 +423,7 @@ class SDContext:
                 kinds.append(2); nsup.append(0); p0.append(d[1]); p1.append(d[2])
         a = [np.ascontiguousarray(kinds, dtype=np.int32), np.ascontiguousarray(nsup, dtype=np.int32),
              _f64(vals if vals else [0.0]), _f64(probs if probs else [0.0]), _f64(p0), _f64(p1)]
-        if not blocks:
+        if not blocks and not lintr:
             check(self.lib.twosd_set_distributions(self.h, self.k, *[ptr(v) for v in a]))
             return
         moff, mem, nreal, bp, bv = [0], [], [], [], []
@@ -428,8 +434,33 @@ class SDContext:
             bp += list(b.probs)
             bv += list(np.asarray(b.values, dtype=np.float64).reshape(len(b.probs), len(b.positions)).ravel())
         j = [np.ascontiguousarray(moff, dtype=np.int32), np.ascontiguousarray(mem, dtype=np.int32),
-             np.ascontiguousarray(nreal, dtype=np.int32), _f64(bp), _f64(bv)]
-        check(self.lib.twosd_set_distributions_joint(self.h, self.k, *[ptr(v) for v in a], len(blocks), *[ptr(v) for v in j]))
+             np.ascontiguousarray(nreal, dtype=np.int32), _f64(bp if bp else [0.0]), _f64(bv if bv else [0.0])]
+        if not lintr:
+            check(self.lib.twosd_set_distributions_joint(self.h, self.k, *[ptr(v) for v in a], len(blocks), *[ptr(v) for v in j]))
+            return
+        # LINTR blocks (twosd_set_distributions_lintr): members and constants, the latents as
+        # set_distributions reads an element, one CSR over the member rows
+        i32 = lambda v: np.ascontiguousarray(v if len(v) else [0], dtype=np.int32)
+        lmoff, lmem, lc, loff, lk, lns, lv, lp, l0, l1, rptr, col, val = [0], [], [], [0], [], [], [], [], [], [], [0], [], []
+        for b in lintr:
+            lmem += [self.pos_index[p] for p in b.positions]
+            lc += [float(v) for v in b.constants]
+            lmoff.append(len(lmem))
+            for d in b.latents:
+                if d[0] == "DISCRETE":
+                    lk.append(0); lns.append(len(d[1])); lv += list(d[1]); lp += list(d[2]); l0.append(0.0); l1.append(0.0)
+                else:
+                    lk.append(1 if d[0] == "NORMAL" else 2); lns.append(0); l0.append(d[1]); l1.append(d[2])
+            loff.append(len(lk))
+            for row in b.rows:
+                col += [l for l, _ in row]
+                val += [h for _, h in row]
+                rptr.append(len(col))
+        keep = [i32(lmoff), i32(lmem), _f64(lc), i32(loff), i32(lk), i32(lns), _f64(lv if lv else [0.0]), _f64(lp if lp else [0.0]),
+                _f64(l0), _f64(l1), i32(rptr), i32(col), _f64(val if val else [0.0])]
+        L = _lib.Lintr(len(lintr), *[ptr(v) for v in keep])
+        check(self.lib.twosd_set_distributions_lintr(self.h, self.k, *[ptr(v) for v in a], len(blocks), *[ptr(v) for v in j],
+                                                     C.byref(L)))
 
     def scenario_values(self, scenario) -> np.ndarray:
         """spSmpsScenario (list of position => value) -> value vector in layout order.
