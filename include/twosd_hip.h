@@ -750,6 +750,63 @@ int twosd_last_lp_ops(twosd_ctx *ctx, int64_t *row_ops, int *row_width);
  * (non-zero only in the TWOSD_STAMPS build libtwosd_hip_stamps.so).  reset != 0 clears. */
 int twosd_debug_stamps(twosd_ctx *ctx, uint64_t *out10, int reset);
 
+/* ---- feasibility rays --------------------------------------------------
+ * A ray sigma (mv = m_lp doubles, bound rows included) has the sign convention of a dual:
+ * sigma_i >= 0 on G rows, <= 0 on L rows (bound rows are L), free on E rows; sigma' W_j <= 0 for
+ * every structural column (to the ratio test's pivot tolerance); sigma' b > 0 certifies that the LP
+ * with right-hand side b = [r_w - T_w x - W s ; hi - lo] has no solution.  W is not random, so a
+ * ray found at one scenario certifies every scenario and every x with sigma' b_w(x) > 0.
+ *
+ * The ray set F of a context: at most TWOSD_FRAY_MAX rays, normalised (divided by max |sigma_i|
+ * after the entries at or below 1e-12 (1 + max) are set to zero), in insertion order.  A pushed ray
+ * whose key is present maps to the existing index (first occurrence kept); the key is the
+ * components rounded to 24 significant bits, mixed with their row.  twosd_fray_push: rays[count*mv]
+ * in order, out_index[count] (nullable), *new_size (nullable).  TWOSD_E_ARG when a ray is all zero
+ * or not finite, TWOSD_E_UNSUPPORTED when the set would pass TWOSD_FRAY_MAX; either leaves the set
+ * as it was.  The set is dropped by twosd_set_template and twosd_set_random_positions.
+ * twosd_fray_key is a pure host function (no context, no GPU call): the key and the normalised
+ * form (each nullable) of one ray, exactly what a push computes. */
+#define TWOSD_FRAY_MAX 4096
+int twosd_fray_push(twosd_ctx *ctx, int count, const double *rays, int *out_index, int *new_size);
+int twosd_fray_size(twosd_ctx *ctx, int *size);
+int twosd_fray_get(twosd_ctx *ctx, int first, int count, double *out /* count*mv */);
+int twosd_fray_clear(twosd_ctx *ctx);
+int twosd_fray_key(const double *ray, int mv, uint64_t *key, double *normalised /* mv */);
+
+/* Solve scenarios [first, first+count) of epigraph `epi` at x as twosd_solve_batch does without
+ * outputs, then recover one Farkas ray per distinct infeasible exit: the infeasible scenarios are
+ * compacted (ascending) and re-solved from their recorded start bases, 4096 at a time, by the LP
+ * kernel's ray instantiation; of every (final basis, leaving variable, sign) the first scenario's
+ * ray is kept, in scenario order, until `cap` rays.  *n_infeasible = infeasible scenarios,
+ * *n_rays = rays returned; scen[i] (cap) = the scenario of ray i as an index of the epigraph;
+ * rays (cap*mv, nullable) raw (unnormalised) sigma = +-e_r' B^{-1}; row (cap, nullable) the leaving
+ * row r (a basis position); head (cap*m_lp, nullable) the basis at the exit (column j < n_lp, or
+ * n_lp + i for the slack of row i); status (count, nullable).  push != 0 also pushes the returned
+ * rays into F on the device.  TWOSD_OK when every scenario is optimal or infeasible; TWOSD_E_LP
+ * only when one ended at the iteration limit or numerically; TWOSD_E_ARG / TWOSD_E_STATE as
+ * twosd_solve_batch.  A batch without an infeasible scenario launches what twosd_solve_batch
+ * launches. */
+int twosd_solve_rays(twosd_ctx *ctx, int epi, const double *x, int first, int count, int cap, int push,
+                     int *n_infeasible, int *n_rays, int *scen, double *rays, int *row, int *head, int *status);
+/* Of the last twosd_solve_rays: list positions the ray instantiation re-solved, and infeasible
+ * scenarios it did not have to because a ray held or found before their chunk cuts them off at x
+ * (the violation scan runs over the remaining list before every chunk after the first, and before
+ * the first when F is not empty); *scan_us: device time (events) of the scan and merge kernels of
+ * the last twosd_feas_scan, in microseconds.  Each nullable. */
+int twosd_last_ray_stats(twosd_ctx *ctx, int64_t *resolved, int64_t *filtered, double *scan_us);
+
+/* Violation scan of scenarios [first, first+count) (count >= 1) of epigraph `epi` against every ray
+ * of F at x.  The score of (ray j, scenario s) is v_js = alpha + beta' x of their feasibility row
+ *     alpha = sigma . [ r_w - W s ; hi - lo ],   beta = -T_w' sigma      (alpha + beta' x <= 0)
+ * evaluated in the arithmetic of the cut's restated score: sigma_j . (r - T x) in index order plus
+ * the random elements' terms by ascending row, every product and sum rounded on its own.
+ * ray_max[J] = max_s v_js and ray_arg[J] the lowest scenario index (of the epigraph) attaining it;
+ * alpha[J] / beta[J*n1] (each nullable) the row of (j, ray_arg[j]); cut_off[count] (nullable) whether
+ * any ray scores > 0 at the scenario, *n_cut_off (nullable) their number.  Bit-identical under any
+ * launch grid.  TWOSD_E_STATE when F is empty; TWOSD_E_UNSUPPORTED for k beyond the cut's 127. */
+int twosd_feas_scan(twosd_ctx *ctx, int epi, const double *x, int first, int count, double *ray_max, int *ray_arg,
+                    double *alpha, double *beta, int64_t *n_cut_off, unsigned char *cut_off);
+
 #ifdef __cplusplus
 }
 #endif

@@ -117,11 +117,21 @@ SIGNATURES = [
     ("twosd_reform_partial_vr", I, [P, I, I, P, I, C.c_uint64, C.c_uint64, D, P, P, P]),
     ("twosd_set_distributions_joint", I, [P, I, P, P, P, P, P, P, I, P, P, P, P, P]),
     ("twosd_set_distributions_lintr", I, [P, I, P, P, P, P, P, P, I, P, P, P, P, P, P]),
+    ("twosd_fray_push", I, [P, I, P, P, P]),
+    ("twosd_fray_size", I, [P, P]),
+    ("twosd_fray_get", I, [P, I, I, P]),
+    ("twosd_fray_clear", I, [P]),
+    ("twosd_fray_key", I, [P, I, P, P]),
+    ("twosd_solve_rays", I, [P, I, P, I, I, I, I, P, P, P, P, P, P, P]),
+    ("twosd_last_ray_stats", I, [P, P, P, P]),
+    ("twosd_feas_scan", I, [P, I, P, I, I, P, P, P, P, P, P]),
 ]
 
 DIST_DISCRETE, DIST_NORMAL, DIST_UNIFORM, DIST_BLOCK, DIST_LINTR = 0, 1, 2, 3, 4
 
 SAMPLING_IID, SAMPLING_ANTITHETIC, SAMPLING_LHS = 0, 1, 2
+
+FRAY_MAX = 4096   # TWOSD_FRAY_MAX
 
 
 class SamplingPlan(C.Structure):

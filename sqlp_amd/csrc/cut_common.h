@@ -166,6 +166,16 @@ int cut_fold_dmax(twosd_ctx *c, int epi, int N, int k);
 // the operands of a cut at x: vertex bases and bands, the pass, the argmax's vertex list and its
 // chunk sources
 void cut_operand_stage(twosd_ctx *c, int epi, const CutShape &sh, const CutPlan &pl, bool twins);
+// The same operands for feasibility rays (feas.hip): a ray is structurally a dual vertex.  For the J
+// rays F (J x m, device) at x: their element gathers PK / PKT / PKO (J x k4, k4 x J, J x k4) by
+// cut_pk_kernel and their bases sigma_j . (r - T x) by cut_vbase_kernel, with coef_e(x) and r - T x
+// uploaded into the cut's own vectors.  scratch: k + 1 + BAND_COUNT words (the band the base kernel
+// folds is not used).  *coef / *eord / *k4: the cut's coef_e(x) table, element order and row length.
+int cut_ray_operands(twosd_ctx *c, const double *x, int J, const double *d_F, double *PK, double *PKT, double *PKO, double *base,
+                     unsigned long long *scratch, const double **coef, const int **eord, int *k4);
+// cut_kernel.hip
+void host_bvec_coef(const twosd_ctx *c, const double *x, int k4, std::vector<double> &bvec, std::vector<double> &coef);
+int cut_size_vectors(CutWs *w, int m);
 // cut_argmax.hip
 int cut_argmax_bpc(int k, const CutKnobs &kn);   // CutShape::bpc: the knob, else the pass's resident blocks per CU
 void cut_argmax_stage(const CutPlan &pl, const CutParams &P, hipStream_t s);   // the passes and the histogram reduce

@@ -168,7 +168,7 @@ static int plan_cut(twosd_ctx *c, int N, const CutKnobs &kn, CutRun &run) {
 // subprob.jl:147): T x accumulated from zero column by column, as SparseArrays' CSC mat-vec
 // does (tx[i] += T[i][j] * x[j] for j ascending, no contraction), then subtracted from r
 // (oracle_build_cut, twosd_ref._seq_base); coef
-static void host_bvec_coef(const twosd_ctx *c, const double *x, int k4, std::vector<double> &bvec, std::vector<double> &coef) {
+void host_bvec_coef(const twosd_ctx *c, const double *x, int k4, std::vector<double> &bvec, std::vector<double> &coef) {
     const int m = c->L.m, n1 = c->n1, k = c->k;
     bvec.assign(m, 0.0);
     coef.assign(k4, 0.0);
@@ -181,14 +181,21 @@ static void host_bvec_coef(const twosd_ctx *c, const double *x, int k4, std::vec
     for (int e = 0; e < k; ++e) coef[e] = c->pos_col[e] < 0 ? 1.0 : -x[c->pos_col[e]];
 }
 
-// every buffer of a cut but the epigraph's dmax (cut_fold_dmax), sized from its shape and plan
-static int size_workspace(CutWs *w, const CutShape &sh, const CutPlan &pl, int m) {
-    const size_t N = sh.N, nv = sh.nv, k = sh.k, tp = (size_t)pl.ntail * pl.S, vcap32 = pl.vcap32;
+// the per-x vectors of the cut's operands: coef_e(x), bvec = r - T x, and g
+int cut_size_vectors(CutWs *w, int m) {
     int rc;
     if (!w->coef || !w->bvec || !w->g || w->vec_m != m) {
         if ((rc = w->coef.alloc(256)) || (rc = w->bvec.alloc(m)) || (rc = w->g.alloc(m))) return rc;
         w->vec_m = m;
     }
+    return TWOSD_OK;
+}
+
+// every buffer of a cut but the epigraph's dmax (cut_fold_dmax), sized from its shape and plan
+static int size_workspace(CutWs *w, const CutShape &sh, const CutPlan &pl, int m) {
+    const size_t N = sh.N, nv = sh.nv, k = sh.k, tp = (size_t)pl.ntail * pl.S, vcap32 = pl.vcap32;
+    int rc;
+    if ((rc = cut_size_vectors(w, m))) return rc;
     if ((rc = w->base.fit(nv))) return rc;
     if ((rc = w->arg.fit(N)) || (rc = w->val.fit(N)) || (rc = w->flag.fit(N))) return rc;
     if ((rc = w->tp_m.fit(tp)) || (rc = w->tp_i.fit(tp)) || (rc = w->tp_f.fit(tp))) return rc;

@@ -393,6 +393,29 @@ int update_pk(twosd_ctx *c) {
     return TWOSD_OK;
 }
 
+int cut_ray_operands(twosd_ctx *c, const double *x, int J, const double *d_F, double *PK, double *PKT, double *PKO, double *base,
+                     unsigned long long *scratch, const double **coef, const int **eord, int *k4_out) {
+    CutWs *w = cws(c);
+    const int k = c->k, m = c->L.m;
+    int rc;
+    if ((rc = update_pk(c))) return rc;   // the element rows and their order (and V's own gathers)
+    const int k4 = w->pk_k4;
+    if ((rc = cut_size_vectors(w, m))) return rc;
+    host_bvec_coef(c, x, k4, w->h_bvec, w->h_coef);
+    HIPCHK(hipMemcpyAsync(w->coef, w->h_coef.data(), sizeof(double) * k4, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(hipMemcpyAsync(w->bvec, w->h_bvec.data(), sizeof(double) * m, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(hipMemsetAsync(scratch, 0, sizeof(unsigned long long) * (k + 1 + BAND_COUNT), c->stream));
+    hipLaunchKernelGGL(cut_pk_kernel, dim3((J * k4 + 255) / 256), dim3(256), 0, c->stream, 0, J, m, k, k4, J, w->rows, w->eord, d_F, PK,
+                       PKT, PKO);
+    hipLaunchKernelGGL(cut_vbase_kernel, dim3(std::max(1, std::min((J + 3) / 4, 4096))), dim3(256), 0, c->stream, J, m, k, k4, d_F,
+                       w->bvec, PK, w->coef, scratch, base, scratch + k + 1, 0.0, 0.0);
+    HIPCHK(hipGetLastError());
+    *coef = w->coef;
+    *eord = w->eord;
+    *k4_out = k4;
+    return TWOSD_OK;
+}
+
 int cut_fold_dmax(twosd_ctx *c, int epi, int N, int k) {
     CutWs *w = cws(c);
     int rc;

@@ -22,8 +22,9 @@ int twosd::run_lp(twosd_ctx *c, const double *x, const double *d_dv, int N, cons
     const bool list = o.d_list != nullptr;
     const int NL = list ? o.nlist : N;   // scenarios this launch solves
     int rc;
+    if (o.want_ray && !list) return fail(TWOSD_E_ARG, "LP rays: list mode only");
     if ((rc = prepare_x(c, x))) return rc;
-    if (list && c->bp.bases.size() > 1 && (size_t)N > c->d_pool_pick.cap) return fail(TWOSD_E_STATE, "LP list mode: no recorded pool picks");
+    if (list &&c->bp.bases.size() > 1 && (size_t)N > c->d_pool_pick.cap) return fail(TWOSD_E_STATE, "LP list mode: no recorded pool picks");
     const int m = c->L.m, n = c->L.n, MP = c->MP, R = c->R;
     if (N > c->out_cap) {
         size_t cap = std::max<size_t>(N, 1024);
@@ -116,6 +117,13 @@ int twosd::run_lp(twosd_ctx *c, const double *x, const double *d_dv, int N, cons
             const size_t need = list ? (size_t)NL : (size_t)N;
             if ((rc = c->d_head_out.fit(need * m))) return rc;
             H.head_out = c->d_head_out;
+        }
+        if (o.want_ray) {   // rows: list positions; a position that does not end infeasible keeps row -1 and key 0
+            FrayState &Fs = c->fray;
+            if ((rc = Fs.ray.fit((size_t)NL * m)) || (rc = Fs.ray_row.fit((size_t)NL)) || (rc = Fs.ray_key.fit((size_t)NL))) return rc;
+            HIPCHK(hipMemsetAsync(Fs.ray_row, 0xff, sizeof(int) * NL, c->stream));
+            HIPCHK(hipMemsetAsync(Fs.ray_key, 0, sizeof(unsigned long long) * NL, c->stream));
+            H.ray = Fs.ray; H.ray_row = Fs.ray_row; H.ray_key = Fs.ray_key;
         }
         H.pi_by_pos = list ? 1 : 0;
         H.status = c->d_status; H.iters = c->d_iters; H.ops = c->d_ops; H.etan = c->d_etan;

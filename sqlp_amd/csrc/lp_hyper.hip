@@ -252,7 +252,11 @@ constexpr int XU = TWOSD_XB_U;
 // FULL = false: the main solve of solve_push / solve_batch without pi, y, heads, basis keys or
 // eta files -- the vertex recovery and the refresh outputs are compiled out (a smaller kernel:
 // fewer registers and instruction-cache lines).
-template <int R, int C, bool FULL>
+// RAY = true (with FULL; twosd_solve_rays' list-mode re-solve of the infeasible scenarios): the
+// infeasible exit keeps its leaving row and the sign of its infeasibility, and the epilogue
+// recovers the Farkas ray sigma = sign(delta) e_r' B^{-1} with the code of the vertex recovery.
+// Everything it adds sits under `if constexpr (RAY)`: the other two instantiations are unchanged.
+template <int R, int C, bool FULL, bool RAY = false>
 __global__ void __launch_bounds__(256, TWOSD_HYPER_WPE(R)) lp_hyper_kernel(HyperParams P) {
     extern __shared__ double lds_raw[];
     using Mask = typename std::conditional<(C > 32), uint64_t, uint32_t>::type;
@@ -372,6 +376,8 @@ __global__ void __launch_bounds__(256, TWOSD_HYPER_WPE(R)) lp_hyper_kernel(Hyper
         int K = 0, it = 0, status = TWOSD_LP_OPTIMAL;
         int eoff = 0;
         unsigned nops = 0;   // entries processed by this solve (< 2^32: at most kmax pivots of <= a few 10^4 each)
+        int ray_r = 0;         // RAY: leaving row of the infeasible exit, and whether it sat above its bound
+        bool ray_up = false;
         // a pool start that ends non-optimal (numerics, iteration cap) is retried from the
         // primary basis, so the pool never changes which scenarios solve
         for (int attempt = 0; attempt < 2; ++attempt) {
@@ -723,6 +729,10 @@ __global__ void __launch_bounds__(256, TWOSD_HYPER_WPE(R)) lp_hyper_kernel(Hyper
             const double thmax = wmin(bnu / bde);
             if (thmax == INFINITY) {
                 status = TWOSD_LP_INFEASIBLE;
+                if constexpr (RAY) {
+                    ray_r = r;
+                    ray_up = delta > 0;
+                }
                 h_wave_sync();
 #pragma unroll
                 for (int c = 0; c < C; ++c) alpha[64 * c + lane] = 0.0;
@@ -1044,14 +1054,23 @@ __global__ void __launch_bounds__(256, TWOSD_HYPER_WPE(R)) lp_hyper_kernel(Hyper
             }
         }
         if constexpr (FULL) {
-        if (status == TWOSD_LP_OPTIMAL && (P.pi || P.y)) {
-            const double *qc = CP.q;
+        // RAY: an infeasible exit recovers e_r' B^{-1} (row r of the final inverse: the pivot row the
+        // ratio test found no entering column in) instead of c_B' B^{-1}.  ut is all zero here (the
+        // exit cleared alpha; at K = 0 the pricing never touched it), so the seed is the one entry.
+        bool rayrec = false;
+        if constexpr (RAY) rayrec = status == TWOSD_LP_INFEASIBLE && CP.ray != nullptr;
+        if ((status == TWOSD_LP_OPTIMAL && (P.pi || P.y)) || rayrec) {
+            if (rayrec) {
+                if (lane == (ray_r & 63)) ut[ray_r] = 1.0;
+            } else {
+                const double *qc = CP.q;
 #pragma unroll
-            for (int t = 0; t < R; ++t) {
-                const int j = hb[t] >> 2;
-                const bool bq = hb[t] >= 0 && j < n;
-                const double qj = qc[bq ? j : 0];
-                ut[64 * t + lane] = bq ? qj : 0.0;
+                for (int t = 0; t < R; ++t) {
+                    const int j = hb[t] >> 2;
+                    const bool bq = hb[t] >= 0 && j < n;
+                    const double qj = qc[bq ? j : 0];
+                    ut[64 * t + lane] = bq ? qj : 0.0;
+                }
             }
             h_wave_sync();
             for (int tt = K - 1; tt >= 0; --tt) {
@@ -1084,13 +1103,39 @@ __global__ void __launch_bounds__(256, TWOSD_HYPER_WPE(R)) lp_hyper_kernel(Hyper
             h_wave_sync();
 #pragma unroll
             for (int t = 0; t < R; ++t) ut[64 * t + lane] = 0.0;
-            if (P.pi) {
+            if constexpr (RAY) {
+                if (rayrec) {
+                    // sigma = sign(delta) rho: with no eligible column, sg rho' a_j <= HTOL_PIV for every
+                    // structural column and sigma has the sign of a dual on every slack; sigma' b = |delta| > 0.
+                    // The key: the final basis as a set (as bkey), the leaving variable and the sign -- W is
+                    // fixed, so equal keys are equal rays.
+                    const auto *A = h_args();
+                    const size_t ro = (size_t)(P.pi_by_pos ? qpos : s);
+                    double *po = A->ray + ro * m;
+                    const uint64_t sm = ray_up ? 0ull : (1ull << 63);
+                    unsigned long long h = 0;
+#pragma unroll
+                    for (int t = 0; t < R; ++t)
+                        if (64 * t + lane < m) {
+                            po[64 * t + lane] = pv[t] == 0.0 ? 0.0 : h_flip(pv[t], sm);
+                            h += mix64((unsigned long long)(hb[t] >> 2));
+                        }
+#pragma unroll
+                    for (int o = 32; o > 0; o >>= 1) h += __shfl_xor(h, o);
+                    const int leaving = h_get_row_i<R>(hb, ray_r) >> 2;
+                    if (lane == 0) {
+                        if (A->ray_row) A->ray_row[ro] = ray_r;
+                        if (A->ray_key) A->ray_key[ro] = mix64(h ^ mix64(((unsigned long long)leaving << 1) | (ray_up ? 1ull : 0ull)));
+                    }
+                }
+            }
+            if (!rayrec && P.pi) {
                 double *po = P.pi + (size_t)(P.pi_by_pos ? qpos : s) * m;
 #pragma unroll
                 for (int t = 0; t < R; ++t)
                     if (64 * t + lane < m) po[64 * t + lane] = pv[t];
             }
-            if (P.y) {
+            if (!rayrec && P.y) {
                 double *yo = P.y + (size_t)s * n;
                 for (int j = lane; j < n; j += 64) yo[j] = 0.0;
                 __builtin_amdgcn_s_waitcnt(0);
@@ -1525,7 +1570,9 @@ int hyper_cols_per_lane(int ncols) {
 template <int R, int C>
 static hipError_t hl(const HyperParams &p, int nb, size_t lds, hipStream_t s) {
     // the lean kernel when the launch asks for none of the recovery / refresh outputs
-    if (p.pi || p.y || p.head_out || p.bkey || p.eo_K)
+    if (p.ray)   // twosd_solve_rays' re-solve of the infeasible scenarios
+        hipLaunchKernelGGL((lp_hyper_kernel<R, C, true, true>), dim3(nb), dim3(256), lds, s, p);
+    else if (p.pi || p.y || p.head_out || p.bkey || p.eo_K)
         hipLaunchKernelGGL((lp_hyper_kernel<R, C, true>), dim3(nb), dim3(256), lds, s, p);
     else
         hipLaunchKernelGGL((lp_hyper_kernel<R, C, false>), dim3(nb), dim3(256), lds, s, p);

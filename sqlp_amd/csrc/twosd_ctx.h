@@ -74,6 +74,34 @@ struct BootState {
     double ms[2] = {0, 0};        // device time of the last twosd_reform_cuts: partial sums, finalize (with its copies)
 };
 
+// feasibility rays (feas.hip): the ray set F and the workspaces of twosd_solve_rays.  Dropped with
+// the template and the random positions, like the pick handles.
+struct FrayState {
+    int mv = 0, size = 0;         // ray length (the LP's rows), rays in F
+    DevBuf<double> F;             // TWOSD_FRAY_MAX x mv normalised rays, insertion order
+    DevBuf<unsigned long long> keys;   // their dedup keys (feas_rays.h)
+    DevBuf<int> d_meta;           // [0] size, [1] != 0: the last push would have overflowed
+    // push: the incoming rays, their normalised forms, keys, validity and resulting indices
+    DevBuf<double> in, nrm;
+    DevBuf<unsigned long long> inkey;
+    DevBuf<int> ok, idx;
+    // twosd_solve_rays: the infeasible scenarios (ascending), the re-solve's outputs by list
+    // position, the kept rays and what goes with them
+    DevBuf<char> flag, tmp;
+    DevBuf<int> list, list2, cnt, zero, sel;
+    long long resolved = 0, filtered = 0;   // of the last twosd_solve_rays: list positions re-solved / dropped by the scan filter
+    DevBuf<double> ray, ray_out;
+    DevBuf<int> ray_row, row_out, head_out, scen_out;
+    DevBuf<unsigned long long> ray_key;
+    // twosd_feas_scan: the rays' operands at x (the cut's prep: element gathers and bases), the
+    // blocks' partial maxima, the merged result, the cut-off flags and their count
+    DevBuf<double> pk, pkt, pko, base, pmax, rmax, dvsel;
+    DevBuf<int> parg, rarg;
+    DevBuf<unsigned long long> scratch, ncut;
+    DevBuf<unsigned char> cut;
+    double scan_us = 0.0;         // device time of the last twosd_feas_scan's scan and merge kernels
+};
+
 // the slots of twosd_last_timings, in the order the ABI reports them (microseconds)
 enum TimeSlot : int {
     T_LP = 0,         // LP kernel of the last batch (solve_push in re-solve mode: main pass + representatives)
@@ -282,6 +310,7 @@ struct TemplateState {
     double push_rep_frac = 0.0;   // representatives / scenarios of the last keyed solve_push (push mode choice)
     int last_push_full = 0;       // 1: the last solve_push recovered every dual in its main pass
     twosd::DevBuf<double> d_pi_rep;   // the representatives' dual rows gathered for the push (full mode)
+    twosd::FrayState fray;        // feasibility ray set and twosd_solve_rays' workspaces (feas.hip)
 };
 
 // The context: the template state plus what lives as long as the handle.
@@ -314,6 +343,8 @@ struct LpRun {
     int nlist = 0;
     int kcap = 0;                 // > 0: pivot cap below kmax, no retry from the primary basis (refresh training)
     double *lp_us_out = nullptr;  // list mode: the launch's LP kernel time (c->last is not written)
+    bool want_ray = false;        // list mode only: Farkas rays, leaving rows and ray keys of the infeasible
+                                  // scenarios into c->fray.ray / ray_row / ray_key, rows by list position
 };
 // Launch the LP kernel over N scenarios whose deltas start at d_dv (device); results in
 // c->d_obj / d_pi / d_y / d_status / d_iters [0, N) (lp_batch.hip).

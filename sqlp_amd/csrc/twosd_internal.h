@@ -80,6 +80,12 @@ struct HyperParams {
     int *eo_pb, *eo_K, *eo_off, *eo_etap, *eo_etaoff;   // nullable (eo_K == nullptr: off)
     int *eo_eidx; double *eo_evals;
     unsigned long long *eo_used; long long eo_cap;      // claim counter (64-bit); arena entries (<= INT32_MAX)
+    // Farkas rays (the RAY instantiation only; rows as pi: list position or scenario): per infeasible
+    // scenario sigma = +-e_r' B^{-1} (m doubles, unnormalised, in the sign convention of pi), the leaving
+    // row r, and a key of (final basis set, leaving variable, sign); ray == nullptr: off
+    double *ray;
+    int *ray_row;
+    unsigned long long *ray_key;
 };
 
 // ---- device pool build of a refresh (pool_gpu.hip) ---------------------------------

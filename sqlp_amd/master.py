@@ -272,6 +272,10 @@ class sdCell:
         self.rho = 0.0
         self.master_status = None      # termination status of the last master solve
         self.master_obj = None
+        # feasibility rows alpha + beta'x <= 0 on x alone (no eta column), from Farkas rays of
+        # infeasible stage-2 LPs; every master solve appends them
+        self.feas_rows: list = []
+        self.feas_margin = 0.0         # rows enter the master as beta'x <= -alpha - feas_margin (1 + |alpha|)
 
     def objf_original(self, x) -> float:
         """evaluate_expr(cell.objf_original, x): the root-stage objective c'x."""
@@ -287,6 +291,17 @@ class sdCell:
         """cell.jl:130-134: objective + sum_i rho/2 (x_i - x0_i)^2."""
         self.reg_center = np.array(x0, dtype=np.float64)
         self.rho = float(rho)
+
+    def add_feasibility_row(self, alpha, beta) -> bool:
+        """Store the feasibility row alpha + beta'x <= 0; a row equal to a stored one in alpha and
+        beta is not added twice.  Returns whether it was added."""
+        alpha = float(alpha)
+        beta = np.array(beta, dtype=np.float64).reshape(self.n1)
+        for a, b in self.feas_rows:
+            if a == alpha and np.array_equal(b, beta):
+                return False
+        self.feas_rows.append((alpha, beta))
+        return True
 
     def sync_cuts(self):
         """cell.jl:198-201."""
@@ -315,9 +330,12 @@ class sdCell:
         nz = n1 + E
         epi_rows = np.asarray(epi_rows, dtype=np.int64)
         alpha = np.asarray(alpha, dtype=np.float64)
+        fixed = []   # epigraphs without a cut: eta fixed at the lower bound, for a cell with feasibility rows only
         for e in range(E):
             if not np.any(epi_rows == e):
-                raise RuntimeError(f"epigraph {e} has no cut: the master is unbounded")
+                if not self.feas_rows:
+                    raise RuntimeError(f"epigraph {e} has no cut: the master is unbounded")
+                fixed.append(e)
         H = np.zeros(nz)
         g = np.concatenate([self.c1, [e.objective_weight for e in self.epi]])
         if self.reg_center is not None and self.rho != 0.0:
@@ -330,6 +348,16 @@ class sdCell:
             Gc[:, :n1] = beta
             Gc[np.arange(len(alpha)), n1 + epi_rows] = -1.0
         Gb, hb = _bound_rows(self.sp1.ylb, self.sp1.yub, nz)
+        if self.feas_rows:   # beta'x <= -alpha - margin, after the bound rows (the cut rows keep their place)
+            fa = np.array([a for a, _ in self.feas_rows])
+            Gf = np.zeros((len(fa), nz))
+            Gf[:, :n1] = np.array([b for _, b in self.feas_rows])
+            Gb, hb = np.vstack([Gb, Gf]), np.concatenate([hb, -fa - self.feas_margin * (1.0 + np.abs(fa))])
+        if fixed:
+            Af = np.zeros((len(fixed), nz))
+            Af[np.arange(len(fixed)), n1 + np.array(fixed)] = 1.0
+            Aeq = np.vstack([Aeq, Af])
+            beq = np.concatenate([beq, [self.epi[e].lower_bound for e in fixed]])
         res = qp_solve(H, g, Aeq, beq, np.vstack([G, Gc, Gb]), np.concatenate([h, -alpha, hb]))
         lam = res.lam[G.shape[0]:G.shape[0] + len(alpha)]
         const = 0.5 * self.rho * float(self.reg_center @ self.reg_center) if self.reg_center is not None else 0.0
@@ -342,19 +370,90 @@ class sdCell:
                 for e in range(len(self.epi))]
 
 
+DEFAULT_FEAS_MARGIN = 1e-15   # ten times the smallest margin at which every measured loop ended well
+
+
+def _scan_rows(cell: sdCell, x) -> int:
+    """Scan every epigraph over all its scenarios against the ray set at x and store the row of
+    every ray that cuts some scenario off (ray_max > 0); returns how many rows were new."""
+    added = 0
+    for epi in cell.epi:
+        if epi.num_scenarios == 0:
+            continue
+        sc = twosd.feas_scan(epi, x)
+        for j in np.nonzero(sc.ray_max > 0)[0]:
+            added += cell.add_feasibility_row(sc.alpha[j], sc.beta[j])
+    return added
+
+
+def _new_infeasible(cell: sdCell, x, firsts, counts) -> int:
+    """solve_rays on the new scenarios of every epigraph at x, rays pushed; infeasible scenarios."""
+    return sum(twosd.solve_rays(epi, x, first, cnt, push=True).n_infeasible
+               for epi, first, cnt in zip(cell.epi, firsts, counts))
+
+
+def _feasibility_rounds(cell: sdCell, firsts, counts, max_rounds):
+    """Rounds of (scan, rows, master) until every new scenario's LP is feasible at x_candidate, then
+    the same check at x_incumbent.  Returns whether the incumbent was cut off (and
+    replaced by the candidate)."""
+    F = twosd.sdFeasRaySet(cell.ctx)
+    for rnd in range(max_rounds + 1):
+        added = _scan_rows(cell, cell.x_candidate) if F.size > 0 else 0
+        if added == 0:
+            ninf = _new_infeasible(cell, cell.x_candidate, firsts, counts)
+            if ninf == 0:
+                break
+            added = _scan_rows(cell, cell.x_candidate)
+            if added == 0:
+                raise RuntimeError(f"feasibility round {rnd}: {ninf} new scenarios infeasible at the candidate, "
+                                   f"but no ray of the {F.size} held yields a new row ({len(cell.feas_rows)} stored; "
+                                   f"margin {cell.feas_margin:g})")
+        if rnd == max_rounds:
+            raise RuntimeError(f"feasibility: {max_rounds} rounds did not make the candidate feasible "
+                               f"({len(cell.feas_rows)} rows, {F.size} rays)")
+        cell.x_candidate = cell.solve_master()
+    cut_off = (_scan_rows(cell, cell.x_incumbent) > 0) if F.size > 0 else False
+    if not cut_off and F.size > 0:   # a stored row may already exclude it
+        cut_off = any(a + float(b @ cell.x_incumbent) > 0 for a, b in cell.feas_rows)
+    if not cut_off and _new_infeasible(cell, cell.x_incumbent, firsts, counts) > 0:
+        cut_off = True
+        _scan_rows(cell, cell.x_incumbent)
+    if cut_off:
+        cell.x_incumbent = cell.x_candidate.copy()
+    return cut_off
+
+
 def sd_iteration(cell: sdCell, scenario_list, update_incumbent_cut=True, quad_scalar_schedule=None,
-                 tie_rel=0.0, keep_picks=False):
+                 tie_rel=0.0, keep_picks=False, feasibility=False, max_feas_rounds=20, feas_margin=None):
     """sd_iteration! (algorithm.jl:39-115).  scenario_list[i] = element values (k) of the new
     scenario of epigraph i.  Steps 1-3 and 5-6 (the data-parallel hot segment) run on the GPU
     (twosd.sd_iteration_solve / sd_iteration_cuts); cut removal, incumbent selection,
     the prox schedule and the master solve run here.  keep_picks: every new cut keeps its argmax
     picks on the device (for stopping.bootstrap_gap_test), and the picks of cuts that left the
-    epigraphs are released."""
+    epigraphs are released.
+    feasibility=True: instances without relatively complete recourse.  After the
+    new scenarios are added, rounds of violation scan / ray extraction / master solve add feasibility
+    rows to the cell until every new scenario's LP is feasible at the candidate (at most
+    max_feas_rounds master solves; a round without progress raises RuntimeError), then the incumbent
+    is checked the same way and replaced by the candidate when it is cut off.  feas_margin: the rows
+    enter the master as beta'x <= -alpha - feas_margin (1 + |alpha|) (default DEFAULT_FEAS_MARGIN).
+    With the default False nothing changes: an infeasible scenario raises TwoSDError."""
     if quad_scalar_schedule is None:
         quad_scalar_schedule = ConstantQuadScalarSchedule(0.1)
     assert len(scenario_list) == len(cell.epi)                        # algorithm.jl:42
     vals = [np.atleast_2d(np.asarray(v, dtype=np.float64)) for v in scenario_list]
-    twosd.sd_iteration_solve(cell.epi, vals, cell.x_candidate, cell.x_incumbent, cell.dual_vertices)
+    if feasibility:
+        # without complete recourse: the new scenarios are added first, feasibility rows make the
+        # candidate and the incumbent feasible for them, and every LP solved below is optimal
+        cell.feas_margin = DEFAULT_FEAS_MARGIN if feas_margin is None else float(feas_margin)
+        firsts = [e.num_scenarios for e in cell.epi]
+        for epi, v in zip(cell.epi, vals):
+            twosd.add_scenarios(epi, v, np.ones(v.shape[0]))
+        if _feasibility_rounds(cell, firsts, [v.shape[0] for v in vals], max_feas_rounds):
+            update_incumbent_cut = True   # the incumbent moved: its cut is rebuilt whatever the caller said
+        twosd.sd_iteration_solve(cell.epi, vals, cell.x_candidate, cell.x_incumbent, cell.dual_vertices, added_at=firsts)
+    else:
+        twosd.sd_iteration_solve(cell.epi, vals, cell.x_candidate, cell.x_incumbent, cell.dual_vertices)
     # remove cuts with small multipliers (algorithm.jl:57-72)
     if cell.master_status == OPTIMAL:
         cell.cuts.remove_cuts_by_multiplier(cell.epi, cell.cut_duals())

@@ -609,6 +609,131 @@ def push(dvs: sdDualVertexSet, vec):
     return dvs.push(vec)
 
 
+def fray_key(ray):
+    """(key, normalised ray) of one feasibility ray: what a push into sdFeasRaySet computes
+    (twosd_fray_key: a pure host function).  An all-zero or non-finite ray raises."""
+    ray = _f64(ray).ravel()
+    key = C.c_uint64()
+    out = np.zeros(ray.shape[0])
+    check(_lib.load().twosd_fray_key(ptr(ray), ray.shape[0], C.byref(key), ptr(out)))
+    return key.value, out
+
+
+class sdFeasRaySet:
+    """Device-resident set F of normalised feasibility rays of an SDContext.
+    There is one set per context; twosd_set_template and set_positions drop it."""
+
+    def __init__(self, ctx: SDContext):
+        self.ctx = ctx
+
+    def push_batch(self, rays) -> np.ndarray:
+        """Push every row in order; returns the index each row maps to (first occurrence kept)."""
+        rays = _f64(np.atleast_2d(rays))
+        if rays.shape[1] != self.ctx.mv:
+            raise ValueError(f"ray length {rays.shape[1]} != {self.ctx.mv}")
+        out = np.zeros(rays.shape[0], dtype=np.int32)
+        ns = C.c_int()
+        check(self.ctx.lib.twosd_fray_push(self.ctx.h, rays.shape[0], ptr(rays), ptr(out), C.byref(ns)))
+        return out
+
+    @property
+    def size(self) -> int:
+        s = C.c_int()
+        check(self.ctx.lib.twosd_fray_size(self.ctx.h, C.byref(s)))
+        return s.value
+
+    def __len__(self):
+        return self.size
+
+    def get(self, first=0, count=None) -> np.ndarray:
+        count = self.size - first if count is None else count
+        out = np.zeros((count, self.ctx.mv))
+        check(self.ctx.lib.twosd_fray_get(self.ctx.h, int(first), int(count), ptr(out)))
+        return out
+
+    def clear(self):
+        check(self.ctx.lib.twosd_fray_clear(self.ctx.h))
+
+
+@dataclass
+class RayBatch:
+    """Result of solve_rays: the infeasible scenarios' count, and per returned ray its scenario
+    (index of the epigraph), the raw ray sigma = +-e_r' B^{-1}, the leaving row r and the basis head
+    at the exit; status of every scenario of the batch."""
+    n_infeasible: int
+    scen: np.ndarray
+    rays: np.ndarray
+    row: np.ndarray
+    head: np.ndarray
+    status: np.ndarray
+
+
+def solve_rays(epi: "sdEpigraph", x, first=0, count=None, cap=256, push=True) -> RayBatch:
+    """Solve scenarios [first, first+count) of epi at x and recover one Farkas ray per distinct
+    infeasible exit (twosd_solve_rays), at most cap, in scenario order; push=True also pushes them
+    into the context's sdFeasRaySet on the device.  Infeasible scenarios do not raise; a scenario
+    that ends at the iteration limit or numerically does."""
+    ctx = epi.ctx
+    count = epi.num_scenarios - first if count is None else count
+    cap = int(cap)
+    scen = np.zeros(max(cap, 1), dtype=np.int32)
+    rays = np.zeros((max(cap, 1), ctx.mv))
+    row = np.zeros(max(cap, 1), dtype=np.int32)
+    head = np.zeros((max(cap, 1), ctx.mv), dtype=np.int32)
+    st = np.zeros(max(count, 1), dtype=np.int32)
+    ni, nr = C.c_int(), C.c_int()
+    check(ctx.lib.twosd_solve_rays(ctx.h, epi.index, ptr(_f64(x)), int(first), int(count), cap, 1 if push else 0,
+                                   C.byref(ni), C.byref(nr), ptr(scen), ptr(rays), ptr(row), ptr(head), ptr(st)))
+    n = nr.value
+    return RayBatch(ni.value, scen[:n], rays[:n], row[:n], head[:n], st[:count])
+
+
+def last_ray_stats(ctx: SDContext):
+    """(list positions re-solved, infeasible scenarios the scan filter dropped) of the last solve_rays."""
+    a, b = C.c_int64(), C.c_int64()
+    check(ctx.lib.twosd_last_ray_stats(ctx.h, C.byref(a), C.byref(b), None))
+    return a.value, b.value
+
+
+def last_scan_us(ctx: SDContext) -> float:
+    """Device time (events) of the scan and merge kernels of the last feas_scan, in microseconds."""
+    t = C.c_double()
+    check(ctx.lib.twosd_last_ray_stats(ctx.h, None, None, C.byref(t)))
+    return t.value
+
+
+@dataclass
+class FeasScan:
+    """Result of feas_scan: per ray of F its largest score over the scenarios and the lowest
+    scenario attaining it, the feasibility row alpha + beta'x <= 0 of that pair, and per scenario
+    whether any ray cuts it off at x (score > 0)."""
+    ray_max: np.ndarray
+    ray_arg: np.ndarray
+    alpha: np.ndarray
+    beta: np.ndarray
+    n_cut_off: int
+    cut_off: np.ndarray
+
+
+def feas_scan(epi: "sdEpigraph", x, first=0, count=None) -> FeasScan:
+    """Violation scan of scenarios [first, first+count) of epi against every ray of the context's
+    sdFeasRaySet at x (twosd_feas_scan).  An empty ray set raises (TWOSD_E_STATE)."""
+    ctx = epi.ctx
+    count = epi.num_scenarios - first if count is None else count
+    s = C.c_int()
+    check(ctx.lib.twosd_fray_size(ctx.h, C.byref(s)))
+    J = max(s.value, 1)
+    rmax = np.zeros(J)
+    rarg = np.zeros(J, dtype=np.int32)
+    alpha = np.zeros(J)
+    beta = np.zeros((J, ctx.n1))
+    ncut = C.c_int64()
+    cut = np.zeros(max(count, 1), dtype=np.uint8)
+    check(ctx.lib.twosd_feas_scan(ctx.h, epi.index, ptr(_f64(x)), int(first), int(count), ptr(rmax), ptr(rarg), ptr(alpha),
+                                  ptr(beta), C.byref(ncut), ptr(cut)))
+    return FeasScan(rmax, rarg, alpha, beta, ncut.value, cut[:count].astype(bool))
+
+
 class sdEpigraph:
     """sdEpigraph (epigraph.jl:17-61): scenario pool + weights on the device, cuts on the host."""
 
@@ -1186,18 +1311,22 @@ class sdEpigraphInfo:
                    epi.lower_bound)
 
 
-def sd_iteration_solve(epis, scenario_values, x_candidate, x_incumbent, V: sdDualVertexSet):
+def sd_iteration_solve(epis, scenario_values, x_candidate, x_incumbent, V: sdDualVertexSet, added_at=None):
     """algorithm.jl:45-55: for every epigraph i, add_scenario!(epi_i, w_i, 1.0), solve at
     x_candidate and at x_incumbent and push! both duals.  The duals are pushed in the
     reference's order (epi 1 cand, epi 1 inc, epi 2 cand, ...; for a block of several
     scenarios per epigraph: cand/inc per scenario in order).  scenario_values[i] is a
-    (N_i x k) block of new scenarios for epigraph i.  Returns the vertex index of every
-    pushed dual (the order above)."""
+    (N_i x k) block of new scenarios for epigraph i.  added_at[i] (optional): the block was already
+    added to epigraph i at that index (the feasibility rounds of master.sd_iteration run between
+    the two).  Returns the vertex index of every pushed dual (the order above)."""
     pis = []
-    for epi, vals in zip(epis, scenario_values):
+    for i, (epi, vals) in enumerate(zip(epis, scenario_values)):
         vals = np.atleast_2d(vals)
-        first = epi.num_scenarios
-        add_scenarios(epi, vals, np.ones(vals.shape[0]))
+        if added_at is None:
+            first = epi.num_scenarios
+            add_scenarios(epi, vals, np.ones(vals.shape[0]))
+        else:
+            first = added_at[i]
         _, _, pc, _ = solve_batch(epi, x_candidate, first, vals.shape[0])
         _, _, pinc, _ = solve_batch(epi, x_incumbent, first, vals.shape[0])
         inter = np.empty((2 * vals.shape[0], pc.shape[1]))
