@@ -709,6 +709,74 @@ int twosd_reform_partial_vr(twosd_ctx *ctx, int epi, int H, const int *handles, 
  * [0] the partial sums (histograms, delta streaming, reductions), [1] the finalize with its copies. */
 int twosd_reform_last_ms(twosd_ctx *ctx, double *ms2);
 
+/* ---- risk measures: weighted quantiles, tail cuts, out-of-sample CVaR -----
+ * No reference counterpart: the reference optimises the expectation only.  Mean-CVaR in the form
+ * of Rockafellar and Uryasev, CVaR_a(h) = min_eta eta + E[(h - eta)+] / (1 - a).
+ *
+ * twosd_quantile_of_values: VaR and CVaR at `level` of the caller's own n values (1 <= n <= 2^27),
+ * selected on the device.  An entry counts when status is NULL or its status is TWOSD_LP_OPTIMAL;
+ * the others are counted in *n_bad and their values are never read into a sum (they may be NaN).
+ * Weights are integers: q_s = rn(w_s * rn(2^58 / W)) with W the weights' sum in index order (the
+ * scale of twosd_reform_cuts), or q_s = 1 when weights is NULL.  With Q = sum q_s over the counted
+ * entries and t = ceil(level * Q), taken exactly (level is a dyadic rational):
+ *     *var     = the smallest counted value v with sum_{value <= v} q_s >= t,
+ *     *tail_q  = sum_{value > *var} q_s,   *total_q = Q   (integers: the same bits on every run),
+ *     *cvar    = *var + (sum_{value > *var} q_s (value_s - *var)) / ((1 - level) Q).
+ * Values are ordered by their sign-flipped bit patterns: the numeric order, with -0 before +0.  The
+ * fp64 sum has a fixed shard layout and every operation is rounded on its own, so all outputs are
+ * bit-identical on every run and under any launch grid.  Every output is nullable.
+ * TWOSD_E_ARG unless 0 < level < 1, 1 <= n <= 2^27, every weight is finite and >= 0, and some
+ * entry counts with a positive integer weight (*n_bad and *total_q are still set then).
+ *
+ * twosd_cut_quantile: the same over the last cut of epigraph epi -- the values are its scenarios'
+ * maximal scores in the caller's space (val[s] + c0 in one rounded add: what twosd_build_cut
+ * returns in max_val), the weights the scenario weights with W the epigraph's total weight.
+ * *tail_weight and *total_weight are tail_q and Q times W / 2^58.  The state rule is that of
+ * twosd_picks_keep: TWOSD_E_STATE if the last cut call was not for epi, took the empty-epigraph
+ * path, or the template, the positions or the vertex set were reset since.
+ *
+ * twosd_cut_tail: the tail cut of the last cut of epi at eta (same state rule).  With
+ * f_s = 1[(val[s] + c0) > eta] (strict; the rounded sum above) and a(s) the stored pick:
+ *     W_t = sum f_s w_s,   p_s = f_s w_s / W_t,
+ *     g = sum p_s pi_a(s),   S_e = sum p_s PK[a(s), e] dv[s, e],
+ *     *alpha = g.r + sum_{e rhs} S_e + c0,   beta = -T'g - sum_{e in T} S_e e_col(e)    (beta: n1)
+ * -- twosd_reform_cuts with the counts f, its integer weights and fixed shard layout (bit-identical
+ * on every run and under any grid).  *tail_weight = W_t and *total_weight = the weight of the cut's
+ * scenarios, both through the integer scale (nullable).  No scenario in the tail: the zero cut with
+ * *tail_weight = 0.  With d = *tail_weight / *total_weight the row
+ *     tau >= d (alpha + beta'x - eta)
+ * is a subgradient of (1/W) sum_s w_s (max_v pi_v (r_s - T_s x) - eta)+ at the cut's x and eta, so
+ * it bounds the sample's E[(h - eta)+] from below at every (x, eta).
+ * TWOSD_E_UNSUPPORTED for k beyond the cut's envelope of 127; TWOSD_E_ARG for a NaN eta.
+ *
+ * twosd_risk_last_ms: device time (HIP events, milliseconds) of [0] the last quantile selection
+ * (of any of the calls here) and [1] the last twosd_cut_tail, copies included. */
+int twosd_quantile_of_values(twosd_ctx *ctx, int64_t n, const double *values, const double *weights, const int *status,
+                             double level, double *var, double *cvar, uint64_t *tail_q, uint64_t *total_q, int64_t *n_bad);
+int twosd_cut_quantile(twosd_ctx *ctx, int epi, double level, double *var, double *cvar, double *tail_weight,
+                       double *total_weight);
+int twosd_cut_tail(twosd_ctx *ctx, int epi, double eta, double *alpha, double *beta, double *tail_weight,
+                   double *total_weight);
+int twosd_risk_last_ms(twosd_ctx *ctx, double *ms2);
+
+/* Out-of-sample CVaR of the stage-2 objective at x over scenarios [first, first + count) of the
+ * i.i.d. device stream `seed` (1 <= count <= 2^27; TWOSD_E_UNSUPPORTED beyond): sampled and solved
+ * in the chunks of twosd_evaluate_moments, the objectives and statuses of the whole range kept on
+ * the device (12 bytes per scenario) and never copied to the host.  var = the level-quantile with
+ * unit weights (twosd_quantile_of_values); y = the moments, reduced once over the whole range, of
+ *     Y_s = var + max(obj_s - var, 0) / (1 - level)        (each operation rounded on its own)
+ * so cvar = y.mean and sqrt(y.m2 / (n - 1) / n) is its asymptotic standard error (the plain-sample
+ * one: the quantile's own estimation error enters in second order only).  n / n_bad: optimal and
+ * other LPs; with n_bad > 0 the return value is TWOSD_E_LP and *out is filled from the optimal
+ * ones.  The caller adds c'x to var and cvar.  There is no plan argument: i.i.d. streams only. */
+typedef struct twosd_cvar {
+    int64_t n, n_bad;
+    double var, cvar;
+    twosd_moments y;
+} twosd_cvar;
+int twosd_evaluate_cvar(twosd_ctx *ctx, const double *x, uint64_t seed, int64_t first, int64_t count, double level,
+                        twosd_cvar *out);
+
 /* Timing of the last kernel phases on the context's stream (HIP events), microseconds:
  * [0] LP kernel, [1] dedup push, [2] argmax+cut partial, [3] cut finalize,
  * [4] warm-start pool selection of the last LP batch (0 without a pool). */

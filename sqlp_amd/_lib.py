@@ -125,6 +125,11 @@ SIGNATURES = [
     ("twosd_solve_rays", I, [P, I, P, I, I, I, I, P, P, P, P, P, P, P]),
     ("twosd_last_ray_stats", I, [P, P, P, P]),
     ("twosd_feas_scan", I, [P, I, P, I, I, P, P, P, P, P, P]),
+    ("twosd_quantile_of_values", I, [P, C.c_int64, P, P, P, D, P, P, P, P, P]),
+    ("twosd_cut_quantile", I, [P, I, D, P, P, P, P]),
+    ("twosd_cut_tail", I, [P, I, D, P, P, P, P]),
+    ("twosd_risk_last_ms", I, [P, P]),
+    ("twosd_evaluate_cvar", I, [P, P, C.c_uint64, C.c_int64, C.c_int64, D, P]),
 ]
 
 DIST_DISCRETE, DIST_NORMAL, DIST_UNIFORM, DIST_BLOCK, DIST_LINTR = 0, 1, 2, 3, 4
@@ -150,6 +155,11 @@ class Lintr(C.Structure):
 class Moments(C.Structure):
     """struct twosd_moments (include/twosd_hip.h)."""
     _fields_ = [("n", C.c_int64), ("n_bad", C.c_int64), ("mean", D), ("m2", D), ("min", D), ("max", D)]
+
+
+class Cvar(C.Structure):
+    """struct twosd_cvar (include/twosd_hip.h)."""
+    _fields_ = [("n", C.c_int64), ("n_bad", C.c_int64), ("var", D), ("cvar", D), ("y", Moments)]
 
 
 _lib = None

@@ -306,6 +306,7 @@ static int cut_finalize_impl(twosd_ctx *c, const double *x, const unsigned long 
 }
 
 const int *cut_last_arg(twosd_ctx *c) { return c->cut_ws ? c->cut_ws->arg.p : nullptr; }
+const double *cut_last_val(twosd_ctx *c) { return c->cut_ws ? c->cut_ws->val.p : nullptr; }
 
 int cut_pk_current(twosd_ctx *c, const double **PK, int *k4) {
     int rc = update_pk(c);

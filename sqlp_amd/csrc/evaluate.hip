@@ -428,6 +428,45 @@ extern "C" int twosd_evaluate_ci_vr(twosd_ctx *c, const double *x, uint64_t seed
     return evaluate_ci(c, x, seed, first, batch, n_max, z, rel_tol, abs_tol, offset, out, half_width, converged, pl);
 }
 
+// Out-of-sample CVaR (risk.hip): the i.i.d. stream solved in evaluate_moments' chunks, every
+// objective and status kept on the device (12 bytes per scenario), the level-quantile selected
+// with unit weights, Y = var + max(obj - var, 0) / (1 - level) formed in place and reduced once
+// over the whole range by the moments kernel.
+extern "C" int twosd_evaluate_cvar(twosd_ctx *c, const double *x, uint64_t seed, int64_t first, int64_t count, double level,
+                                   twosd_cvar *out) {
+    int rc = eval_check_state(c, "evaluate_cvar");
+    if (rc) return rc;
+    if (!out || first < 0 || count < 1 || (c->n1 > 0 && !x)) return fail(TWOSD_E_ARG, "evaluate_cvar: bad arguments");
+    if (!(level > 0.0 && level < 1.0)) return fail(TWOSD_E_ARG, "evaluate_cvar: level = %g outside (0, 1)", level);
+    if (count > (1ll << 27))
+        return fail(TWOSD_E_UNSUPPORTED, "evaluate_cvar: count = %lld scenarios exceed 2^27 (their objectives stay on the device)",
+                    (long long)count);
+    HIPCHK(hipSetDevice(c->device));
+    RiskState &S = c->risk;
+    if ((rc = S.obj.fit((size_t)count)) || (rc = S.ost.fit((size_t)count))) return rc;
+    const int64_t chunk = eval_chunk_size(1);
+    bool lp_bad = false;
+    for (int64_t at = 0; at < count; at += chunk) {
+        const int n = (int)std::min(chunk, count - at);
+        rc = eval_solve_chunk(c, x, first + at, n, seed, EvalPlan());
+        if (rc == TWOSD_E_LP) lp_bad = true;
+        else if (rc) return rc;
+        HIPCHK(hipMemcpyAsync(S.obj + at, c->d_obj, sizeof(double) * n, hipMemcpyDeviceToDevice, c->stream));
+        HIPCHK(hipMemcpyAsync(S.ost + at, c->d_status, sizeof(int) * n, hipMemcpyDeviceToDevice, c->stream));
+        HIPCHK(hipStreamSynchronize(c->stream));   // the next solve may reallocate d_obj / d_status
+    }
+    *out = twosd_cvar{0, count, NAN, NAN, kMomentsEmpty};
+    out->y.n_bad = count;
+    RiskResult R{};
+    if ((rc = risk_select(c, count, S.obj, nullptr, S.ost, 1.0, false, 0.0, level, "evaluate_cvar", &R)))
+        return lp_bad && R.n_ok == 0 ? fail(TWOSD_E_LP, "evaluate_cvar: none of %lld scenario LPs is optimal", (long long)count) : rc;
+    if ((rc = risk_form_y(c, count, S.obj, S.ost, R.var, 1.0 - level))) return rc;
+    twosd_moments y;
+    if ((rc = device_moments(c, count, S.obj, S.ost, nullptr, nullptr, &y))) return rc;
+    out->n = y.n; out->n_bad = y.n_bad; out->var = R.var; out->cvar = y.mean; out->y = y;
+    return eval_lp_result(lp_bad, y, "evaluate_cvar");
+}
+
 // evaluate(sp1, sp2, sto, x; N) stage-2 part (smps_routines.jl:67-82) on device-drawn
 // scenarios: *s2 = sum over scenarios first..first+count-1 of the stream `seed`, in index
 // order, of (1/N_total) * obj (s2_cost += 1/N*obj, :79).  Chunks of <= 1M scenarios (fixed: not

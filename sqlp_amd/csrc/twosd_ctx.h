@@ -102,6 +102,21 @@ struct FrayState {
     double scan_us = 0.0;         // device time of the last twosd_feas_scan's scan and merge kernels
 };
 
+// risk measures (risk.hip): the workspaces of the quantile selection and of the tail cut, the
+// uploads of twosd_quantile_of_values and the objectives twosd_evaluate_cvar keeps on the device.
+// Grow-only scratch: nothing here outlives the call that filled it.
+struct RiskState {
+    DevBuf<unsigned long long> u64;   // the passes' digit histograms, then the selection record (risk.hip: RiskSel)
+    DevBuf<double> part;              // the tail sum's shard partials
+    DevBuf<double> val, w;            // quantile_of_values: the caller's values and weights
+    DevBuf<int> st;                   //   and statuses
+    DevBuf<double> obj;               // evaluate_cvar: the whole range's objectives, overwritten by Y
+    DevBuf<int> ost;                  //   and statuses
+    DevBuf<unsigned long long> thist; // tail cut: [0] W_t, [1] the total, [2 ..) the per-vertex weights
+    DevBuf<double> slots, S, gpart, out;   // tail cut: shard partials of S, S, g partials, [alpha, beta]
+    double ms[2] = {0, 0};            // device time of the last selection / tail re-formation
+};
+
 // the slots of twosd_last_timings, in the order the ABI reports them (microseconds)
 enum TimeSlot : int {
     T_LP = 0,         // LP kernel of the last batch (solve_push in re-solve mode: main pass + representatives)
@@ -311,6 +326,7 @@ struct TemplateState {
     int last_push_full = 0;       // 1: the last solve_push recovered every dual in its main pass
     twosd::DevBuf<double> d_pi_rep;   // the representatives' dual rows gathered for the push (full mode)
     twosd::FrayState fray;        // feasibility ray set and twosd_solve_rays' workspaces (feas.hip)
+    twosd::RiskState risk;        // quantile selection and tail cut workspaces (risk.hip)
 };
 
 // The context: the template state plus what lives as long as the handle.
@@ -402,6 +418,17 @@ void cut_truncate_pk(twosd_ctx *c, int size);   // V truncated to size: PK rows 
 // brought up to date with the vertex set)
 const int *cut_last_arg(twosd_ctx *c);
 int cut_pk_current(twosd_ctx *c, const double **PK, int *k4);
+// for risk.hip: the maximal scores of the last cut (device, last_cut_n doubles, the canonical LP's:
+// without c0)
+const double *cut_last_val(twosd_ctx *c);
+// risk.hip, for twosd_evaluate_cvar (evaluate.hip).  risk_select: the weighted quantile of n
+// device-resident values (weights / status nullable; scale: the integer weights' factor), every
+// output of twosd_quantile_of_values; TWOSD_E_ARG when no entry counts.  risk_form_y:
+// y[i] = var + max(obj[i] - var, 0) / denom in place, each operation rounded on its own.
+struct RiskResult { double var, cvar; unsigned long long tail_q, total_q; long long n_bad, n_ok; };
+int risk_select(twosd_ctx *c, long long n, const double *d_val, const double *d_w, const int *d_st, double scale, bool has_add,
+                double add, double level, const char *who, RiskResult *out);
+int risk_form_y(twosd_ctx *c, long long n, double *d_obj, const int *d_st, double var, double denom);
 // sampling plans (api.hip): a caller's plan -> (mode, G), NULL meaning i.i.d.; and `what` = value
 // must be a whole number of groups.  Both fail with TWOSD_E_ARG and the offending value.
 int sampling_plan(const twosd_sampling *plan, const char *who, int *mode, int *G);

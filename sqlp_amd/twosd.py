@@ -1217,6 +1217,128 @@ def reform_last_ms(ctx: SDContext):
     return out
 
 
+# -- risk measures: weighted quantiles, tail cuts, out-of-sample CVaR (risk.hip; the reference
+#    optimises the expectation only) -----------------------------------------------------------
+@dataclass(frozen=True)
+class Quantile:
+    """twosd_quantile_of_values' result: VaR and CVaR at `level`, and the integer weights
+    tail_q = sum of q_s over value > var, total_q = Q; n_bad entries were left out."""
+    var: float
+    cvar: float
+    tail_q: int
+    total_q: int
+    n_bad: int
+
+
+def _level(level) -> float:
+    level = float(level)
+    if not 0.0 < level < 1.0:
+        raise ValueError(f"level = {level} outside (0, 1)")
+    return level
+
+
+def quantile_of_values(ctx: SDContext, values, level, weights=None, status=None) -> Quantile:
+    """VaR / CVaR at `level` of the caller's own values, selected on the device
+    (twosd_quantile_of_values): integer weights q_s = rn(w_s 2^58 / sum w) (1 without weights),
+    entries whose status is not optimal left out (n_bad), the threshold ceil(level Q) exact."""
+    values = _f64(np.ravel(values))
+    w = None if weights is None else _f64(np.ravel(weights))
+    st = None if status is None else np.ascontiguousarray(np.ravel(status), dtype=np.int32)
+    if (w is not None and w.shape != values.shape) or (st is not None and st.shape != values.shape):
+        raise ValueError("weights / status and values differ in length")
+    var, cvar = C.c_double(), C.c_double()
+    tq, Q, nb = C.c_uint64(), C.c_uint64(), C.c_int64()
+    check(ctx.lib.twosd_quantile_of_values(ctx.h, C.c_int64(values.size), ptr(values), ptr(w), ptr(st), float(level),
+                                           C.byref(var), C.byref(cvar), C.byref(tq), C.byref(Q), C.byref(nb)))
+    return Quantile(var.value, cvar.value, tq.value, Q.value, nb.value)
+
+
+@dataclass(frozen=True)
+class CutQuantile:
+    """twosd_cut_quantile's result: VaR and CVaR of the last cut's scores under the scenario
+    weights; tail_weight = the weight of the scenarios scoring above var."""
+    var: float
+    cvar: float
+    tail_weight: float
+    total_weight: float
+
+
+def cut_quantile(epi: sdEpigraph, level) -> CutQuantile:
+    """VaR / CVaR at `level` of the maximal scores of the last cut built on epi (what
+    build_sasa_cut returns in max_val), under the scenario weights; no score leaves the device."""
+    ctx = epi.ctx
+    out = [C.c_double() for _ in range(4)]
+    check(ctx.lib.twosd_cut_quantile(ctx.h, epi.index, _level(level), *[C.byref(o) for o in out]))
+    return CutQuantile(*[o.value for o in out])
+
+
+@dataclass
+class sdTailCut:
+    """cut_tail's result: tau >= d (alpha + beta'x - eta) with d = tail_weight / total_weight
+    bounds the sample's E[(h - eta)+] from below; the zero cut with tail_weight 0 when no scenario
+    scores above eta."""
+    alpha: float
+    beta: np.ndarray
+    tail_weight: float
+    total_weight: float
+    eta: float
+
+    @property
+    def d(self) -> float:
+        return self.tail_weight / self.total_weight
+
+
+def cut_tail(epi: sdEpigraph, eta) -> sdTailCut:
+    """twosd_cut_tail: the last cut built on epi re-formed from its picks over the scenarios whose
+    score exceeds eta (strictly), normalised by their weight."""
+    ctx = epi.ctx
+    a, tw, W = C.c_double(), C.c_double(), C.c_double()
+    beta = np.zeros(ctx.n1)
+    check(ctx.lib.twosd_cut_tail(ctx.h, epi.index, float(eta), C.byref(a), ptr(beta), C.byref(tw), C.byref(W)))
+    return sdTailCut(a.value, beta, tw.value, W.value, float(eta))
+
+
+def risk_last_ms(ctx: SDContext):
+    """Device milliseconds of [the last quantile selection, the last cut_tail]."""
+    out = np.zeros(2)
+    check(ctx.lib.twosd_risk_last_ms(ctx.h, ptr(out)))
+    return out
+
+
+@dataclass(frozen=True)
+class EvaluateCVaR:
+    """twosd_evaluate_cvar's result (c'x included in var and cvar): y holds the moments of
+    Y = var + (obj - var)+ / (1 - level), whose mean is cvar."""
+    var: float
+    cvar: float
+    n: int
+    n_bad: int
+    y: Moments
+
+    @property
+    def std_error(self) -> float:
+        """Asymptotic standard error of cvar (the plain-sample one of Y)."""
+        return self.y.std_error
+
+    def half_width(self, z: float = 1.959963984540054) -> float:
+        return z * self.std_error
+
+
+def evaluate_cvar(ctx: SDContext, first_stage_cost, x, seed, first, count, level, raise_on_status=True,
+                  sampling=None) -> EvaluateCVaR:
+    """Out-of-sample VaR and CVaR at `level` of c'x + obj_w over scenarios [first, first+count) of
+    the i.i.d. device stream `seed` (twosd_evaluate_cvar: no objective leaves the device).
+    Variance-reduced plans are not supported: ValueError for a sampling= other than i.i.d."""
+    if sampling is not None and (int(sampling.mode) != _lib.SAMPLING_IID or int(sampling.group) != 1):
+        raise ValueError("evaluate_cvar: i.i.d. streams only (no variance-reduced plan)")
+    out = _lib.Cvar()
+    rc = ctx.lib.twosd_evaluate_cvar(ctx.h, ptr(_f64(x)), C.c_uint64(seed), C.c_int64(first), C.c_int64(count), _level(level),
+                                     C.byref(out))
+    _lp_status_ok(rc, raise_on_status)
+    c = float(np.dot(first_stage_cost, x))
+    return EvaluateCVaR(out.var + c, out.cvar + c, int(out.n), int(out.n_bad), _shift(Moments._of(out.y), c))
+
+
 def reform_partial_len(ctx: SDContext, cuts, M):
     hs = _handles_of(cuts)
     a, b = C.c_int64(), C.c_int64()
