@@ -350,7 +350,7 @@ extern "C" int twosd_set_random_positions(twosd_ctx *c, int k, const int *row, c
     c->has_blocks = false;
     c->has_lintr = false;
     cut_invalidate_pk(c);
-    c->boot = twosd::BootState();   // stored picks and the re-formation's template copies
+    c->reform = twosd::ReformState();   // stored picks and the re-formation's template copies
     c->fray = twosd::FrayState();   // the feasibility rays and their workspaces
     return TWOSD_OK;
 }

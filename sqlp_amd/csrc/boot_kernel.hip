@@ -39,25 +39,21 @@
 //                        lanes = elements (e = lane, lane + 64) while the tile's scenarios go by one
 //                        at a time with wave-uniform picks and counts (v_readlane); 16 + 1
 //                        accumulators per element stay in VGPRs (KE = 2: 191 VGPRs, no scratch)
-//   boot_reduce_kernel   the blocks' S partials summed in block order
-//   boot_g_kernel        gpart = (per-vertex weights) x V for 8 replicate rows at a time, skipping the
-//                        vertices no scenario picked (the identity row's weight is 0)
-//   boot_final_kernel    g, alpha, beta per (handle, replicate), normalised by W_jb
+// then reform.hip's stage, shared with the tail cut of risk.hip: S from the shards' partials, g, and
+// alpha, beta per (handle, replicate) normalised by W_jb.  boot_hist_kernel and boot_reform_kernel
+// stay the bootstrap's own: do not merge them with risk.hip's look-alikes (reform.hip's header).
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <algorithm>
 #include <cmath>
 #include <vector>
-#include "twosd_ctx.h"
+#include "reform.h"
 #include "philox.h"
 
 namespace twosd {
 
 constexpr int kBootMaxM = 64;            // bootstrap replicates per call
 constexpr int kBootGroup = 16;           // replicates whose accumulators a wave holds at once (4 Philox calls)
-constexpr int kBootMaxChunks = 512;      // blocks per (handle, replicate group): the S partials' shard count
-constexpr int kBootRB = 8;               // replicate rows per block of boot_g_kernel
-constexpr double kBootFix = 288230376151711744.0;   // 2^58: sum of 12 q_s stays below 2^62
 
 // Poisson(1) count of a uniform 32-bit word: #{ j : u >= T_j }, T_j = rne(2^32 sum_{i<=j} e^-1 / i!)
 TWOSD_HD int boot_count_of_word(uint32_t u) {
@@ -69,10 +65,6 @@ TWOSD_HD int boot_count_of_word(uint32_t u) {
 // the four counts of replicates 4 Q .. 4 Q + 3 for global scenario g
 TWOSD_HD Philox4 boot_words(unsigned long long g, int Q, unsigned long long seed) {
     return philox4x32_10((uint32_t)g, (uint32_t)(g >> 32), (uint32_t)Q, 1u, (uint32_t)seed, (uint32_t)(seed >> 32));
-}
-
-__device__ __forceinline__ unsigned long long boot_q(double w, double scale) {
-    return w > 0.0 ? (unsigned long long)__double2ull_rn(w * scale) : 0ull;   // NaN and w <= 0 weigh nothing
 }
 
 // GR (here and below): the draw's index is the scenario's group, first / off count groups and G is
@@ -111,7 +103,7 @@ __global__ void __launch_bounds__(256) boot_weight_kernel(int n, const double *_
     const int nq = (M + 3) / 4, Q = blockIdx.y;
     unsigned long long a[4] = {0ull, 0ull, 0ull, 0ull};
     for (int s = blockIdx.x * 256 + threadIdx.x; s < n; s += gridDim.x * 256) {
-        const unsigned long long q = boot_q(w[s], scale);
+        const unsigned long long q = reform_q(w[s], scale);
         if (Q == nq) { a[0] += q; continue; }
         const Philox4 r = boot_words(boot_index<GR>(off, s, G), Q, seed);
 #pragma unroll
@@ -151,7 +143,7 @@ __global__ void __launch_bounds__(1024) boot_hist_kernel(int n, int nv, int nvs,
     for (int s = blockIdx.x * 1024 + threadIdx.x; s < n; s += gridDim.x * 1024) {
         const int pick = picks[s];
         if (pick < v0 || pick >= v1) continue;
-        const unsigned long long q = boot_q(w[s], scale);
+        const unsigned long long q = reform_q(w[s], scale);
         if (!q) continue;
         if (Q == nq) {
             __hip_atomic_fetch_add(&hl[pick - v0], q, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
@@ -215,7 +207,7 @@ __global__ void __launch_bounds__(256) boot_reform_kernel(BootParams P) {
         const bool valid = s < P.n;
         const int pick = valid ? P.picks[s] : -1;
         const bool ok = pick >= 0 && pick < P.nv;          // a scenario without a pick weighs in W only
-        const unsigned long long q = ok ? boot_q(P.w[s], P.scale) : 0ull;
+        const unsigned long long q = ok ? reform_q(P.w[s], P.scale) : 0ull;
         unsigned chi[kBootGroup];                           // high word of (double)count: 0 for count 0
 #pragma unroll
         for (int qd = 0; qd < kBootGroup / 4; ++qd) {
@@ -316,104 +308,9 @@ __global__ void __launch_bounds__(256) boot_reform_kernel(BootParams P) {
     }
 }
 
-// S[row][e] = sum over the chunks in a fixed order: 8 segments of consecutive chunks summed side by
-// side (32 outputs per block), then the segments in order
-__global__ void __launch_bounds__(256) boot_reduce_kernel(int nchunks, int width, const double *__restrict__ slots,
-                                                          double *__restrict__ out) {
-    __shared__ double sh[8][32];
-    const int li = threadIdx.x & 31, seg = threadIdx.x >> 5;
-    const int idx = blockIdx.x * 32 + li;
-    const int per = (nchunks + 7) / 8;
-    const int c0 = seg * per, c1 = min(nchunks, c0 + per);
-    double s = 0.0;
-    if (idx < width)
-        for (int c = c0; c < c1; ++c) s += slots[(size_t)c * width + idx];
-    sh[seg][li] = s;
-    __syncthreads();
-    if (seg != 0 || idx >= width) return;
-    double t = 0.0;
-#pragma unroll
-    for (int g = 0; g < 8; ++g) t += sh[g][li];
-    out[idx] = t;
-}
-
-// gpart[c][b][i] = sum_{v in vertex chunk c} hist[b][v] V[v][i] for rows b0 .. b0 + 7 (blockIdx.y)
-__global__ void __launch_bounds__(256) boot_g_kernel(int nv, int nvs, int m, int chunk, int B,
-                                                     const unsigned long long *__restrict__ hist, const double *__restrict__ V,
-                                                     double *__restrict__ gpart) {
-    const int b0 = blockIdx.y * kBootRB;
-    const int v0 = blockIdx.x * chunk, v1 = min(nv, v0 + chunk);
-    for (int i = threadIdx.x; i < m; i += 256) {
-        double acc[kBootRB];
-#pragma unroll
-        for (int r = 0; r < kBootRB; ++r) acc[r] = 0.0;
-        for (int v = v0; v < v1; ++v) {
-            if (hist[v] == 0ull) continue;   // row 0 (all counts 1): no scenario picks v, so no replicate weighs it
-            const double x = V[(size_t)v * m + i];
-#pragma unroll
-            for (int r = 0; r < kBootRB; ++r)
-                if (b0 + r < B) acc[r] = fma((double)hist[(size_t)(b0 + r) * nvs + v], x, acc[r]);
-        }
-#pragma unroll
-        for (int r = 0; r < kBootRB; ++r)
-            if (b0 + r < B) gpart[((size_t)blockIdx.x * B + b0 + r) * m + i] = acc[r];
-    }
-}
-
-// one block per replicate row b of one handle: g = sum of the vertex chunks (chunk order), then
-// alpha = (g.r + sum_{e rhs} S_e) / Wq (+ c0), beta = (-T'g - sum_{e in T} S_e e_col) / Wq; Wq = 0:
-// the zero cut with weight_mark 0 (the reference's empty-epigraph cut).  Outputs at index b * H + j.
-__global__ void __launch_bounds__(256) boot_final_kernel(int B, int H, int j, int m, int n1, int k, int nbc,
-                                                         const double *__restrict__ gpart, const double *__restrict__ r,
-                                                         const double *__restrict__ T, const int *__restrict__ col,
-                                                         const double *__restrict__ S, const unsigned long long *__restrict__ Wq,
-                                                         double wunit, double c0, double *__restrict__ alpha,
-                                                         double *__restrict__ beta, double *__restrict__ wm) {
-    __shared__ double gs[1024];
-    __shared__ double as;
-    const int b = blockIdx.x;
-    const size_t o = (size_t)b * H + j;
-    double *bo = beta + o * n1;
-    const unsigned long long wq = Wq[b];
-    if (wq == 0ull) {
-        for (int jj = threadIdx.x; jj < n1; jj += 256) bo[jj] = 0.0;
-        if (threadIdx.x == 0) { alpha[o] = 0.0; wm[o] = 0.0; }
-        return;
-    }
-    for (int i = threadIdx.x; i < m; i += 256) {
-        double s = 0.0;
-        for (int c = 0; c < nbc; ++c) s += gpart[((size_t)c * B + b) * m + i];
-        gs[i] = s;
-    }
-    __syncthreads();
-    for (int jj = threadIdx.x; jj < n1; jj += 256) {
-        double s = 0.0;
-        for (int i = 0; i < m; ++i) s = fma(T[(size_t)i * n1 + jj], gs[i], s);
-        bo[jj] = -s;
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        double a = 0.0;
-        for (int i = 0; i < m; ++i) a = fma(gs[i], r[i], a);
-        for (int e = 0; e < k; ++e) {
-            const double se = S[(size_t)b * k + e];
-            if (col[e] < 0) a += se;
-            else bo[col[e]] -= se;
-        }
-        as = a;
-    }
-    __syncthreads();
-    const double inv = 1.0 / (double)wq;
-    for (int jj = threadIdx.x; jj < n1; jj += 256) bo[jj] *= inv;
-    if (threadIdx.x == 0) {
-        alpha[o] = as * inv + c0;
-        wm[o] = (double)wq * wunit;
-    }
-}
-
 static PickSet *pick_of(twosd_ctx *c, int handle) {
-    if (handle < 0 || handle >= (int)c->boot.picks.size() || !c->boot.picks[handle].live) return nullptr;
-    return &c->boot.picks[handle];
+    if (handle < 0 || handle >= (int)c->reform.picks.size() || !c->reform.picks[handle].live) return nullptr;
+    return &c->reform.picks[handle];
 }
 
 // a usable handle, or the error code with its message
@@ -429,11 +326,6 @@ static int usable_pick(twosd_ctx *c, int handle, const char *what, PickSet **out
     return TWOSD_OK;
 }
 
-struct BootLayout {
-    int H, B, nvs, k;
-    size_t o_wj, o_hist, n_u64, n_f64;   // u64: [B totals][H x B Wj][H x B x nvs hist]; f64: H x B x k sums
-};
-
 static int boot_layout(twosd_ctx *c, int epi, int H, const int *handles, int M, const char *what, BootLayout *L) {
     if (!c || !c->has_template) return fail(TWOSD_E_STATE, "%s: no template", what);
     if (H < 1 || !handles) return fail(TWOSD_E_ARG, "%s: H = %d handles (at least 1)", what, H);
@@ -448,11 +340,7 @@ static int boot_layout(twosd_ctx *c, int epi, int H, const int *handles, int M, 
             return fail(TWOSD_E_ARG, "%s: pick handle %d belongs to epigraph %d, not %d", what, handles[j], h->epi, epi);
         nvs = std::max(nvs, h->nv);
     }
-    L->H = H; L->B = M + 1; L->nvs = nvs; L->k = c->k;
-    L->o_wj = (size_t)L->B;
-    L->o_hist = L->o_wj + (size_t)H * L->B;
-    L->n_u64 = L->o_hist + (size_t)H * L->B * nvs;
-    L->n_f64 = std::max<size_t>((size_t)H * L->B * c->k, 1);
+    *L = boot_offsets(H, M, nvs, c->k);
     return TWOSD_OK;
 }
 
@@ -462,7 +350,7 @@ static int boot_partial_impl(twosd_ctx *c, int epi, const BootLayout &L, const i
                              unsigned long long off, int G, double total_weight, unsigned long long *d_u64, double *d_f64) {
     const EpiDevice &E = c->epis[epi];
     const int k = c->k, B = L.B;
-    const double scale = kBootFix / total_weight;
+    const double scale = kReformFix / total_weight;
     const double *PK = nullptr;
     int k4 = 0, rc;
     if ((rc = cut_pk_current(c, &PK, &k4))) return rc;
@@ -480,25 +368,16 @@ static int boot_partial_impl(twosd_ctx *c, int epi, const BootLayout &L, const i
     };
     weights(E.count, d_u64);
     const int ngroups = std::max(1, (M + kBootGroup - 1) / kBootGroup);
-    // the blocks' shard layout of a handle depends on its own scenario count alone
-    auto shard = [](int n, int *tpb, int *nchunks) {
-        const int ntiles = (n + 63) / 64;
-        const int want = std::min(kBootMaxChunks, (ntiles + 3) / 4);
-        *tpb = (ntiles + want - 1) / want;
-        *nchunks = (ntiles + *tpb - 1) / *tpb;
-    };
     size_t slots_need = 1;
     for (int j = 0; j < L.H; ++j) {
-        const PickSet &h = c->boot.picks[handles[j]];
+        const PickSet &h = c->reform.picks[handles[j]];
         if (h.n > E.count)
             return fail(TWOSD_E_STATE, "reform: pick handle %d holds %d scenarios, epigraph %d only %d", handles[j], h.n, epi, E.count);
-        int tpb, nchunks;
-        shard(h.n, &tpb, &nchunks);
-        slots_need = std::max(slots_need, (size_t)nchunks * B * k);
+        slots_need = std::max(slots_need, (size_t)reform_shards(h.n).nchunks * B * k);   // h.n >= 1: picks_keep
     }
-    if ((rc = c->boot.slots.fit(slots_need))) return rc;   // once, before the first launch that writes it
+    if ((rc = c->reform.slots.fit(slots_need))) return rc;   // once, before the first launch that writes it
     for (int j = 0; j < L.H; ++j) {
-        const PickSet &h = c->boot.picks[handles[j]];
+        const PickSet &h = c->reform.picks[handles[j]];
         weights(h.n, d_u64 + L.o_wj + (size_t)j * B);
         const dim3 hgrid(std::max(1, std::min((h.n + 8191) / 8192, 64)), nq + 1, (h.nv + kBootVW - 1) / kBootVW);
         if (G == 1)
@@ -508,14 +387,13 @@ static int boot_partial_impl(twosd_ctx *c, int epi, const BootLayout &L, const i
             hipLaunchKernelGGL(boot_hist_kernel<true>, hgrid, dim3(1024), 0, c->stream, h.n, h.nv, L.nvs, M, h.d.p, E.d_w.p, scale, seed,
                                off, d_u64 + L.o_hist + (size_t)j * B * L.nvs, (unsigned)G);
         if (k == 0) continue;
-        int tpb, nchunks;
-        shard(h.n, &tpb, &nchunks);
+        const ReformShards sh = reform_shards(h.n);
         BootParams P{};
-        P.n = h.n; P.k = k; P.k4 = k4; P.nv = h.nv; P.M = M; P.ngroups = ngroups; P.tpb = tpb; P.G = G;
+        P.n = h.n; P.k = k; P.k4 = k4; P.nv = h.nv; P.M = M; P.ngroups = ngroups; P.tpb = sh.tpb; P.G = G;
         P.scale = scale; P.seed = seed; P.off = off;
         P.dv = E.d_dv; P.w = E.d_w; P.PK = PK; P.picks = h.d;
-        P.slots = c->boot.slots;
-        const dim3 rgrid(nchunks * ngroups);
+        P.slots = c->reform.slots;
+        const dim3 rgrid(sh.nchunks * ngroups);
         if (G == 1) {
             if (k <= 64) hipLaunchKernelGGL((boot_reform_kernel<1, 0>), rgrid, dim3(256), 0, c->stream, P);
             else hipLaunchKernelGGL((boot_reform_kernel<2, 0>), rgrid, dim3(256), 0, c->stream, P);
@@ -526,50 +404,27 @@ static int boot_partial_impl(twosd_ctx *c, int epi, const BootLayout &L, const i
             if (k <= 64) hipLaunchKernelGGL((boot_reform_kernel<1, 1>), rgrid, dim3(256), 0, c->stream, P);
             else hipLaunchKernelGGL((boot_reform_kernel<2, 1>), rgrid, dim3(256), 0, c->stream, P);
         }
-        hipLaunchKernelGGL(boot_reduce_kernel, dim3((B * k + 31) / 32), dim3(256), 0, c->stream, nchunks, B * k, c->boot.slots.p,
-                           d_f64 + (size_t)j * B * k);
+        reform_sum_shards(c, true, sh.nchunks, B * k, c->reform.slots.p, d_f64 + (size_t)j * B * k);
     }
     HIPCHK(hipGetLastError());
-    return TWOSD_OK;
-}
-
-static int boot_template(twosd_ctx *c) {
-    BootState &S = c->boot;
-    if (S.tmpl_ready) return TWOSD_OK;
-    int rc;
-    std::vector<int> col(std::max(c->k, 1), -1);
-    for (int e = 0; e < c->k; ++e) col[e] = c->pos_col[e];
-    std::vector<double> T = c->T;
-    if (T.empty()) T.push_back(0.0);
-    if ((rc = S.d_T.upload(T)) || (rc = S.d_r.upload(c->r)) || (rc = S.d_col.upload(col))) return rc;
-    S.tmpl_ready = true;
     return TWOSD_OK;
 }
 
 static int boot_finalize_impl(twosd_ctx *c, const BootLayout &L, const int *handles, double total_weight,
                               const unsigned long long *d_u64, const double *d_f64, double *alpha, double *beta,
                               double *weight_mark, double *total_out) {
-    BootState &S = c->boot;
-    const int B = L.B, H = L.H, m = c->L.m, n1 = c->n1, k = c->k;
+    ReformState &S = c->reform;
+    const int B = L.B, H = L.H, n1 = c->n1, k = c->k;
     int rc;
-    if ((rc = boot_template(c))) return rc;
+    if ((rc = reform_prepare(c, B, H, L.nvs))) return rc;
     const size_t rows = (size_t)B * H;
-    if ((rc = S.d_alpha.fit(rows)) || (rc = S.d_beta.fit(std::max<size_t>(rows * n1, 1))) || (rc = S.d_wm.fit(rows))) return rc;
-    const double wunit = total_weight / kBootFix;
-    // vertex chunks of 32 or more, at most 256 of them
-    if ((rc = S.gpart.fit((size_t)std::max(1, (L.nvs + 31) / 32) * B * m))) return rc;
+    const double wunit = total_weight / kReformFix;
     for (int j = 0; j < H; ++j) {
-        const PickSet &h = c->boot.picks[handles[j]];
-        const int chunk = std::max(32, (h.nv + 255) / 256);
-        const int nbc = std::max(1, (h.nv + chunk - 1) / chunk);
-        const unsigned long long *hist = d_u64 + L.o_hist + (size_t)j * B * L.nvs;
-        hipLaunchKernelGGL(boot_g_kernel, dim3(nbc, (B + kBootRB - 1) / kBootRB), dim3(256), 0, c->stream, h.nv, L.nvs, m, chunk, B,
-                           hist, c->dvs.V, S.gpart.p);
-        hipLaunchKernelGGL(boot_final_kernel, dim3(B), dim3(256), 0, c->stream, B, H, j, m, n1, k, nbc, S.gpart.p, S.d_r.p, S.d_T.p,
-                           S.d_col.p, d_f64 + (size_t)j * B * k, d_u64 + L.o_wj + (size_t)j * B, wunit, c->has_bounds ? c->c0 : 0.0,
-                           S.d_alpha.p, S.d_beta.p, S.d_wm.p);
+        const PickSet &h = S.picks[handles[j]];
+        if ((rc = reform_finalize_block(c, B, H, j, h.nv, L.nvs, d_u64 + L.o_hist + (size_t)j * B * L.nvs, d_f64 + (size_t)j * B * k,
+                                        d_u64 + L.o_wj + (size_t)j * B, wunit)))
+            return rc;
     }
-    HIPCHK(hipGetLastError());
     std::vector<unsigned long long> tw(B);
     HIPCHK(hipMemcpyAsync(alpha, S.d_alpha, sizeof(double) * rows, hipMemcpyDeviceToHost, c->stream));
     if (n1 > 0) HIPCHK(hipMemcpyAsync(beta, S.d_beta, sizeof(double) * rows * n1, hipMemcpyDeviceToHost, c->stream));
@@ -596,17 +451,17 @@ static int bootstrap_counts_impl(twosd_ctx *c, int M, uint64_t seed, uint64_t fi
     if (count == 0) return TWOSD_OK;
     HIPCHK(hipSetDevice(c->device));
     int rc;
-    if ((rc = c->boot.counts.fit((size_t)count * M))) return rc;
+    if ((rc = c->reform.counts.fit((size_t)count * M))) return rc;
     const long long total = count * ((M + 3) / 4);
     const dim3 grid((unsigned)((total + 255) / 256));
     if (G == 1)
         hipLaunchKernelGGL(boot_counts_kernel<false>, grid, dim3(256), 0, c->stream, M, (unsigned long long)seed,
-                           (unsigned long long)first_index, (long long)count, c->boot.counts.p, 1u);
+                           (unsigned long long)first_index, (long long)count, c->reform.counts.p, 1u);
     else
         hipLaunchKernelGGL(boot_counts_kernel<true>, grid, dim3(256), 0, c->stream, M, (unsigned long long)seed,
-                           (unsigned long long)first_index / (unsigned long long)G, (long long)count, c->boot.counts.p, (unsigned)G);
+                           (unsigned long long)first_index / (unsigned long long)G, (long long)count, c->reform.counts.p, (unsigned)G);
     HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(out, c->boot.counts, (size_t)count * M, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipMemcpyAsync(out, c->reform.counts, (size_t)count * M, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
     return TWOSD_OK;
 }
@@ -629,24 +484,16 @@ extern "C" int twosd_bootstrap_counts_vr(twosd_ctx *c, int M, uint64_t seed, uin
 extern "C" int twosd_picks_keep(twosd_ctx *c, int epi, int *handle) {
     if (!c || !c->has_template) return fail(TWOSD_E_STATE, "picks_keep: no template");
     if (!handle) return fail(TWOSD_E_ARG, "picks_keep: handle is NULL");
-    if (epi < 0 || epi >= (int)c->epis.size()) return fail(TWOSD_E_ARG, "picks_keep: epigraph %d does not exist", epi);
-    if (c->last_cut_epi < 0)
-        return fail(TWOSD_E_STATE, "picks_keep: no cut to keep the picks of (none built, or the template, the positions or "
-                    "the vertex set were reset since)");
-    if (c->last_cut_epi != epi)
-        return fail(TWOSD_E_STATE, "picks_keep: the last cut was built on epigraph %d, not %d", c->last_cut_epi, epi);
-    const int *arg = cut_last_arg(c);
-    if (c->last_cut_n <= 0 || !arg)
-        return fail(TWOSD_E_STATE, "picks_keep: the last cut of epigraph %d took the empty-epigraph path (no picks)", epi);
+    int rc = cut_last_usable(c, epi, "picks_keep", "keep");
+    if (rc) return rc;
     HIPCHK(hipSetDevice(c->device));
-    std::vector<PickSet> &v = c->boot.picks;
+    std::vector<PickSet> &v = c->reform.picks;
     int id = 0;
     while (id < (int)v.size() && v[id].live) ++id;
     if (id == (int)v.size()) v.emplace_back();
     PickSet &h = v[id];
-    int rc;
     if ((rc = h.d.alloc(c->last_cut_n))) return rc;
-    HIPCHK(hipMemcpyAsync(h.d, arg, sizeof(int) * c->last_cut_n, hipMemcpyDeviceToDevice, c->stream));
+    HIPCHK(hipMemcpyAsync(h.d, cut_last_arg(c), sizeof(int) * c->last_cut_n, hipMemcpyDeviceToDevice, c->stream));
     h.epi = epi; h.n = c->last_cut_n; h.nv = c->last_cut_nv; h.live = true; h.stale = false;
     *handle = id;
     return TWOSD_OK;
@@ -687,7 +534,7 @@ extern "C" int twosd_picks_release(twosd_ctx *c, int handle) {
 extern "C" int twosd_picks_count(twosd_ctx *c, int *live) {
     if (!c || !live) return fail(TWOSD_E_ARG, "picks_count: NULL");
     int n = 0;
-    for (const PickSet &h : c->boot.picks) n += h.live ? 1 : 0;
+    for (const PickSet &h : c->reform.picks) n += h.live ? 1 : 0;
     *live = n;
     return TWOSD_OK;
 }
@@ -717,7 +564,7 @@ static int reform_whole_groups(twosd_ctx *c, int epi, int H, const int *handles,
         return fail(TWOSD_E_ARG, "%s: epigraph %d holds %d scenarios, no multiple of the sampling group %d", what, epi,
                     c->epis[epi].count, G);
     for (int j = 0; j < H; ++j) {
-        const PickSet &h = c->boot.picks[handles[j]];
+        const PickSet &h = c->reform.picks[handles[j]];
         if (h.n % G)
             return fail(TWOSD_E_ARG, "%s: pick handle %d holds %d scenarios, no multiple of the sampling group %d", what, handles[j],
                         h.n, G);
@@ -775,19 +622,19 @@ static int reform_cuts_impl(twosd_ctx *c, int epi, int H, const int *handles, in
     if (!(E.total_weight > 0.0)) return fail(TWOSD_E_STATE, "reform_cuts: epigraph %d holds no scenario weight", epi);
     if ((rc = reform_whole_groups(c, epi, H, handles, index_offset, G, "reform_cuts"))) return rc;
     HIPCHK(hipSetDevice(c->device));
-    if ((rc = c->boot.u64.fit(L.n_u64)) || (rc = c->boot.f64.fit(L.n_f64))) return rc;
+    if ((rc = c->reform.u64.fit(L.n_u64)) || (rc = c->reform.f64.fit(L.n_f64))) return rc;
     HIPCHK(hipEventRecord(c->ev[EV_MARK_0], c->stream));
-    if ((rc = boot_partial_impl(c, epi, L, handles, M, seed, index_offset, G, E.total_weight, c->boot.u64, c->boot.f64))) return rc;
+    if ((rc = boot_partial_impl(c, epi, L, handles, M, seed, index_offset, G, E.total_weight, c->reform.u64, c->reform.f64))) return rc;
     HIPCHK(hipEventRecord(c->ev[EV_MARK_1], c->stream));
-    if ((rc = boot_finalize_impl(c, L, handles, E.total_weight, c->boot.u64, c->boot.f64, alpha, beta, weight_mark, total_weight)))
+    if ((rc = boot_finalize_impl(c, L, handles, E.total_weight, c->reform.u64, c->reform.f64, alpha, beta, weight_mark, total_weight)))
         return rc;
     HIPCHK(hipEventRecord(c->ev[EV_MARK_2], c->stream));
     HIPCHK(hipEventSynchronize(c->ev[EV_MARK_2]));
     float ms1 = 0, ms2 = 0;
     hipEventElapsedTime(&ms1, c->ev[EV_MARK_0], c->ev[EV_MARK_1]);
     hipEventElapsedTime(&ms2, c->ev[EV_MARK_1], c->ev[EV_MARK_2]);
-    c->boot.ms[0] = ms1;
-    c->boot.ms[1] = ms2;
+    c->reform.ms[0] = ms1;
+    c->reform.ms[1] = ms2;
     return TWOSD_OK;
 }
 
@@ -807,7 +654,7 @@ extern "C" int twosd_reform_cuts_vr(twosd_ctx *c, int epi, int H, const int *han
 
 extern "C" int twosd_reform_last_ms(twosd_ctx *c, double *ms2) {
     if (!c || !ms2) return fail(TWOSD_E_ARG, "reform_last_ms: NULL");
-    ms2[0] = c->boot.ms[0];
-    ms2[1] = c->boot.ms[1];
+    ms2[0] = c->reform.ms[0];
+    ms2[1] = c->reform.ms[1];
     return TWOSD_OK;
 }

@@ -115,7 +115,7 @@ void cut_free(CutWs *w) { delete w; }
 
 void cut_truncate_pk(twosd_ctx *c, int size) {
     // stored picks over vertices past `size` name vertices that no longer exist
-    for (PickSet &h : c->boot.picks)
+    for (PickSet &h : c->reform.picks)
         if (h.live && h.nv > size) h.stale = true;
     if (c->last_cut_nv > size) c->last_cut_epi = -1;
     if (!c->cut_ws) return;
@@ -307,6 +307,19 @@ static int cut_finalize_impl(twosd_ctx *c, const double *x, const unsigned long 
 
 const int *cut_last_arg(twosd_ctx *c) { return c->cut_ws ? c->cut_ws->arg.p : nullptr; }
 const double *cut_last_val(twosd_ctx *c) { return c->cut_ws ? c->cut_ws->val.p : nullptr; }
+
+int cut_last_usable(twosd_ctx *c, int epi, const char *who, const char *verb) {
+    if (!c || !c->has_template) return fail(TWOSD_E_STATE, "%s: no template", who);
+    if (epi < 0 || epi >= (int)c->epis.size()) return fail(TWOSD_E_ARG, "%s: epigraph %d does not exist", who, epi);
+    if (c->last_cut_epi < 0)
+        return fail(TWOSD_E_STATE, "%s: no cut to %s the picks of (none built, or the template, the positions or "
+                    "the vertex set were reset since)", who, verb);
+    if (c->last_cut_epi != epi)
+        return fail(TWOSD_E_STATE, "%s: the last cut was built on epigraph %d, not %d", who, c->last_cut_epi, epi);
+    if (c->last_cut_n <= 0 || !cut_last_arg(c) || !cut_last_val(c))   // picks and scores are sized together
+        return fail(TWOSD_E_STATE, "%s: the last cut of epigraph %d took the empty-epigraph path (no picks)", who, epi);
+    return TWOSD_OK;
+}
 
 int cut_pk_current(twosd_ctx *c, const double **PK, int *k4) {
     int rc = update_pk(c);

@@ -6,7 +6,7 @@
 //     CVaR_a(h) = min_eta  eta + E[(h - eta)+] / (1 - a),  attained at eta = VaR_a(h).
 //
 // Selection.  An entry counts when its status is optimal (or status is NULL); its integer weight is
-// q_s = rn(w_s scale) (boot_kernel.hip's scale 2^58 / total weight), or 1 without weights.  With
+// q_s = rn(w_s scale) (reform.h's weight, scale 2^58 / total weight), or 1 without weights.  With
 // Q = sum q_s and t = ceil(level Q) (exact: risk_keys.h, on the host, once per call),
 //     VaR = the smallest counted value v with sum_{value <= v} q_s >= t
 // found by a most-significant-digit radix select over the order-preserving keys of risk_keys.h:
@@ -21,16 +21,16 @@
 // entries in index order, the 256 partials go through the fixed LDS tree, and the host adds the
 // shards in shard order.  Every product, difference and sum is rounded on its own (no FMA).
 //
-// Tail cut.  twosd_reform_cuts with one replicate whose count is f_s = 1[val_s (+ c0) > eta]:
+// Tail cut.  The last cut re-formed from its picks with the weights 1[val_s (+ c0) > eta] q_s:
 //   risk_thist_kernel    W_t = sum f_s q_s, the total sum q_s and the per-vertex weights (uint64
 //                        block histograms in LDS over windows of 2048 vertices, integer atomics)
 //   risk_treform_kernel  one pass over the N x k deltas: a wave walks tiles of 64 scenarios, lanes =
 //                        scenarios for pick, weight and flag, then lanes = elements while the tile's
 //                        tail scenarios go by (a scenario outside the tail is skipped: its row is
-//                        never loaded); the shard layout is boot_kernel.hip's (a function of N alone)
-//   risk_tsum_kernel     S_e = the shards' partials in shard order
-//   risk_tg_kernel       g partials over fixed vertex chunks
-//   risk_tfinal_kernel   g, alpha, beta normalised by W_t; W_t = 0: the zero cut
+//                        never loaded); the shard layout is reform_layout.h's (a function of N alone)
+// then reform.hip's stage, one handle and one row: S_e = the shards' partials in shard order (not the
+// bootstrap's eight segments), g, and alpha, beta normalised by W_t (W_t = 0: the zero cut).  The two
+// kernels above stay the tail's own: no merging with boot_kernel.hip's look-alikes (reform.hip's header).
 // No floating-point atomics anywhere; TWOSD_RISK_BLOCKS (test knob) sets the grids and must not
 // change a bit of any result.
 #include <hip/hip_runtime.h>
@@ -39,16 +39,14 @@
 #include <cmath>
 #include <cstdlib>
 #include <vector>
-#include "twosd_ctx.h"
+#include "reform.h"
 #include "risk_keys.h"
 
 namespace twosd {
 
 constexpr int kRiskBits = 8, kRiskBins = 1 << kRiskBits, kRiskPasses = 64 / kRiskBits;
 constexpr int kRiskShards = 256;                       // shards of the tail sum (fixed: the result's bits depend on it)
-constexpr double kRiskFix = 288230376151711744.0;      // 2^58, boot_kernel.hip's kBootFix
 constexpr int kRiskVW = 2048;                          // vertices per LDS histogram window of the tail cut
-constexpr int kRiskMaxChunks = 512;                    // shards of the tail cut's S sums, as kBootMaxChunks
 
 // the selection record, behind the histograms in RiskState::u64
 struct RiskSel {
@@ -68,8 +66,8 @@ struct RiskIn {
 
 __device__ __forceinline__ unsigned long long risk_q(const RiskIn &I, long long s) {
     if (!I.w) return 1ull;
-    const double w = I.w[s];
-    return w > 0.0 ? (unsigned long long)__double2ull_rn(w * I.scale) : 0ull;   // NaN and w <= 0 weigh nothing
+    const double w = I.w[s];   // reform_q, written out: through the call the selection kernels take 2 or 3 more VGPRs
+    return w > 0.0 ? (unsigned long long)__double2ull_rn(w * I.scale) : 0ull;
 }
 __device__ __forceinline__ bool risk_counted(const RiskIn &I, long long s) { return !I.st || I.st[s] == TWOSD_LP_OPTIMAL; }
 __device__ __forceinline__ double risk_value(const RiskIn &I, long long s) {
@@ -260,10 +258,6 @@ __device__ __forceinline__ bool tail_flag(const TailParams &P, int s) {
     const double v = P.val[s];
     return (P.has_add ? __dadd_rn(v, P.add) : v) > P.eta;
 }
-__device__ __forceinline__ unsigned long long tail_q(const TailParams &P, int s) {
-    const double w = P.w[s];
-    return w > 0.0 ? (unsigned long long)__double2ull_rn(w * P.scale) : 0ull;
-}
 
 // out[0] += W_t, out[1] += the total (blockIdx.y == 0 only), hist[v] += the tail weight of pick v
 // over the window of kRiskVW vertices blockIdx.y
@@ -276,7 +270,7 @@ __global__ void __launch_bounds__(1024) risk_thist_kernel(TailParams P, unsigned
     __syncthreads();
     unsigned long long wt = 0, wa = 0;
     for (int s = blockIdx.x * 1024 + threadIdx.x; s < P.n; s += gridDim.x * 1024) {
-        const unsigned long long q = tail_q(P, s);
+        const unsigned long long q = reform_q(P.w[s], P.scale);
         if (!q) continue;
         wa += q;
         if (!tail_flag(P, s)) continue;
@@ -321,7 +315,7 @@ __global__ void __launch_bounds__(256) risk_treform_kernel(TailParams P) {
             const bool valid = s < P.n;
             const int pick = valid ? P.picks[s] : -1;
             const bool ok = pick >= 0 && pick < P.nv && tail_flag(P, s);
-            const double qf = ok ? (double)tail_q(P, s) : 0.0;
+            const double qf = ok ? (double)reform_q(P.w[s], P.scale) : 0.0;
             const int qlo = __double2loint(qf), qhi = __double2hiint(qf);
             const int pk0 = ok ? pick : 0;
             unsigned long long live = __ballot(qf != 0.0);
@@ -353,97 +347,9 @@ __global__ void __launch_bounds__(256) risk_treform_kernel(TailParams P) {
     }
 }
 
-__global__ void __launch_bounds__(128) risk_tsum_kernel(int nchunks, int k, const double *__restrict__ slots, double *__restrict__ S) {
-    const int e = threadIdx.x;
-    if (e >= k) return;
-    double s = 0.0;
-    for (int cidx = 0; cidx < nchunks; ++cidx) s += slots[(size_t)cidx * k + e];
-    S[e] = s;
-}
-
-// gpart[c][i] = sum over the vertices of chunk c of hist[v] V[v][i]
-__global__ void __launch_bounds__(256) risk_tg_kernel(int nv, int m, int chunk, int nbc, const unsigned long long *__restrict__ hist,
-                                                      const double *__restrict__ V, double *__restrict__ gpart) {
-    for (int cb = blockIdx.x; cb < nbc; cb += gridDim.x) {
-        const int v0 = cb * chunk, v1 = min(nv, v0 + chunk);
-        for (int i = threadIdx.x; i < m; i += 256) {
-            double acc = 0.0;
-            for (int v = v0; v < v1; ++v) {
-                const unsigned long long h = hist[v];
-                if (h) acc = fma((double)h, V[(size_t)v * m + i], acc);
-            }
-            gpart[(size_t)cb * m + i] = acc;
-        }
-    }
-}
-
-// one block: out[0] = alpha, out[1 ..] = beta (boot_final_kernel's arithmetic for one row)
-__global__ void __launch_bounds__(256) risk_tfinal_kernel(int m, int n1, int k, int nbc, const double *__restrict__ gpart,
-                                                          const double *__restrict__ r, const double *__restrict__ T,
-                                                          const int *__restrict__ col, const double *__restrict__ S,
-                                                          const unsigned long long *__restrict__ Wq, double c0,
-                                                          double *__restrict__ out) {
-    extern __shared__ __attribute__((aligned(16))) double gs[];   // m
-    double *bo = out + 1;
-    const unsigned long long wq = Wq[0];
-    if (wq == 0ull) {
-        for (int jj = threadIdx.x; jj < n1; jj += 256) bo[jj] = 0.0;
-        if (threadIdx.x == 0) out[0] = 0.0;
-        return;
-    }
-    for (int i = threadIdx.x; i < m; i += 256) {
-        double s = 0.0;
-        for (int cb = 0; cb < nbc; ++cb) s += gpart[(size_t)cb * m + i];
-        gs[i] = s;
-    }
-    __syncthreads();
-    for (int jj = threadIdx.x; jj < n1; jj += 256) {
-        double s = 0.0;
-        for (int i = 0; i < m; ++i) s = fma(T[(size_t)i * n1 + jj], gs[i], s);
-        bo[jj] = -s;
-    }
-    __syncthreads();
-    double a = 0.0;   // thread 0's
-    if (threadIdx.x == 0) {
-        for (int i = 0; i < m; ++i) a = fma(gs[i], r[i], a);
-        for (int e = 0; e < k; ++e) {
-            const double se = S[e];
-            if (col[e] < 0) a += se;
-            else bo[col[e]] -= se;
-        }
-    }
-    __syncthreads();
-    const double inv = 1.0 / (double)wq;
-    for (int jj = threadIdx.x; jj < n1; jj += 256) bo[jj] *= inv;
-    if (threadIdx.x == 0) out[0] = a * inv + c0;
-}
-
-// the template's device copies boot_final_kernel reads, shared with the bootstrap (BootState)
-static int risk_template(twosd_ctx *c) {
-    BootState &B = c->boot;
-    if (B.tmpl_ready) return TWOSD_OK;
-    int rc;
-    std::vector<int> col(std::max(c->k, 1), -1);
-    for (int e = 0; e < c->k; ++e) col[e] = c->pos_col[e];
-    std::vector<double> T = c->T;
-    if (T.empty()) T.push_back(0.0);
-    if ((rc = B.d_T.upload(T)) || (rc = B.d_r.upload(c->r)) || (rc = B.d_col.upload(col))) return rc;
-    B.tmpl_ready = true;
-    return TWOSD_OK;
-}
-
-// the state rule of twosd_picks_keep: the last cut was built on epi, with scenarios, and its picks
-// and scores still sit in the cut workspace
+// the last cut's state rule, and the two checks of a reader of the epigraph's weights
 static int last_cut_of(twosd_ctx *c, int epi, const char *who) {
-    if (!c || !c->has_template) return fail(TWOSD_E_STATE, "%s: no template", who);
-    if (epi < 0 || epi >= (int)c->epis.size()) return fail(TWOSD_E_ARG, "%s: epigraph %d does not exist", who, epi);
-    if (c->last_cut_epi < 0)
-        return fail(TWOSD_E_STATE, "%s: no cut to read the picks of (none built, or the template, the positions or "
-                    "the vertex set were reset since)", who);
-    if (c->last_cut_epi != epi)
-        return fail(TWOSD_E_STATE, "%s: the last cut was built on epigraph %d, not %d", who, c->last_cut_epi, epi);
-    if (c->last_cut_n <= 0 || !cut_last_arg(c) || !cut_last_val(c))
-        return fail(TWOSD_E_STATE, "%s: the last cut of epigraph %d took the empty-epigraph path (no picks)", who, epi);
+    if (int rc = cut_last_usable(c, epi, who, "read")) return rc;
     if (c->last_cut_n > c->epis[epi].count)
         return fail(TWOSD_E_STATE, "%s: the last cut holds %d scenarios, epigraph %d only %d", who, c->last_cut_n, epi,
                     c->epis[epi].count);
@@ -485,7 +391,7 @@ extern "C" int twosd_quantile_of_values(twosd_ctx *c, int64_t n, const double *v
         HIPCHK(hipMemcpy(S.st, status, sizeof(int) * n, hipMemcpyHostToDevice));
     }
     RiskResult R{};
-    rc = risk_select(c, n, S.val, weights ? S.w.p : nullptr, status ? S.st.p : nullptr, weights ? kRiskFix / total : 1.0, false, 0.0,
+    rc = risk_select(c, n, S.val, weights ? S.w.p : nullptr, status ? S.st.p : nullptr, weights ? kReformFix / total : 1.0, false, 0.0,
                      level, "quantile_of_values", &R);
     if (n_bad) *n_bad = R.n_bad;
     if (total_q) *total_q = R.total_q;
@@ -504,10 +410,10 @@ extern "C" int twosd_cut_quantile(twosd_ctx *c, int epi, double level, double *v
     HIPCHK(hipSetDevice(c->device));
     const EpiDevice &E = c->epis[epi];
     RiskResult R{};
-    if ((rc = risk_select(c, c->last_cut_n, cut_last_val(c), E.d_w, nullptr, kRiskFix / E.total_weight, c->has_bounds, c->c0, level,
+    if ((rc = risk_select(c, c->last_cut_n, cut_last_val(c), E.d_w, nullptr, kReformFix / E.total_weight, c->has_bounds, c->c0, level,
                           "cut_quantile", &R)))
         return rc;
-    const double wunit = E.total_weight / kRiskFix;
+    const double wunit = E.total_weight / kReformFix;
     if (var) *var = R.var;
     if (cvar) *cvar = R.cvar;
     if (tail_weight) *tail_weight = (double)R.tail_q * wunit;
@@ -526,42 +432,35 @@ extern "C" int twosd_cut_tail(twosd_ctx *c, int epi, double eta, double *alpha, 
     HIPCHK(hipSetDevice(c->device));
     const EpiDevice &E = c->epis[epi];
     RiskState &S = c->risk;
-    const int n = c->last_cut_n, nv = c->last_cut_nv, k = c->k, m = c->L.m, n1 = c->n1;
+    ReformState &R = c->reform;   // one handle, one row: its scratch, its S sums (f64) and its output row 0
+    const int n = c->last_cut_n, nv = c->last_cut_nv, k = c->k, n1 = c->n1;
     const double *PK = nullptr;
     int k4 = 0;
-    if ((rc = cut_pk_current(c, &PK, &k4)) || (rc = risk_template(c))) return rc;
-    // the shard layout of the S sums depends on n alone (boot_kernel.hip's)
-    const int ntiles = (n + 63) / 64;
-    const int want = std::min(kRiskMaxChunks, (ntiles + 3) / 4);
-    const int tpb = (ntiles + want - 1) / want, nchunks = (ntiles + tpb - 1) / tpb;
-    // vertex chunks of 32 or more, at most 256 of them
-    const int vchunk = std::max(32, (nv + 255) / 256), nbc = std::max(1, (nv + vchunk - 1) / vchunk);
-    if ((rc = S.thist.fit((size_t)2 + nv)) || (rc = S.slots.fit((size_t)nchunks * std::max(k, 1))) || (rc = S.S.fit(std::max(k, 1))) ||
-        (rc = S.gpart.fit((size_t)nbc * m)) || (rc = S.out.fit((size_t)1 + n1)))
+    const ReformShards sh = reform_shards(n);   // n >= 1: last_cut_of
+    if ((rc = cut_pk_current(c, &PK, &k4)) || (rc = reform_prepare(c, 1, 1, nv)) || (rc = S.thist.fit((size_t)2 + nv)) ||
+        (rc = R.slots.fit((size_t)sh.nchunks * std::max(k, 1))) || (rc = R.f64.fit(std::max(k, 1))))
         return rc;
+    const double wunit = E.total_weight / kReformFix;
     TailParams P{};
-    P.n = n; P.k = k; P.k4 = k4; P.nv = nv; P.tpb = tpb; P.nchunks = nchunks;
-    P.has_add = c->has_bounds ? 1 : 0; P.add = c->c0; P.eta = eta; P.scale = kRiskFix / E.total_weight;
+    P.n = n; P.k = k; P.k4 = k4; P.nv = nv; P.tpb = sh.tpb; P.nchunks = sh.nchunks;
+    P.has_add = c->has_bounds ? 1 : 0; P.add = c->c0; P.eta = eta; P.scale = kReformFix / E.total_weight;
     P.dv = E.d_dv; P.w = E.d_w; P.PK = PK; P.val = cut_last_val(c); P.picks = cut_last_arg(c);
-    P.slots = S.slots;
+    P.slots = R.slots;
     HIPCHK(hipEventRecord(c->ev[EV_MARK_0], c->stream));
     HIPCHK(hipMemsetAsync(S.thist, 0, sizeof(unsigned long long) * ((size_t)2 + nv), c->stream));
     hipLaunchKernelGGL(risk_thist_kernel, dim3(risk_grid(c, n, 8192, 64), (nv + kRiskVW - 1) / kRiskVW), dim3(1024), 0, c->stream, P,
                        S.thist.p);
     if (k > 0) {
-        const dim3 rgrid(std::min(nchunks, risk_grid(c, n, 256, nchunks)));
+        const dim3 rgrid(std::min(sh.nchunks, risk_grid(c, n, 256, sh.nchunks)));
         if (k <= 64) hipLaunchKernelGGL(risk_treform_kernel<1>, rgrid, dim3(256), 0, c->stream, P);
         else hipLaunchKernelGGL(risk_treform_kernel<2>, rgrid, dim3(256), 0, c->stream, P);
-        hipLaunchKernelGGL(risk_tsum_kernel, dim3(1), dim3(128), 0, c->stream, nchunks, k, S.slots.p, S.S.p);
+        reform_sum_shards(c, false, sh.nchunks, k, R.slots.p, R.f64.p);   // plain shard order
     }
-    hipLaunchKernelGGL(risk_tg_kernel, dim3(std::min(nbc, risk_grid(c, nv, vchunk, nbc))), dim3(256), 0, c->stream, nv, m, vchunk, nbc,
-                       S.thist + 2, c->dvs.V, S.gpart.p);
-    hipLaunchKernelGGL(risk_tfinal_kernel, dim3(1), dim3(256), sizeof(double) * m, c->stream, m, n1, k, nbc, S.gpart.p, c->boot.d_r.p,
-                       c->boot.d_T.p, c->boot.d_col.p, S.S.p, S.thist.p, c->has_bounds ? c->c0 : 0.0, S.out.p);
-    HIPCHK(hipGetLastError());
-    std::vector<double> out((size_t)1 + n1);
+    // W_t is the one W word; the per-vertex weights follow the two totals (row 0: the stride is not read)
+    if ((rc = reform_finalize_block(c, 1, 1, 0, nv, nv, S.thist + 2, R.f64.p, S.thist.p, wunit))) return rc;
+    std::vector<double> out((size_t)2 + n1);   // one row: [alpha][weight_mark][beta], one copy
     unsigned long long tw[2] = {0, 0};
-    HIPCHK(hipMemcpyAsync(out.data(), S.out, sizeof(double) * out.size(), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipMemcpyAsync(out.data(), R.out, sizeof(double) * out.size(), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipMemcpyAsync(tw, S.thist, sizeof tw, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipEventRecord(c->ev[EV_MARK_1], c->stream));
     HIPCHK(hipEventSynchronize(c->ev[EV_MARK_1]));
@@ -569,8 +468,7 @@ extern "C" int twosd_cut_tail(twosd_ctx *c, int epi, double eta, double *alpha, 
     hipEventElapsedTime(&ms, c->ev[EV_MARK_0], c->ev[EV_MARK_1]);
     S.ms[1] = ms;
     *alpha = out[0];
-    for (int j = 0; j < n1; ++j) beta[j] = out[1 + j];
-    const double wunit = E.total_weight / kRiskFix;
+    for (int j = 0; j < n1; ++j) beta[j] = out[2 + j];
     if (tail_weight) *tail_weight = (double)tw[0] * wunit;
     if (total_weight) *total_weight = (double)tw[1] * wunit;
     return TWOSD_OK;

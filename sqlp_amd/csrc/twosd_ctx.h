@@ -58,18 +58,19 @@ struct PickSet {
     bool stale = false;           // the vertex set was truncated below nv since: unusable
 };
 
-// bootstrap re-formation (boot_kernel.hip): the pick handles, the template's device copies the
-// finalize kernel reads, and the workspaces of a call.  twosd_set_template and
-// twosd_set_random_positions assign a fresh one (every handle dropped).
-struct BootState {
+// cuts re-formed from stored picks (reform.hip; boot_kernel.hip's bootstrap and risk.hip's tail cut, synchronous on the
+// one stream): the pick handles, the template's device copies, and the workspaces and output rows of a call.
+// twosd_set_template and twosd_set_random_positions assign a fresh one (every handle dropped).
+struct ReformState {
     std::vector<PickSet> picks;
     bool tmpl_ready = false;
     DevBuf<double> d_T, d_r;      // dense T (m x n1), r (m)
     DevBuf<int> d_col;            // k: first-stage column of each random element, -1 for an rhs element
-    DevBuf<double> slots, gpart;  // the blocks' S partials of one handle; the vertex chunks' g partials
-    DevBuf<double> d_alpha, d_beta, d_wm;   // outputs of a call, (M + 1) x H rows
+    DevBuf<double> slots, gpart;  // the shards' S partials of one handle; the vertex chunks' g partials
+    DevBuf<double> out;           // outputs of a call, rows = (M + 1) x H: [alpha][weight_mark][beta: rows x n1], one copy when small
+    double *d_alpha = nullptr, *d_wm = nullptr, *d_beta = nullptr;
     DevBuf<unsigned long long> u64;   // twosd_reform_cuts' own partial buffers (the split's are the caller's)
-    DevBuf<double> f64;
+    DevBuf<double> f64;               //   its S sums; the tail cut's too
     DevBuf<uint8_t> counts;
     double ms[2] = {0, 0};        // device time of the last twosd_reform_cuts: partial sums, finalize (with its copies)
 };
@@ -102,7 +103,7 @@ struct FrayState {
     double scan_us = 0.0;         // device time of the last twosd_feas_scan's scan and merge kernels
 };
 
-// risk measures (risk.hip): the workspaces of the quantile selection and of the tail cut, the
+// risk measures (risk.hip): the workspaces of the quantile selection, the tail cut's own, the
 // uploads of twosd_quantile_of_values and the objectives twosd_evaluate_cvar keeps on the device.
 // Grow-only scratch: nothing here outlives the call that filled it.
 struct RiskState {
@@ -112,8 +113,7 @@ struct RiskState {
     DevBuf<int> st;                   //   and statuses
     DevBuf<double> obj;               // evaluate_cvar: the whole range's objectives, overwritten by Y
     DevBuf<int> ost;                  //   and statuses
-    DevBuf<unsigned long long> thist; // tail cut: [0] W_t, [1] the total, [2 ..) the per-vertex weights
-    DevBuf<double> slots, S, gpart, out;   // tail cut: shard partials of S, S, g partials, [alpha, beta]
+    DevBuf<unsigned long long> thist; // tail cut: [0] W_t, [1] the total, [2 ..) the per-vertex weights (the rest: ReformState)
     double ms[2] = {0, 0};            // device time of the last selection / tail re-formation
 };
 
@@ -279,7 +279,7 @@ struct TemplateState {
     // the last twosd_build_cut / twosd_cut_partial whose picks still sit in the cut workspace:
     // its epigraph (-1: none, or invalidated since), scenarios (0: the empty-epigraph path), |V|
     int last_cut_epi = -1, last_cut_n = 0, last_cut_nv = 0;
-    twosd::BootState boot;        // stored picks and the re-formation's buffers (boot_kernel.hip)
+    twosd::ReformState reform;    // stored picks and the buffers of cuts re-formed from picks (reform.hip)
     // dual-vertex key workspace (vkey.hip) and the key output of the LP kernel
     std::unique_ptr<twosd::VkeyWs, void (*)(twosd::VkeyWs *)> vkey_ws{nullptr, twosd::vkey_free};
     twosd::DevBuf<unsigned long long> d_vkey, d_bkey;
@@ -414,8 +414,12 @@ int dvs_push_device(twosd_ctx *c, int count, const double *d_pis, int *d_out_ind
 // cut: what other subsystems call (cut_kernel.hip; what the cut's own files share is in cut_common.h)
 void cut_invalidate_pk(twosd_ctx *c);
 void cut_truncate_pk(twosd_ctx *c, int size);   // V truncated to size: PK rows past it are stale
-// for boot_kernel.hip: the picks of the last cut (device, last_cut_n ints), and PK (|V| x k4,
-// brought up to date with the vertex set)
+// The state rule of twosd_picks_keep, twosd_cut_quantile and twosd_cut_tail: a template, an existing
+// epigraph, and the last cut built on it with scenarios, its picks and scores still in the cut
+// workspace.  who: the caller's name; verb: what it does with the picks ("keep", "read").
+int cut_last_usable(twosd_ctx *c, int epi, const char *who, const char *verb);
+// for boot_kernel.hip and risk.hip: the picks of the last cut (device, last_cut_n ints), and PK
+// (|V| x k4, brought up to date with the vertex set)
 const int *cut_last_arg(twosd_ctx *c);
 int cut_pk_current(twosd_ctx *c, const double **PK, int *k4);
 // for risk.hip: the maximal scores of the last cut (device, last_cut_n doubles, the canonical LP's:

@@ -171,6 +171,16 @@ def test_replicates_around_one_tile(name, G, N):
     B.ctx.close()
 
 
+def test_replicates_past_eight_shards():
+    """lands in antithetic pairs at N = 2500: 10 shards, more than the eight summing segments."""
+    from sqlp_amd import twosd
+    B = _build("lands", [(0, 2500)])
+    E = B.epis[0]
+    got = twosd.reform_cuts(E.epi, [E.kept[0].h], 1, SEED, sampling=_plan(2))
+    _check(got, _ref_rows(B, E, 1, SEED, 0, 2), "lands G=2 N=2500 M=1")
+    B.ctx.close()
+
+
 # ---------------------------------------------------------------- 4. the group property
 @pytest.mark.parametrize("which", ["anti", "lhs3", "lhs256"])
 def test_total_weight_is_counts_times_group_weights(which):

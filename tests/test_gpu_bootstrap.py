@@ -5,7 +5,9 @@ rule end to end on lands.  The reference has no counterpart (plugin/stopping_rul
 Tolerance: the project's cut tolerance, 1e-8 relative to 1 + |reference| (tests/test_gpu_sd_loop.py).
 Shapes: N = 300 (no multiple of the 64-scenario tile, several tiles and waves), N in {1, 63, 64, 65}
 around one tile, k = 1 .. 120 (one and two elements per lane: the kernel's two instantiations),
-M in {1, 33, 64} (one replicate, a group of 16 with one member, four full groups)."""
+M in {1, 33, 64} (one replicate, a group of 16 with one member, four full groups), and lands at
+N = 2500: 40 tiles in 10 shards, more than the eight segments the shards' partials are summed in
+(sqlp_amd/csrc/reform_layout.h, reform.hip)."""
 from types import SimpleNamespace
 
 import numpy as np
@@ -205,6 +207,31 @@ def test_replicates_around_one_tile(name, N):
         _close(R.beta, b, f"{name} N={N} M={M} beta")
         _close(R.weight_mark, wm, f"{name} N={N} M={M} weight_mark")
         _close(R.total_weight, tw, f"{name} N={N} M={M} total_weight")
+    _close(R.alpha[0, 0], cut.alpha, "identity alpha")
+    ctx.close()
+
+
+def test_replicates_past_eight_shards():
+    """One handle over 2500 scenarios: 10 shards, so some of the eight segments add two."""
+    from sqlp_amd import twosd
+    N, M = 2500, 1
+    ctx, x, _ = _context("lands")
+    vals, w = I.sample("lands", N, 3), np.random.default_rng(9).uniform(0.5, 1.5, size=N)
+    r, T, c0 = _template_arrays(ctx)
+    V = twosd.sdDualVertexSet(ctx)
+    epi = twosd.sdEpigraph(ctx, 1.0, 0.0)
+    twosd.add_scenarios(epi, vals, w)
+    twosd.solve_push(epi, x, 0, N)
+    cut, _, ma = twosd._build_cut(epi, x, 0.0, want_argmax=True)
+    h = twosd.keep_picks_of_last_cut(epi)
+    B = SimpleNamespace(ctx=ctx, r=r, T=T, c0=c0, V=V)
+    E = SimpleNamespace(w=w, dv=vals - ctx.template_values, kept=[SimpleNamespace(arg=ma, n=N)])
+    R = twosd.reform_cuts(epi, [h], M, SEED)
+    a, b, wm, tw = _ref_rows(B, E, M, SEED, 0)
+    _close(R.alpha, a, f"lands N={N} M={M} alpha")
+    _close(R.beta, b, f"lands N={N} M={M} beta")
+    _close(R.weight_mark, wm, f"lands N={N} M={M} weight_mark")
+    _close(R.total_weight, tw, f"lands N={N} M={M} total_weight")
     _close(R.alpha[0, 0], cut.alpha, "identity alpha")
     ctx.close()
 

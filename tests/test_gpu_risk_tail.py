@@ -8,7 +8,9 @@ general bounds (a shifted and a boxed column: c0 != 0 and dual vectors longer th
 Tolerance: the project's cut tolerance 1e-8 (1 + |ref|), beta against its largest entry
 (tests/test_gpu_bootstrap._close).  The tail weight is compared bit for bit with the integer-scaled
 sum, which with these distinct random weights also pins the set of flagged scenarios.
-Sizes: N in {1, 63, 64, 65} around one 64-scenario tile, 300 with several tiles and waves."""
+Sizes: N in {1, 63, 64, 65} around one 64-scenario tile, 300 with several tiles and waves, and
+lands at 2500: 40 tiles in 10 shards, where the shard-order sum of S has more terms than the
+bootstrap's eight side-by-side segments (sqlp_amd/csrc/reform_layout.h, reform.hip)."""
 import contextlib
 import os
 import struct
@@ -114,11 +116,14 @@ def _context(name):
     return _CTX[name]
 
 
-def _cut(name, N, plant=False):
-    """A fresh epigraph of the first N scenarios with its cut at x: (B, epi, cut, max_val, max_arg)."""
+def _cut(name, N, plant=False, data=None):
+    """A fresh epigraph of the first N scenarios (of data = (values, weights) when given) with its cut
+    at x: (B, epi, cut, max_val, max_arg)."""
     from types import SimpleNamespace
     from sqlp_amd import twosd
     ctx, x, vals, w = _context(name)
+    if data is not None:
+        vals, w = data
     vals, w = vals[:N].copy(), w[:N].copy()
     if plant and N >= 2:
         vals[1] = vals[0]                                  # two identical scenarios: one score, twice
@@ -179,6 +184,15 @@ def test_tail_cut_matches_the_restatement(name, N):
     got = _check_tail(name, B, epi, mv, ma, float(mv[0]), f"{name} N={N} eta at the planted score")
     q = RR.int_weights(B.w, B.total)
     assert got.tail_weight == float(sum(qq for qq, v in zip(q, mv) if v > mv[0])) * (B.total / FIX)
+
+
+def test_tail_cut_past_eight_shards():
+    """N = 2500: the S sums are added over 10 shards in shard order (one segment; the bootstrap's eight
+    segments would add them in another order)."""
+    N = 2500
+    data = (I.sample("lands", N, 3), np.random.default_rng(22).uniform(0.5, 1.5, size=N))
+    B, epi, cut, mv, ma = _cut("lands", N, data=data)
+    _check_tail("lands", B, epi, mv, ma, float(np.sort(mv)[(7 * N) // 10]), f"lands N={N} eta at the 0.7 point")
 
 
 @pytest.mark.parametrize("N", [1, 65, 300])

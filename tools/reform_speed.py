@@ -16,6 +16,10 @@ sampling=: whole groups resampled) is timed on the same epigraph and handles bes
 the same way (warm-up, best of three, every repeat kept); the scenario count must be whole groups of
 each.  The epigraph's own stream stays the i.i.d. one: the work does not depend on the values.
 
+--tree PATH imports sqlp_amd from another checkout (its library built in-tree) instead of this one,
+as tools/risk_speed.py does: the parent commit's re-formation is then measured in the same job.
+reform_device_ms_runs keeps the two phases' device times of every repeat.
+
 Prints one JSON line.  --out also writes it to a file.
 """
 import argparse
@@ -27,7 +31,6 @@ import time
 import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
 
 HBM_PEAK_GBS = 8000.0     # MI355X HBM3E peak
 
@@ -66,15 +69,18 @@ def main():
     ap.add_argument("--replicates", type=int, default=32)
     ap.add_argument("--seed", type=int, default=20250219)
     ap.add_argument("--sampling", default="", help="comma-separated plans to time beside the i.i.d. call: antithetic, lhs64, ...")
+    ap.add_argument("--tree", default=ROOT)
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
+    tree = os.path.abspath(args.tree)
+    sys.path.insert(0, tree)
     import torch
     torch.cuda.init()
     from sqlp_amd import smps, twosd
     name = args.instance
-    cor, tim, sto = smps.load_smps(os.path.join(ROOT, "data", "smps", name), name)
+    cor, tim, sto = smps.load_smps(os.path.join(tree, "data", "smps", name), name)
     sp2 = smps.get_smps_stage_template(cor, tim, 2)
-    with open(os.path.join(ROOT, "tests", "golden", "ev_x.json")) as f:
+    with open(os.path.join(tree, "tests", "golden", "ev_x.json")) as f:
         x = np.array(json.load(f)[name]["x"])
     ctx = twosd.SDContext(sp2, sto)
     ctx.compute_basis(x, smps.mean_values(sto))
@@ -100,7 +106,13 @@ def main():
     cut_ms = best_of(lambda: twosd.build_sasa_cut(epi, x, V, tie_rel=1e-12))
     cut_kernel_ms = float(ctx.timings_us()[2] + ctx.timings_us()[3]) / 1e3
     one_ms = best_of(lambda: twosd.reform_cuts(epi, cuts[:1], M, args.seed))
-    all_runs = runs_of(lambda: twosd.reform_cuts(epi, cuts, M, args.seed))
+    dev_runs = []
+
+    def all_handles():
+        twosd.reform_cuts(epi, cuts, M, args.seed)
+        dev_runs.append([float(v) for v in twosd.reform_last_ms(ctx)])
+    all_runs = runs_of(all_handles)
+    dev_runs = dev_runs[1:]     # without the warm-up
     all_ms = min(all_runs)
     id_ms = best_of(lambda: twosd.reform_cuts(epi, cuts, 0, args.seed))
     R = twosd.reform_cuts(epi, cuts, M, args.seed)
@@ -113,9 +125,9 @@ def main():
                       "over_iid": min(runs) / all_ms}
     k = ctx.k
     model = H * N * (8 * k + 12)
-    out = {"instance": name, "scenarios": N, "vertices": len(V), "k": k, "handles": H, "replicates": M,
+    out = {"instance": name, "tree": os.path.relpath(tree, ROOT), "scenarios": N, "vertices": len(V), "k": k, "handles": H, "replicates": M,
            "build_cut_ms": cut_ms, "build_cut_kernels_ms": cut_kernel_ms,
-           "reform_ms": all_ms, "reform_ms_runs": all_runs, "reform_device_ms": dev_ms, "reform_ms_per_handle": all_ms / H, "reform_one_handle_ms": one_ms,
+           "reform_ms": all_ms, "reform_ms_runs": all_runs, "reform_device_ms": dev_ms, "reform_device_ms_runs": dev_runs, "reform_ms_per_handle": all_ms / H, "reform_one_handle_ms": one_ms,
            "reform_identity_only_ms": id_ms,
            "model_bytes": model, "achieved_GBs": model / (all_ms * 1e-3) / 1e9,
            "fraction_of_hbm_peak": model / (all_ms * 1e-3) / 1e9 / HBM_PEAK_GBS,
