@@ -759,6 +759,41 @@ int twosd_cut_tail(twosd_ctx *ctx, int epi, double eta, double *alpha, double *b
                    double *total_weight);
 int twosd_risk_last_ms(twosd_ctx *ctx, double *ms2);
 
+/*
+ * Tail handles: the tail of the last cut of epi at eta as a compact list, so that a tail row can be
+ * re-formed under resampled weights (the stopping rule of the mean-CVaR loop).  With its tail set
+ * and picks fixed a tail row is linear in the scenario weights, as a mean cut is; at the (x, eta) it
+ * was built at the re-formed row is the replicate's own E_b[(h - eta)+] (the set {h_s > eta} does
+ * not depend on the weights), and a fixed set bounds it from below everywhere else.
+ *   tail_keep: the nt scenarios s of the cut with f_s = 1[(val[s] + c0) > eta] -- twosd_cut_tail's
+ *     flag bit for bit, the set it sums over -- in ascending order, and their picks.  State rule and
+ *     refusals of twosd_cut_tail (TWOSD_E_ARG for a NaN eta, TWOSD_E_UNSUPPORTED for k > 127).  The
+ *     list is compacted on the device (per 64-scenario tile a ballot of the flags, an exclusive scan
+ *     of the tiles' counts, a scatter by offset plus lane rank: the same under any grid); no score or
+ *     pick leaves the device, nt alone is copied to size the arrays.  A handle costs 8 bytes per TAIL
+ *     scenario.  nt = 0 (eta at or above every score) is a valid handle.
+ *   tail_info: the cut's (epi, n, nv), nt and eta (each nullable); tail_get: scen[nt], pick[nt].
+ *   tail_last_ms: device time of the last twosd_tail_keep (HIP events, milliseconds).
+ * Tail handles live in the pick handles' table: twosd_picks_info reports (epi, n, nv) of the cut,
+ * twosd_picks_release and twosd_picks_count cover them, the calls that drop or disable pick handles
+ * do the same to them; twosd_picks_get refuses one (TWOSD_E_ARG: use twosd_tail_get) and the tail_
+ * calls refuse a pick handle.
+ *
+ * twosd_reform_cuts, _partial, _partial_len, _finalize and their _vr forms take tail handles mixed
+ * freely with pick handles of the same epigraph.  For a tail handle j the counts are c_b(s) f_s:
+ *     W_jb = sum_{i < nt} c_b(scen_i) w_{scen_i},  alpha, beta: the formula above over the list,
+ *     weight_mark = W_jb;   W_jb = 0 or nt = 0: the zero cut with weight_mark 0
+ * -- the count of an entry is that of its scenario's global index index_offset + scen_i (of its group
+ * under a plan), so the row is the one a pick handle with -1 outside the tail would give.  Only the
+ * tail's deltas are read: three kernels over the list, shards = those of nt entries, summed as every
+ * handle's (the same bits on every run, and for H handles in one call as in H calls); nothing is
+ * launched over an empty list.  The handle's words of the partial buffers stay what they are.
+ */
+int twosd_tail_keep(twosd_ctx *ctx, int epi, double eta, int *handle);
+int twosd_tail_info(twosd_ctx *ctx, int handle, int *epi, int *n, int *nv, int *nt, double *eta);
+int twosd_tail_get(twosd_ctx *ctx, int handle, int *scen, int *pick);
+int twosd_tail_last_ms(twosd_ctx *ctx, double *ms);
+
 /* Out-of-sample CVaR of the stage-2 objective at x over scenarios [first, first + count) of the
  * i.i.d. device stream `seed` (1 <= count <= 2^27; TWOSD_E_UNSUPPORTED beyond): sampled and solved
  * in the chunks of twosd_evaluate_moments, the objectives and statuses of the whole range kept on

@@ -129,6 +129,10 @@ SIGNATURES = [
     ("twosd_cut_quantile", I, [P, I, D, P, P, P, P]),
     ("twosd_cut_tail", I, [P, I, D, P, P, P, P]),
     ("twosd_risk_last_ms", I, [P, P]),
+    ("twosd_tail_keep", I, [P, I, D, P]),
+    ("twosd_tail_info", I, [P, I, P, P, P, P, P]),
+    ("twosd_tail_get", I, [P, I, P, P]),
+    ("twosd_tail_last_ms", I, [P, P]),
     ("twosd_evaluate_cvar", I, [P, P, C.c_uint64, C.c_int64, C.c_int64, D, P]),
 ]
 

@@ -39,6 +39,13 @@
 //                        lanes = elements (e = lane, lane + 64) while the tile's scenarios go by one
 //                        at a time with wave-uniform picks and counts (v_readlane); 16 + 1
 //                        accumulators per element stay in VGPRs (KE = 2: 191 VGPRs, no scratch)
+//   boot_tweight_kernel, boot_thist_kernel, boot_treform_kernel<KE, GR>
+//                        the three above over a tail handle's compact list (twosd_tail_keep, risk.hip:
+//                        the nt scenarios of a cut scoring above eta, and their picks): the counts are
+//                        c_b(s) 1[s in the tail], a count still a function of the scenario's global
+//                        index (or group), and only the tail's rows of the deltas are read -- the shards
+//                        are reform_shards(nt) over the list.  Nothing is launched over an empty list
+//                        (the zero cut), and a call without tail handles launches what it always did.
 // then reform.hip's stage, shared with the tail cut of risk.hip: S from the shards' partials, g, and
 // alpha, beta per (handle, replicate) normalised by W_jb.  boot_hist_kernel and boot_reform_kernel
 // stay the bootstrap's own: do not merge them with risk.hip's look-alikes (reform.hip's header).
@@ -167,6 +174,81 @@ __global__ void __launch_bounds__(1024) boot_hist_kernel(int n, int nv, int nvs,
     }
 }
 
+// The tail handles' siblings of the two kernels above: the nt entries of a compact list (scen[i]
+// ascending scenario indices, picks[i] by list position) instead of the scenarios 0 .. n - 1.  The
+// weight and the count of entry i are those of scenario scen[i] -- the draw's index is the
+// scenario's (or its group's), never the list position -- so a row is the one a pick handle with
+// -1 outside the list would give.  Integer sums, as above.
+template <bool GR>
+__global__ void __launch_bounds__(256) boot_tweight_kernel(int nt, const int *__restrict__ scen, const double *__restrict__ w,
+                                                           double scale, int M, unsigned long long seed, unsigned long long off,
+                                                           unsigned long long *__restrict__ out, unsigned G) {
+    __shared__ unsigned long long sh[4][4];
+    const int nq = (M + 3) / 4, Q = blockIdx.y;
+    unsigned long long a[4] = {0ull, 0ull, 0ull, 0ull};
+    for (int i = blockIdx.x * 256 + threadIdx.x; i < nt; i += gridDim.x * 256) {
+        const int s = scen[i];
+        const unsigned long long q = reform_q(w[s], scale);
+        if (Q == nq) { a[0] += q; continue; }
+        const Philox4 r = boot_words(boot_index<GR>(off, s, G), Q, seed);
+#pragma unroll
+        for (int t = 0; t < 4; ++t) a[t] += (unsigned long long)boot_count_of_word(r.v[t]) * q;
+    }
+#pragma unroll
+    for (int t = 0; t < 4; ++t)
+        for (int o = 32; o > 0; o >>= 1) a[t] += __shfl_xor(a[t], o);
+    if ((threadIdx.x & 63) == 0)
+        for (int t = 0; t < 4; ++t) sh[threadIdx.x >> 6][t] = a[t];
+    __syncthreads();
+    if (threadIdx.x >= 4) return;
+    const int t = threadIdx.x;
+    const unsigned long long v = sh[0][t] + sh[1][t] + sh[2][t] + sh[3][t];
+    if (!v) return;
+    if (Q == nq) {
+        if (t == 0) atomicAdd(&out[0], v);
+    } else if (4 * Q + t < M) {
+        atomicAdd(&out[1 + 4 * Q + t], v);
+    }
+}
+
+template <bool GR>
+__global__ void __launch_bounds__(1024) boot_thist_kernel(int nt, int nv, int nvs, int M, const int *__restrict__ scen,
+                                                          const int *__restrict__ picks, const double *__restrict__ w, double scale,
+                                                          unsigned long long seed, unsigned long long off,
+                                                          unsigned long long *__restrict__ hist, unsigned G) {
+    __shared__ unsigned long long hl[4 * kBootVW];
+    const int nq = (M + 3) / 4, Q = blockIdx.y;
+    const int v0 = blockIdx.z * kBootVW, v1 = min(nv, v0 + kBootVW);
+    for (int i = threadIdx.x; i < 4 * kBootVW; i += 1024) hl[i] = 0ull;
+    __syncthreads();
+    for (int i = blockIdx.x * 1024 + threadIdx.x; i < nt; i += gridDim.x * 1024) {
+        const int pick = picks[i];
+        if (pick < v0 || pick >= v1) continue;
+        const int s = scen[i];
+        const unsigned long long q = reform_q(w[s], scale);
+        if (!q) continue;
+        if (Q == nq) {
+            __hip_atomic_fetch_add(&hl[pick - v0], q, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+            continue;
+        }
+        const Philox4 r = boot_words(boot_index<GR>(off, s, G), Q, seed);
+#pragma unroll
+        for (int t = 0; t < 4; ++t) {
+            const int cnt = (4 * Q + t < M) ? boot_count_of_word(r.v[t]) : 0;
+            if (cnt)
+                __hip_atomic_fetch_add(&hl[t * kBootVW + pick - v0], (unsigned long long)cnt * q, __ATOMIC_RELAXED,
+                                       __HIP_MEMORY_SCOPE_WORKGROUP);
+        }
+    }
+    __syncthreads();
+    for (int i = threadIdx.x; i < 4 * kBootVW; i += 1024) {
+        const unsigned long long h = hl[i];
+        if (!h) continue;
+        const int row = Q == nq ? 0 : 1 + 4 * Q + i / kBootVW;
+        atomicAdd(&hist[(size_t)row * nvs + v0 + i % kBootVW], h);
+    }
+}
+
 struct BootParams {
     int n, k, k4, nv, M, ngroups, tpb;   // tpb: 64-scenario tiles per block
     int G;                               // sampling group (grouped kernels; off then counts groups)
@@ -175,6 +257,7 @@ struct BootParams {
     const double *dv, *w, *PK;
     const int *picks;
     double *slots;                       // nchunks x (M + 1) x k
+    const int *scen;                     // boot_treform_kernel: n is the list's length, picks go by list position
 };
 
 // KE: elements per lane (k <= 64 KE).  GM: whose count a scenario carries --
@@ -308,13 +391,137 @@ __global__ void __launch_bounds__(256) boot_reform_kernel(BootParams P) {
     }
 }
 
+// boot_reform_kernel's sibling over a tail handle's compact list (P.n entries, P.scen, P.picks by
+// list position): lanes = the 64 list entries of a tile for the draws -- each lane the Philox words of
+// its own scenario (GR: of its scenario's group; a tile of the list straddles groups whatever G is, so
+// there is no tile-uniform form) -- then lanes = elements while the tile's entries go by four at a
+// time, the rows dv[scen_i] and PK[pick_i] of the next four in flight.  Only the list's rows of dv are
+// read.  The shards are reform_shards(nt) over the list: the same bits on every run.  A sibling, not
+// an instantiation: reform.hip's header.
+template <int KE, bool GR>
+__global__ void __launch_bounds__(256) boot_treform_kernel(BootParams P) {
+    __shared__ double comb[(kBootGroup + 1) * KE * 64];
+    const int lane = threadIdx.x & 63;
+    const int wid = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int grp = blockIdx.x % P.ngroups, chunk = blockIdx.x / P.ngroups;
+    const int ntiles = (P.n + 63) >> 6;
+    const int t0 = chunk * P.tpb, t1 = min(ntiles, t0 + P.tpb);
+    int ec[KE];                       // this lane's elements, clamped to k - 1
+#pragma unroll
+    for (int u = 0; u < KE; ++u) ec[u] = min(lane + 64 * u, P.k - 1);
+    double acc[kBootGroup + 1][KE];
+#pragma unroll
+    for (int r = 0; r <= kBootGroup; ++r)
+#pragma unroll
+        for (int u = 0; u < KE; ++u) acc[r][u] = 0.0;
+
+    for (int t = t0 + wid; t < t1; t += 4) {
+        // lanes = the tile's list entries
+        const int li = t * 64 + lane;
+        const bool valid = li < P.n;
+        const int s = valid ? P.scen[li] : 0;
+        const int pick = valid ? P.picks[li] : -1;
+        const bool ok = pick >= 0 && pick < P.nv;
+        const unsigned long long q = ok ? reform_q(P.w[s], P.scale) : 0ull;
+        unsigned chi[kBootGroup];                           // high word of (double)count: 0 for count 0
+#pragma unroll
+        for (int qd = 0; qd < kBootGroup / 4; ++qd) {
+            const int Q = grp * (kBootGroup / 4) + qd;
+            Philox4 r;
+            r.v[0] = r.v[1] = r.v[2] = r.v[3] = 0u;
+            if (4 * Q < P.M) r = boot_words(boot_index<GR>(P.off, s, (unsigned)P.G), Q, P.seed);   // wave-uniform
+#pragma unroll
+            for (int tt = 0; tt < 4; ++tt) {
+                const int cnt = (4 * Q + tt < P.M) ? boot_count_of_word(r.v[tt]) : 0;
+                chi[4 * qd + tt] = (unsigned)__double2hiint((double)cnt);
+            }
+        }
+        const double qf = (double)q;
+        const int qlo = __double2loint(qf), qhi = __double2hiint(qf);
+        const int pk0 = ok ? pick : 0;
+        // lanes = elements; a lane past k reads element k - 1 again and its sums are never stored; a
+        // step past the tile's last entry reads that entry again with weight 0
+        const int nvalid = min(64, P.n - t * 64);
+        auto load4 = [&](int i0, double (&d)[4][KE], double (&p)[4][KE]) {
+#pragma unroll
+            for (int u4 = 0; u4 < 4; ++u4) {
+                const int i = min(i0 + u4, nvalid - 1);
+                const int pv = __builtin_amdgcn_readlane(pk0, i);
+                const int sv = __builtin_amdgcn_readlane(s, i);
+#pragma unroll
+                for (int u = 0; u < KE; ++u) {
+                    d[u4][u] = P.dv[(size_t)sv * P.k + ec[u]];
+                    p[u4][u] = P.PK[(size_t)pv * P.k4 + ec[u]];
+                }
+            }
+        };
+        auto work4 = [&](int i0, const double (&d)[4][KE], const double (&p)[4][KE]) {
+#pragma unroll
+            for (int u4 = 0; u4 < 4; ++u4) {
+                const int i = min(i0 + u4, 63);
+                const double wq = i0 + u4 < nvalid ? __hiloint2double(__builtin_amdgcn_readlane(qhi, i), __builtin_amdgcn_readlane(qlo, i)) : 0.0;
+                double term[KE];
+#pragma unroll
+                for (int u = 0; u < KE; ++u) term[u] = wq * p[u4][u] * d[u4][u];
+#pragma unroll
+                for (int r = 0; r < kBootGroup; ++r) {
+                    const double cd = __hiloint2double(__builtin_amdgcn_readlane((int)chi[r], i), 0);   // wave-uniform count
+#pragma unroll
+                    for (int u = 0; u < KE; ++u) acc[r][u] = fma(cd, term[u], acc[r][u]);
+                }
+#pragma unroll
+                for (int u = 0; u < KE; ++u) acc[kBootGroup][u] += term[u];
+            }
+        };
+        double da[4][KE], pa[4][KE], db[4][KE], pb[4][KE];
+        load4(0, da, pa);
+        for (int i0 = 0; i0 < nvalid; i0 += 8) {
+            if (i0 + 4 < nvalid) load4(i0 + 4, db, pb);
+            work4(i0, da, pa);
+            if (i0 + 4 >= nvalid) break;
+            if (i0 + 8 < nvalid) load4(i0 + 8, da, pa);
+            work4(i0 + 4, db, pb);
+        }
+    }
+    // the block's four waves combined in wave order
+    for (int wv = 0; wv < 4; ++wv) {
+        if (wid == wv) {
+#pragma unroll
+            for (int r = 0; r <= kBootGroup; ++r)
+#pragma unroll
+                for (int u = 0; u < KE; ++u) {
+                    double &d = comb[(r * KE + u) * 64 + lane];
+                    d = wv == 0 ? acc[r][u] : d + acc[r][u];
+                }
+        }
+        __syncthreads();
+    }
+    const int B = P.M + 1;
+    double *out = P.slots + (size_t)chunk * B * P.k;
+    for (int idx = threadIdx.x; idx < (kBootGroup + 1) * KE * 64; idx += 256) {
+        const int r = idx / (KE * 64), e = idx % (KE * 64);
+        const int row = r == kBootGroup ? (grp == 0 ? 0 : -1) : 1 + grp * kBootGroup + r;
+        if (row >= 0 && row < B && e < P.k) out[(size_t)row * P.k + e] = comb[idx];
+    }
+}
+
 static PickSet *pick_of(twosd_ctx *c, int handle) {
     if (handle < 0 || handle >= (int)c->reform.picks.size() || !c->reform.picks[handle].live) return nullptr;
     return &c->reform.picks[handle];
 }
 
+// the first slot of the handle table that is not live (a new one at its end): the caller fills it
+PickSet *pick_slot(twosd_ctx *c, int *id) {
+    std::vector<PickSet> &v = c->reform.picks;
+    int i = 0;
+    while (i < (int)v.size() && v[i].live) ++i;
+    if (i == (int)v.size()) v.emplace_back();
+    *id = i;
+    return &v[i];
+}
+
 // a usable handle, or the error code with its message
-static int usable_pick(twosd_ctx *c, int handle, const char *what, PickSet **out) {
+int usable_pick(twosd_ctx *c, int handle, const char *what, PickSet **out) {
     PickSet *h = pick_of(c, handle);
     if (!h)
         return fail(TWOSD_E_ARG, "%s: pick handle %d does not exist (released, or dropped by twosd_set_template / "
@@ -373,11 +580,53 @@ static int boot_partial_impl(twosd_ctx *c, int epi, const BootLayout &L, const i
         const PickSet &h = c->reform.picks[handles[j]];
         if (h.n > E.count)
             return fail(TWOSD_E_STATE, "reform: pick handle %d holds %d scenarios, epigraph %d only %d", handles[j], h.n, epi, E.count);
-        slots_need = std::max(slots_need, (size_t)reform_shards(h.n).nchunks * B * k);   // h.n >= 1: picks_keep
+        if (h.entries() > 0)   // a pick handle's n >= 1 (picks_keep); an empty tail launches nothing
+            slots_need = std::max(slots_need, (size_t)reform_shards(h.entries()).nchunks * B * k);
     }
     if ((rc = c->reform.slots.fit(slots_need))) return rc;   // once, before the first launch that writes it
     for (int j = 0; j < L.H; ++j) {
         const PickSet &h = c->reform.picks[handles[j]];
+        if (h.is_tail()) {
+            // the handle's words of the layout from its compact list: the weight, histogram and S
+            // kernels' siblings over nt entries (nothing outside the tail is read)
+            const int nt = h.nt;
+            double *Sj = d_f64 + (size_t)j * B * k;
+            if (nt == 0) {   // no launch over an empty list: W and the histogram rows stay 0, S is set to 0 -- the zero cut
+                if (k > 0) HIPCHK(hipMemsetAsync(Sj, 0, sizeof(double) * (size_t)B * k, c->stream));
+                continue;
+            }
+            const dim3 wgrid(std::max(1, std::min((nt + 8191) / 8192, 32)), nq + 1);
+            const dim3 hgrid(std::max(1, std::min((nt + 8191) / 8192, 64)), nq + 1, (h.nv + kBootVW - 1) / kBootVW);
+            unsigned long long *Wj = d_u64 + L.o_wj + (size_t)j * B, *Hj = d_u64 + L.o_hist + (size_t)j * B * L.nvs;
+            if (G == 1) {
+                hipLaunchKernelGGL(boot_tweight_kernel<false>, wgrid, dim3(256), 0, c->stream, nt, h.scen.p, E.d_w.p, scale, M, seed, off,
+                                   Wj, 1u);
+                hipLaunchKernelGGL(boot_thist_kernel<false>, hgrid, dim3(1024), 0, c->stream, nt, h.nv, L.nvs, M, h.scen.p, h.d.p,
+                                   E.d_w.p, scale, seed, off, Hj, 1u);
+            } else {
+                hipLaunchKernelGGL(boot_tweight_kernel<true>, wgrid, dim3(256), 0, c->stream, nt, h.scen.p, E.d_w.p, scale, M, seed, off,
+                                   Wj, (unsigned)G);
+                hipLaunchKernelGGL(boot_thist_kernel<true>, hgrid, dim3(1024), 0, c->stream, nt, h.nv, L.nvs, M, h.scen.p, h.d.p,
+                                   E.d_w.p, scale, seed, off, Hj, (unsigned)G);
+            }
+            if (k == 0) continue;
+            const ReformShards sh = reform_shards(nt);
+            BootParams P{};
+            P.n = nt; P.k = k; P.k4 = k4; P.nv = h.nv; P.M = M; P.ngroups = ngroups; P.tpb = sh.tpb; P.G = G;
+            P.scale = scale; P.seed = seed; P.off = off;
+            P.dv = E.d_dv; P.w = E.d_w; P.PK = PK; P.picks = h.d; P.scen = h.scen;
+            P.slots = c->reform.slots;
+            const dim3 rgrid(sh.nchunks * ngroups);
+            if (G == 1) {
+                if (k <= 64) hipLaunchKernelGGL((boot_treform_kernel<1, false>), rgrid, dim3(256), 0, c->stream, P);
+                else hipLaunchKernelGGL((boot_treform_kernel<2, false>), rgrid, dim3(256), 0, c->stream, P);
+            } else {
+                if (k <= 64) hipLaunchKernelGGL((boot_treform_kernel<1, true>), rgrid, dim3(256), 0, c->stream, P);
+                else hipLaunchKernelGGL((boot_treform_kernel<2, true>), rgrid, dim3(256), 0, c->stream, P);
+            }
+            reform_sum_shards(c, true, sh.nchunks, B * k, c->reform.slots.p, Sj);
+            continue;
+        }
         weights(h.n, d_u64 + L.o_wj + (size_t)j * B);
         const dim3 hgrid(std::max(1, std::min((h.n + 8191) / 8192, 64)), nq + 1, (h.nv + kBootVW - 1) / kBootVW);
         if (G == 1)
@@ -487,11 +736,8 @@ extern "C" int twosd_picks_keep(twosd_ctx *c, int epi, int *handle) {
     int rc = cut_last_usable(c, epi, "picks_keep", "keep");
     if (rc) return rc;
     HIPCHK(hipSetDevice(c->device));
-    std::vector<PickSet> &v = c->reform.picks;
     int id = 0;
-    while (id < (int)v.size() && v[id].live) ++id;
-    if (id == (int)v.size()) v.emplace_back();
-    PickSet &h = v[id];
+    PickSet &h = *pick_slot(c, &id);
     if ((rc = h.d.alloc(c->last_cut_n))) return rc;
     HIPCHK(hipMemcpyAsync(h.d, cut_last_arg(c), sizeof(int) * c->last_cut_n, hipMemcpyDeviceToDevice, c->stream));
     h.epi = epi; h.n = c->last_cut_n; h.nv = c->last_cut_nv; h.live = true; h.stale = false;
@@ -515,6 +761,9 @@ extern "C" int twosd_picks_get(twosd_ctx *c, int handle, int *out) {
     PickSet *h = nullptr;
     int rc = usable_pick(c, handle, "picks_get", &h);
     if (rc) return rc;
+    if (h->is_tail())
+        return fail(TWOSD_E_ARG, "picks_get: handle %d is a tail handle (%d of %d scenarios): read it with twosd_tail_get", handle,
+                    h->nt, h->n);
     HIPCHK(hipSetDevice(c->device));
     HIPCHK(hipMemcpyAsync(out, h->d, sizeof(int) * h->n, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));

@@ -12,6 +12,10 @@ __device__ __forceinline__ unsigned long long reform_q(double w, double scale) {
 }
 
 #pragma GCC visibility push(hidden)
+// The handle table (boot_kernel.hip; risk.hip's tail handles share it): a free slot of it, made live by
+// the caller; and a usable handle, or the error code with its message (what: the caller's name)
+PickSet *pick_slot(twosd_ctx *c, int *id);
+int usable_pick(twosd_ctx *c, int handle, const char *what, PickSet **out);
 // Before the first reform_finalize_block of a call: the template's device copies (once per
 // template) and room in ReformState for B x H output rows and the g partials over nvs vertices.
 int reform_prepare(twosd_ctx *c, int B, int H, int nvs);

@@ -4,8 +4,9 @@
 // with per-vertex integer weights, shard partials of S and a total weight W per row; S, g and the
 // normalised cut are formed here, in reform_layout.h's layouts.  No floating-point atomics.
 //
-// Not here, on purpose: the streaming kernels boot_reform_kernel<KE, GM> and risk_treform_kernel<KE>
-// and the histogram kernels boot_hist_kernel and risk_thist_kernel.  Their bodies look alike and are
+// Not here, on purpose: the streaming kernels boot_reform_kernel<KE, GM>, its sibling over a tail
+// handle's list boot_treform_kernel<KE, GR> and risk_treform_kernel<KE>, and the histogram kernels
+// boot_hist_kernel, boot_thist_kernel and risk_thist_kernel.  Their bodies look alike and are
 // not to be merged or templated over a count source: the tail kernel never loads the row of a
 // scenario outside the tail, the bootstrap kernel holds 17 accumulators per element at 191 VGPRs,
 // and how the compiler contracts wq * PK * dv + acc in a merged body -- every bit of both results

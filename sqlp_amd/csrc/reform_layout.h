@@ -14,6 +14,8 @@ constexpr double kReformFix = 288230376151711744.0;
 // The S sums of n scenarios are formed per shard of tpb 64-scenario tiles, nchunks shards in all: at
 // most four tiles per shard until that makes more than 512 shards, then 512 or fewer equal ones.  A
 // function of n alone.  Precondition: n >= 1 (a pick set and a last cut with picks hold a scenario).
+// A tail handle's S sums are sharded over its compact list: n = nt list entries, in tiles of 64
+// entries; an empty list (nt = 0) has no shards and is never passed here.
 constexpr int kReformMaxChunks = 512;
 struct ReformShards { int tpb, nchunks; };
 inline ReformShards reform_shards(int n) {
@@ -33,6 +35,7 @@ inline ReformVertexChunks reform_vertex_chunks(int nv) {
 
 // the partial buffers of H handles with B = M + 1 rows (row 0: the identity replicate) --
 //   u64: [B totals][H x B W_jb][H x B x nvs per-vertex weights]     f64: H x B x k S sums (at least 1)
+// a tail handle's words are a pick handle's: its W word the tail's weight, its histogram rows, its S sums
 struct BootLayout {
     int H, B, nvs, k;
     size_t o_wj, o_hist, n_u64, n_f64;

@@ -31,6 +31,16 @@
 // then reform.hip's stage, one handle and one row: S_e = the shards' partials in shard order (not the
 // bootstrap's eight segments), g, and alpha, beta normalised by W_t (W_t = 0: the zero cut).  The two
 // kernels above stay the tail's own: no merging with boot_kernel.hip's look-alikes (reform.hip's header).
+//
+// Tail handles (twosd_tail_keep).  The set the tail cut sums over -- the scenarios with
+// tail_flag, bit for bit -- as a compact list in the pick handles' table (ReformState::picks), so
+// that boot_kernel.hip can re-form the tail row under resampled weights reading the tail's deltas
+// only.  Compaction on the device, order-preserving and the same under any grid:
+//   risk_tcount_kernel    a wave per 64-scenario tile: one ballot of the flags, the tile's count
+//   risk_tscan_kernel     one block: the exclusive scan of the tiles' counts, nt behind the last
+//   risk_tscatter_kernel  (scenario, pick) at the tile's offset plus the lane's rank in the ballot
+// nt is the one value copied to the host (it sizes the handle's two arrays: 8 bytes per tail scenario).
+//
 // No floating-point atomics anywhere; TWOSD_RISK_BLOCKS (test knob) sets the grids and must not
 // change a bit of any result.
 #include <hip/hip_runtime.h>
@@ -347,6 +357,68 @@ __global__ void __launch_bounds__(256) risk_treform_kernel(TailParams P) {
     }
 }
 
+// ---- tail handles: the tail of the last cut as a compact list ---------------------------------
+// Order-preserving compaction, the same under any grid: a wave takes 64-scenario tiles; the tile's
+// flags are one ballot.  Pass 1 writes the tiles' counts, one block scans them (exclusive; the total
+// behind the last), pass 2 writes (scenario, pick) at the tile's offset plus the lane's rank among
+// the flagged lanes below it.
+struct TailKeep {
+    int n, has_add;
+    double eta, add;
+    const double *val;
+    const int *picks;
+};
+
+__device__ __forceinline__ bool keep_flag(const TailKeep &P, int s) {   // tail_flag, bit for bit
+    const double v = P.val[s];
+    return (P.has_add ? __dadd_rn(v, P.add) : v) > P.eta;
+}
+
+__global__ void __launch_bounds__(256) risk_tcount_kernel(TailKeep P, int *__restrict__ cnt) {
+    const int lane = threadIdx.x & 63;
+    const int ntiles = (P.n + 63) >> 6;
+    for (int t = blockIdx.x * 4 + (threadIdx.x >> 6); t < ntiles; t += gridDim.x * 4) {
+        const int s = t * 64 + lane;
+        const unsigned long long m = __ballot(s < P.n && keep_flag(P, s));
+        if (lane == 0) cnt[t] = __popcll(m);
+    }
+}
+
+// one block: cnt[t] <- sum_{u < t} cnt[u] for t < ntiles, cnt[ntiles] <- the total.  A thread owns a
+// run of consecutive tiles; the 1024 runs' sums are scanned by thread 0.
+__global__ void __launch_bounds__(1024) risk_tscan_kernel(int ntiles, int *__restrict__ cnt) {
+    __shared__ int run[1024];
+    const int per = (ntiles + 1023) / 1024;
+    const int a = min(ntiles, (int)threadIdx.x * per), b = min(ntiles, a + per);
+    int sum = 0;
+    for (int t = a; t < b; ++t) sum += cnt[t];
+    run[threadIdx.x] = sum;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        int acc = 0;
+        for (int i = 0; i < 1024; ++i) { const int v = run[i]; run[i] = acc; acc += v; }
+        cnt[ntiles] = acc;
+    }
+    __syncthreads();
+    int off = run[threadIdx.x];
+    for (int t = a; t < b; ++t) { const int v = cnt[t]; cnt[t] = off; off += v; }
+}
+
+__global__ void __launch_bounds__(256) risk_tscatter_kernel(TailKeep P, const int *__restrict__ offs, int *__restrict__ scen,
+                                                            int *__restrict__ pick) {
+    const int lane = threadIdx.x & 63;
+    const int ntiles = (P.n + 63) >> 6;
+    for (int t = blockIdx.x * 4 + (threadIdx.x >> 6); t < ntiles; t += gridDim.x * 4) {
+        const int s = t * 64 + lane;
+        const bool f = s < P.n && keep_flag(P, s);
+        const unsigned long long m = __ballot(f);
+        if (!f) continue;
+        const int o = offs[t] + __popcll(m & ((1ull << lane) - 1ull));
+        scen[o] = s;
+        pick[o] = P.picks[s];
+    }
+}
+
 // the last cut's state rule, and the two checks of a reader of the epigraph's weights
 static int last_cut_of(twosd_ctx *c, int epi, const char *who) {
     if (int rc = cut_last_usable(c, epi, who, "read")) return rc;
@@ -471,6 +543,89 @@ extern "C" int twosd_cut_tail(twosd_ctx *c, int epi, double eta, double *alpha, 
     for (int j = 0; j < n1; ++j) beta[j] = out[2 + j];
     if (tail_weight) *tail_weight = (double)tw[0] * wunit;
     if (total_weight) *total_weight = (double)tw[1] * wunit;
+    return TWOSD_OK;
+}
+
+extern "C" int twosd_tail_keep(twosd_ctx *c, int epi, double eta, int *handle) {
+    if (c && c->has_template && c->k > 127)   // as twosd_cut_tail: no cut of such a template exists
+        return fail(TWOSD_E_UNSUPPORTED, "k = %d random elements exceeds the cut kernel envelope (127)", c->k);
+    int rc = last_cut_of(c, epi, "tail_keep");
+    if (rc) return rc;
+    if (!handle) return fail(TWOSD_E_ARG, "tail_keep: handle is NULL");
+    if (std::isnan(eta)) return fail(TWOSD_E_ARG, "tail_keep: eta is NaN");
+    HIPCHK(hipSetDevice(c->device));
+    RiskState &S = c->risk;
+    const int n = c->last_cut_n, ntiles = (n + 63) >> 6;
+    if ((rc = S.tcnt.fit((size_t)ntiles + 1))) return rc;
+    TailKeep P{};
+    P.n = n; P.has_add = c->has_bounds ? 1 : 0; P.add = c->c0; P.eta = eta;
+    P.val = cut_last_val(c); P.picks = cut_last_arg(c);
+    const dim3 grid(risk_grid(c, n, 256, 0));
+    HIPCHK(hipEventRecord(c->ev[EV_MARK_0], c->stream));
+    hipLaunchKernelGGL(risk_tcount_kernel, grid, dim3(256), 0, c->stream, P, S.tcnt.p);
+    hipLaunchKernelGGL(risk_tscan_kernel, dim3(1), dim3(1024), 0, c->stream, ntiles, S.tcnt.p);
+    HIPCHK(hipGetLastError());
+    int nt = 0;   // the one copy: it sizes the handle's two arrays
+    HIPCHK(hipMemcpyAsync(&nt, S.tcnt + ntiles, sizeof nt, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    if (nt < 0 || nt > n) return fail(TWOSD_E_DEVICE, "tail_keep: the tiles' counts sum to %d of %d scenarios", nt, n);
+    PickSet fresh;
+    if ((rc = fresh.d.alloc((size_t)nt)) || (rc = fresh.scen.alloc((size_t)nt))) return rc;
+    if (nt > 0) {
+        hipLaunchKernelGGL(risk_tscatter_kernel, grid, dim3(256), 0, c->stream, P, S.tcnt.p, fresh.scen.p, fresh.d.p);
+        HIPCHK(hipGetLastError());
+    }
+    HIPCHK(hipEventRecord(c->ev[EV_MARK_1], c->stream));
+    HIPCHK(hipEventSynchronize(c->ev[EV_MARK_1]));
+    float ms = 0;
+    hipEventElapsedTime(&ms, c->ev[EV_MARK_0], c->ev[EV_MARK_1]);
+    S.keep_ms = ms;
+    fresh.epi = epi; fresh.n = n; fresh.nv = c->last_cut_nv; fresh.nt = nt; fresh.eta = eta; fresh.live = true;
+    int id = 0;
+    *pick_slot(c, &id) = std::move(fresh);
+    *handle = id;
+    return TWOSD_OK;
+}
+
+// a usable tail handle of the shared table, or the error with its message
+static int usable_tail(twosd_ctx *c, int handle, const char *what, PickSet **out) {
+    int rc = usable_pick(c, handle, what, out);
+    if (rc) return rc;
+    if (!(*out)->is_tail())
+        return fail(TWOSD_E_ARG, "%s: handle %d is a pick handle, not a tail handle (twosd_picks_info / twosd_picks_get)", what, handle);
+    return TWOSD_OK;
+}
+
+extern "C" int twosd_tail_info(twosd_ctx *c, int handle, int *epi, int *n, int *nv, int *nt, double *eta) {
+    if (!c) return fail(TWOSD_E_ARG, "tail_info: ctx is NULL");
+    PickSet *h = nullptr;
+    int rc = usable_tail(c, handle, "tail_info", &h);
+    if (rc) return rc;
+    if (epi) *epi = h->epi;
+    if (n) *n = h->n;
+    if (nv) *nv = h->nv;
+    if (nt) *nt = h->nt;
+    if (eta) *eta = h->eta;
+    return TWOSD_OK;
+}
+
+extern "C" int twosd_tail_get(twosd_ctx *c, int handle, int *scen, int *pick) {
+    if (!c) return fail(TWOSD_E_ARG, "tail_get: ctx is NULL");
+    PickSet *h = nullptr;
+    int rc = usable_tail(c, handle, "tail_get", &h);
+    if (rc) return rc;
+    if (h->nt == 0) return TWOSD_OK;
+    if (!scen || !pick) return fail(TWOSD_E_ARG, "tail_get: scen / pick NULL for a tail of %d scenarios", h->nt);
+    HIPCHK(hipSetDevice(c->device));
+    HIPCHK(hipMemcpyAsync(scen, h->scen, sizeof(int) * h->nt, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipMemcpyAsync(pick, h->d, sizeof(int) * h->nt, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    return TWOSD_OK;
+}
+
+extern "C" int twosd_tail_last_ms(twosd_ctx *c, double *ms) {
+    if (!c || !ms) return fail(TWOSD_E_ARG, "tail_last_ms: NULL");
+    *ms = c->risk.keep_ms;
     return TWOSD_OK;
 }
 

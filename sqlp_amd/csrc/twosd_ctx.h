@@ -51,11 +51,20 @@ struct EpiDevice {
 
 // stored picks of one cut (twosd_picks_keep): the argmax's vertex index of each of the n scenarios
 // the epigraph held then, over the first nv vertices of the set
+//
+// A tail handle (twosd_tail_keep) lives in the same table: nt >= 0, scen = the nt scenarios of that
+// cut scoring above eta in ascending order and d = their nt picks (8 bytes per tail scenario); epi,
+// n and nv stay the cut's.  nt < 0: a pick handle.
 struct PickSet {
-    DevBuf<int> d;                // n picks
+    DevBuf<int> d;                // n picks (a tail handle: nt, by list position)
+    DevBuf<int> scen;             // a tail handle's nt scenario indices, ascending
     int epi = -1, n = 0, nv = 0;
+    int nt = -1;                  // tail handle: the list's length (0: an empty tail)
+    double eta = 0.0;             //   and the eta it was taken at
     bool live = false;
     bool stale = false;           // the vertex set was truncated below nv since: unusable
+    bool is_tail() const { return nt >= 0; }
+    int entries() const { return nt >= 0 ? nt : n; }   // what a re-formation walks: the list, or the n scenarios
 };
 
 // cuts re-formed from stored picks (reform.hip; boot_kernel.hip's bootstrap and risk.hip's tail cut, synchronous on the
@@ -114,7 +123,9 @@ struct RiskState {
     DevBuf<double> obj;               // evaluate_cvar: the whole range's objectives, overwritten by Y
     DevBuf<int> ost;                  //   and statuses
     DevBuf<unsigned long long> thist; // tail cut: [0] W_t, [1] the total, [2 ..) the per-vertex weights (the rest: ReformState)
+    DevBuf<int> tcnt;                 // tail_keep: the 64-scenario tiles' tail counts, then their exclusive offsets and nt
     double ms[2] = {0, 0};            // device time of the last selection / tail re-formation
+    double keep_ms = 0.0;             //   and of the last twosd_tail_keep
 };
 
 // the slots of twosd_last_timings, in the order the ABI reports them (microseconds)

@@ -16,8 +16,15 @@ incumbent test is twosd.check_improvement on the two composite epigraph values.
 
 One epigraph per cell: CVaR of a sum of recourse functions does not separate over epigraphs.
 lam == 0 delegates to master.sd_iteration on the wrapped sdCell, so the x iterates are those of
-the risk-neutral loop bit for bit.  Feasibility rows and the bootstrap stopping rule are out of
-scope here (sd_run runs a fixed number of iterations).
+the risk-neutral loop bit for bit.  Feasibility rows are out of scope here.
+
+The stopping rule (sd_run_stop, bootstrap_gap_test) is the risk-neutral one on both row sets: with
+keep_picks every mean cut keeps its pick handle and every tail row a tail handle (twosd.cut_tail's
+keep=: the scenarios above eta and their picks, compacted on the device).  With its tail set and
+picks fixed a tail row is linear in the scenario weights, so one twosd.reform_cuts call re-forms all
+rows under the Poisson(1) replicates.  The tail set is the one of the row's own (x, eta): at that
+point the re-formed row is the replicate's own E_b[(h - eta)+], elsewhere a lower bound of it
+(DESIGN.md §5.13, §9).  sd_run keeps its fixed iteration count and its int return.
 """
 from __future__ import annotations
 
@@ -26,7 +33,7 @@ from types import SimpleNamespace
 
 import numpy as np
 
-from . import cut_pool, master, twosd
+from . import cut_pool, master, stopping, twosd
 from .smps import spStageProblem
 
 
@@ -55,7 +62,16 @@ def _extend(cut: twosd.sdCut) -> twosd.sdCut:
 def tail_row(tail: twosd.sdTailCut, weight_mark: float) -> twosd.sdCut:
     """tau >= d (alpha + beta'x - eta) as a cut over (x, eta), aged through weight_mark as a mean cut is."""
     d = tail.d
-    return twosd.sdCut(d * tail.alpha, np.append(d * tail.beta, -d), float(weight_mark))
+    return twosd.sdCut(d * tail.alpha, np.append(d * tail.beta, -d), float(weight_mark), tail.picks)
+
+
+def _tail_of_row(row: twosd.sdCut) -> twosd.sdCut:
+    """tail_row undone: the tail cut (alpha, beta over x, weight_mark = the tail's weight W_t) behind a
+    tail row, carrying the row's tail handle -- what reform_cuts re-forms.  d = 0: the zero cut."""
+    d = -float(row.beta[-1])
+    if d == 0.0:
+        return twosd.sdCut(0.0, np.zeros(len(row.beta) - 1), 0.0, row.picks)
+    return twosd.sdCut(row.alpha / d, np.asarray(row.beta[:-1]) / d, d * row.weight_mark, row.picks)
 
 
 class RiskCell:
@@ -157,10 +173,30 @@ class RiskCell:
     def solve_master(self):
         """The regularised master over z = (x, eta, m, tau): returns (x, eta) and stores the cut rows'
         multipliers for the next iteration's cut removal."""
+        n1 = self.cell.n1
+        var, alpha, beta = self.master_rows()
+        res, lam, obj = self.solve_master_rows(var, alpha, beta)
+        self.master_status = res.status
+        if res.status != master.OPTIMAL:
+            raise RuntimeError(f"master not solved: {res.status}")
+        nm = len(self.cell.epi[0].cuts)
+        n_mean_rows = int(np.sum(var == 0))
+        self._mean_duals = lam[:nm]
+        self._tail_duals = lam[n_mean_rows:n_mean_rows + len(self.tail_cuts)]
+        self.master_obj = obj
+        return res.z[:n1].copy(), float(res.z[n1])
+
+    def solve_master_rows(self, var, alpha, beta):
+        """The cell's regularised master (root-stage rows and bounds, tau >= 0, prox term of the
+        current rho and centre) over the given rows var >= alpha + beta'(x, eta), var 0 the mean and
+        1 the tail variable: (QPResult, the rows' multipliers, objective value with the prox constant).
+        Changes nothing in the cell; solve_master is this on the cell's own rows (the stopping rule
+        passes re-formed ones)."""
         c = self.cell
         n1 = c.n1
         nz = n1 + 3
-        var, alpha, beta = self.master_rows()
+        var = np.asarray(var, dtype=np.int64)
+        alpha = np.asarray(alpha, dtype=np.float64)
         if not np.any(var == 0):
             raise RuntimeError("the epigraph has no cut: the master is unbounded")
         wm, wt = self.weights()
@@ -177,18 +213,9 @@ class RiskCell:
         Gt = np.zeros((1, nz))
         Gt[0, n1 + 2] = -1.0              # tau >= 0
         res = master.qp_solve(H, g, Aeq, beq, np.vstack([G, Gc, Gb, Gt]), np.concatenate([h, -alpha, hb, [0.0]]))
-        self.master_status = res.status
-        if res.status != master.OPTIMAL:
-            raise RuntimeError(f"master not solved: {res.status}")
         lam = res.lam[G.shape[0]:G.shape[0] + len(alpha)]
-        epi = c.epi[0]
-        nm = len(epi.cuts)
-        n_mean_rows = int(np.sum(var == 0))
-        self._mean_duals = lam[:nm]
-        self._tail_duals = lam[n_mean_rows:n_mean_rows + len(self.tail_cuts)]
         const = 0.5 * self.rho * float(self.reg_center @ self.reg_center) if self.reg_center is not None else 0.0
-        self.master_obj = res.obj + const
-        return res.z[:n1].copy(), float(res.z[n1])
+        return res, lam, res.obj + const
 
     def remove_cuts_by_multiplier(self, tol=cut_pool.CUT_REMOVE_TOLERANCE):
         """algorithm.jl:57-72 on both row sets: a mean cut or a tail cut whose master row has a
@@ -202,15 +229,18 @@ class RiskCell:
 
 
 def sd_iteration(cell: RiskCell, scenario_list, update_incumbent_cut=True, quad_scalar_schedule=None, tie_rel=0.0,
-                 feasibility=False):
+                 feasibility=False, keep_picks=False):
     """One SD iteration on the mean-CVaR master: master.sd_iteration's steps with the tail cut taken
     right after each mean cut (twosd.cut_tail at the eta of the cut's point) and (x, eta) as the
-    master point.  lam == 0: master.sd_iteration on the wrapped cell itself."""
+    master point.  keep_picks: every new mean cut keeps its pick handle and every new tail row its
+    tail handle (for bootstrap_gap_test), and the handles of rows that left are released: the live
+    handles are then len(epi.cuts) + len(cell.tail_cuts) + 2.  lam == 0: master.sd_iteration on the
+    wrapped cell itself."""
     if feasibility:
         raise ValueError("risk.sd_iteration: feasibility rows are not supported for the composite objective")
     if cell.risk.lam == 0.0:
         master.sd_iteration(cell.cell, scenario_list, update_incumbent_cut=update_incumbent_cut,
-                            quad_scalar_schedule=quad_scalar_schedule, tie_rel=tie_rel)
+                            quad_scalar_schedule=quad_scalar_schedule, tie_rel=tie_rel, keep_picks=keep_picks)
         cell.improvement_info = cell.cell.improvement_info
         return
     if quad_scalar_schedule is None:
@@ -223,14 +253,17 @@ def sd_iteration(cell: RiskCell, scenario_list, update_incumbent_cut=True, quad_
     if cell.master_status == master.OPTIMAL:
         cell.remove_cuts_by_multiplier()
     info_last = cell.composite()
-    cut = twosd.build_sasa_cut(epi, c.x_candidate, V, tie_rel)
+    cut = twosd.build_sasa_cut(epi, c.x_candidate, V, tie_rel, keep_picks=keep_picks)
     if cell.eta_candidate is None:      # the first iteration: eta starts at the sample's VaR at the candidate
         cell.eta_candidate = cell.eta_incumbent = twosd.cut_quantile(epi, cell.risk.level).var
     epi.cuts.append(cut)
-    cell.tail_cuts.append(tail_row(twosd.cut_tail(epi, cell.eta_candidate), cut.weight_mark))
+    cell.tail_cuts.append(tail_row(twosd.cut_tail(epi, cell.eta_candidate, keep=keep_picks), cut.weight_mark))
     if update_incumbent_cut:
-        epi.incumbent_cut = twosd.build_sasa_cut(epi, c.x_incumbent, V, tie_rel)
-        cell.tail_incumbent = tail_row(twosd.cut_tail(epi, cell.eta_incumbent), epi.incumbent_cut.weight_mark)
+        epi.incumbent_cut = twosd.build_sasa_cut(epi, c.x_incumbent, V, tie_rel, keep_picks=keep_picks)
+        cell.tail_incumbent = tail_row(twosd.cut_tail(epi, cell.eta_incumbent, keep=keep_picks), epi.incumbent_cut.weight_mark)
+    if keep_picks:   # removed rows and the replaced incumbent rows no longer need their handles
+        live = [r.picks for r in cell.tail_cuts + [cell.tail_incumbent] if r is not None and r.picks is not None]
+        twosd.release_unused_picks(epi, keep=live)
     zc = np.append(c.x_candidate, cell.eta_candidate)
     zi = np.append(c.x_incumbent, cell.eta_incumbent)
     cell.improvement_info = c.improvement_info = twosd.check_improvement(
@@ -245,12 +278,136 @@ def sd_iteration(cell: RiskCell, scenario_list, update_incumbent_cut=True, quad_
 
 
 def sd_run(cell: RiskCell, next_scenarios, max_iter, **iteration_args):
-    """max_iter iterations of sd_iteration(cell, next_scenarios(it)).  There is no stopping rule for
-    the composite objective: no stop= argument, and feasibility=True raises ValueError."""
+    """max_iter iterations of sd_iteration(cell, next_scenarios(it)): a fixed count, returned as an
+    int.  The loop with the stopping rule is sd_run_stop: no stop= argument here, and
+    feasibility=True raises ValueError."""
     if "stop" in iteration_args:
-        raise TypeError("risk.sd_run takes no stop= (no stopping rule for the composite objective)")
+        raise TypeError("risk.sd_run takes no stop= (a fixed number of iterations; the loop with the stopping rule "
+                        "is risk.sd_run_stop)")
     if iteration_args.get("feasibility"):
         raise ValueError("risk.sd_run: feasibility rows are not supported for the composite objective")
     for it in range(int(max_iter)):
         sd_iteration(cell, next_scenarios(it), **iteration_args)
     return int(max_iter)
+
+
+def _rows_with_picks(cell: RiskCell):
+    """(mean cuts, has incumbent, tail rows, has incumbent tail) of the cell, every one with its handle."""
+    epi = cell.cell.epi[0]
+    mean = stopping._epigraph_cuts(epi, 0)
+    tails = list(cell.tail_cuts) + ([cell.tail_incumbent] if cell.tail_incumbent is not None else [])
+    for j, row in enumerate(tails):
+        if row.picks is None:
+            which = "incumbent tail row" if (cell.tail_incumbent is not None and j == len(tails) - 1) else f"tail row {j}"
+            raise ValueError(f"bootstrap_gap_test: {which} carries no picks; run the iterations with keep_picks=True "
+                             "(risk.sd_iteration / risk.sd_run_stop)")
+    return mean, epi.incumbent_cut is not None, tails, cell.tail_incumbent is not None
+
+
+def bootstrap_gap_test(cell: RiskCell, M=32, seed=0, eps=1e-3, frac=0.95, index_offset=0, reform=None,
+                       sampling=None) -> "stopping.GapTest":
+    """stopping.bootstrap_gap_test for the composite objective, at the incumbent (x^, eta^).
+
+    One reform_cuts call re-forms the mean cuts, the incumbent cut, the tail rows' tail handles and the
+    incumbent tail's under the identity weights (b = 0) and M Poisson(1) replicates.  With
+    total_b = total_weight[b], the rows of replicate b in master_rows() order:
+        mean rows      those of stopping.bootstrap_gap_test, on variable 0
+        tail rows      tau >= (W_t,jb / total_b) (alpha_jb + beta_jb'x - eta)
+        incumbent tail tau >= (W_t,b / W_inc,b) (...), W_inc,b the re-formed incumbent mean cut's
+                       weight_mark; dropped when that is 0
+        tau >= 0       always (solve_master_rows)
+    U_b = c'x^ + lam eta^ + w_mean max(mean rows at x^, lower bound) + w_tail max(tail rows at (x^, eta^), 0),
+    L_b = solve_master_rows over those rows; gaps, threshold, fraction and passed as in the
+    risk-neutral test.  rows0: replicate 0's (var, alpha, beta); rows: every replicate's.
+    The tail sets are fixed at each row's own (x, eta) and the resampling is a Poisson(1) bootstrap:
+    DESIGN.md §9.  lam == 0: stopping.bootstrap_gap_test on the wrapped cell.
+    reform(epi, cuts, M, seed, index_offset) replaces twosd.reform_cuts (tests): its cuts are sdCut
+    objects, a tail row's the tail cut behind it with weight_mark = the tail's weight."""
+    if cell.risk.lam == 0.0:
+        return stopping.bootstrap_gap_test(cell.cell, M=M, seed=seed, eps=eps, frac=frac, index_offsets=[index_offset],
+                                           reform=reform, sampling=sampling)
+    if M < 1:
+        raise ValueError("bootstrap_gap_test: M must be at least 1")
+    reform = twosd.reform_cuts if reform is None else reform
+    c = cell.cell
+    epi = c.epi[0]
+    n1 = c.n1
+    mean, has_inc, tails, has_tinc = _rows_with_picks(cell)
+    nc, nt = len(epi.cuts), len(cell.tail_cuts)
+    kw = {} if sampling is None else {"sampling": sampling}
+    R = reform(epi, mean + [_tail_of_row(r) for r in tails], M, seed, index_offset, **kw)
+    o_t = len(mean)                                    # the first tail handle's column
+    z = np.append(np.asarray(c.x_incumbent, dtype=np.float64), float(cell.eta_incumbent))
+    cz = cell.objf_original(z[:n1], z[n1])
+    wm, wt = cell.weights()
+    lb = epi.lower_bound
+    U, L, rows = np.zeros(M + 1), np.zeros(M + 1), []
+
+    def over_z(a, beta_x, d, eta_coef):
+        return d * a, np.append(d * np.asarray(beta_x, dtype=np.float64), eta_coef)
+    for b in range(M + 1):
+        tw = float(R.total_weight[b])
+        var, ra, rb = [], [], []
+        # the mean rows: stopping.bootstrap_gap_test's (a replicate that drew nothing leaves the lower bound)
+        if tw > 0.0:
+            for j in range(nc):
+                d = float(R.weight_mark[b, j]) / tw
+                a, be = over_z(R.alpha[b, j], R.beta[b, j], d, 0.0)
+                var.append(0); ra.append(a + (1 - d) * lb); rb.append(be)
+        w_inc = float(R.weight_mark[b, nc]) if has_inc else 0.0
+        if has_inc:
+            if w_inc == 0.0:
+                var.append(0); ra.append(lb); rb.append(np.zeros(n1 + 1))
+            else:
+                var.append(0); ra.append(float(R.alpha[b, nc])); rb.append(np.append(R.beta[b, nc], 0.0))
+        if not var:
+            var.append(0); ra.append(lb); rb.append(np.zeros(n1 + 1))
+        n_mean = len(var)
+        # the tail rows: tau >= d (alpha + beta'x - eta), d the tail's share of the replicate's weight
+        if tw > 0.0:
+            for j in range(nt):
+                d = float(R.weight_mark[b, o_t + j]) / tw
+                a, be = over_z(R.alpha[b, o_t + j], R.beta[b, o_t + j], d, -d)
+                var.append(1); ra.append(a); rb.append(be)
+        if has_tinc and w_inc > 0.0:
+            d = float(R.weight_mark[b, o_t + nt]) / w_inc
+            a, be = over_z(R.alpha[b, o_t + nt], R.beta[b, o_t + nt], d, -d)
+            var.append(1); ra.append(a); rb.append(be)
+        var, ra, rb = np.array(var, dtype=np.int64), np.array(ra), np.array(rb).reshape(len(ra), n1 + 1)
+        at_z = ra + rb @ z
+        m_val = max(lb, float(at_z[:n_mean].max()))
+        t_val = max(0.0, float(at_z[n_mean:].max())) if len(ra) > n_mean else 0.0
+        res, _, obj = cell.solve_master_rows(var, ra, rb)
+        if res.status != master.OPTIMAL:
+            raise RuntimeError(f"bootstrap_gap_test: master of replicate {b} not solved: {res.status}")
+        U[b], L[b] = cz + wm * m_val + wt * t_val, obj
+        rows.append((var, ra, rb))
+    gaps = U - L
+    thr = eps * (1.0 + abs(U[0]))
+    fraction = float(np.count_nonzero(gaps[1:] <= thr)) / M
+    return stopping.GapTest(U, L, gaps, thr, fraction, fraction >= frac, rows[0], tuple(rows))
+
+
+def sd_run_stop(cell: RiskCell, next_scenarios, max_iter, min_iter=0, check_every=10, stop=None, sampling=None,
+                stop_args=None, **iteration_args):
+    """master.sd_run for the composite objective: sd_iteration(cell, next_scenarios(it), keep_picks=True)
+    for it = 0, 1, ... and, every check_every iterations once min_iter have run, stop(cell) --
+    default bootstrap_gap_test(cell, sampling=sampling, **stop_args) -- ending when its result has
+    .passed, or after max_iter.  Returns (iterations run, the last test result or None)."""
+    if check_every < 1:
+        raise ValueError("check_every must be at least 1")
+    if iteration_args.get("feasibility"):
+        raise ValueError("risk.sd_run_stop: feasibility rows are not supported for the composite objective")
+    if stop is None:
+        def stop(c):
+            return bootstrap_gap_test(c, sampling=sampling, **(stop_args or {}))
+    result = None
+    it = 0
+    while it < max_iter:
+        sd_iteration(cell, next_scenarios(it), keep_picks=True, **iteration_args)
+        it += 1
+        if it >= min_iter and it % check_every == 0:
+            result = stop(cell)
+            if result.passed:
+                break
+    return it, result

@@ -34,6 +34,7 @@ class GapTest:
     fraction: float        # share of the replicates 1..M with gap <= threshold
     passed: bool           # fraction >= frac
     rows0: tuple = ()      # (epi, alpha, beta) master rows of the identity replicate, in sync_cuts' order
+    rows: tuple = ()       # every replicate's (variable, alpha, beta) rows (risk.bootstrap_gap_test fills it)
 
 
 def _epigraph_cuts(epi, e):

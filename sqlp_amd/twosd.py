@@ -1180,7 +1180,7 @@ class ReformedCuts:
 def _handles_of(cuts):
     hs = []
     for cut in cuts:
-        h = cut.picks if isinstance(cut, sdCut) else cut
+        h = cut.picks if isinstance(cut, (sdCut, sdTailCut)) else cut   # a pick handle or a tail handle, alike
         if h is None:
             raise ValueError("reform_cuts: a cut carries no picks (build it with keep_picks=True)")
         hs.append(int(h))
@@ -1282,20 +1282,64 @@ class sdTailCut:
     tail_weight: float
     total_weight: float
     eta: float
+    picks: Optional[int] = None   # the tail handle (cut_tail(keep=True)), for reform_cuts
 
     @property
     def d(self) -> float:
         return self.tail_weight / self.total_weight
 
 
-def cut_tail(epi: sdEpigraph, eta) -> sdTailCut:
+def cut_tail(epi: sdEpigraph, eta, keep=False) -> sdTailCut:
     """twosd_cut_tail: the last cut built on epi re-formed from its picks over the scenarios whose
-    score exceeds eta (strictly), normalised by their weight."""
+    score exceeds eta (strictly), normalised by their weight.  keep: the result carries a tail
+    handle of that set and its picks (keep_tail_of_last_cut)."""
     ctx = epi.ctx
     a, tw, W = C.c_double(), C.c_double(), C.c_double()
     beta = np.zeros(ctx.n1)
     check(ctx.lib.twosd_cut_tail(ctx.h, epi.index, float(eta), C.byref(a), ptr(beta), C.byref(tw), C.byref(W)))
-    return sdTailCut(a.value, beta, tw.value, W.value, float(eta))
+    return sdTailCut(a.value, beta, tw.value, W.value, float(eta), keep_tail_of_last_cut(epi, eta) if keep else None)
+
+
+def keep_tail_of_last_cut(epi: sdEpigraph, eta) -> int:
+    """twosd_tail_keep: a handle of the tail of the last cut built on epi at eta -- the scenarios
+    scoring above eta (cut_tail's set, bit for bit) in ascending order and their picks, compacted on
+    the device (8 bytes per tail scenario).  reform_cuts takes it like a pick handle; it is released,
+    counted and dropped like one."""
+    h = C.c_int()
+    check(epi.ctx.lib.twosd_tail_keep(epi.ctx.h, epi.index, float(eta), C.byref(h)))
+    epi._pick_handles.add(h.value)
+    return h.value
+
+
+@dataclass(frozen=True)
+class TailInfo:
+    """twosd_tail_info's result: the cut's epigraph, scenarios and |V|, the tail's length and its eta."""
+    epi: int
+    n: int
+    nv: int
+    nt: int
+    eta: float
+
+
+def tail_info(ctx: SDContext, handle) -> TailInfo:
+    e, n, nv, nt, eta = C.c_int(), C.c_int(), C.c_int(), C.c_int(), C.c_double()
+    check(ctx.lib.twosd_tail_info(ctx.h, int(handle), C.byref(e), C.byref(n), C.byref(nv), C.byref(nt), C.byref(eta)))
+    return TailInfo(e.value, n.value, nv.value, nt.value, eta.value)
+
+
+def tail_get(ctx: SDContext, handle):
+    """(scenario indices ascending, their picks) of a tail handle: two int32 arrays of length nt."""
+    nt = tail_info(ctx, handle).nt
+    scen, pick = np.zeros(nt, dtype=np.int32), np.zeros(nt, dtype=np.int32)
+    check(ctx.lib.twosd_tail_get(ctx.h, int(handle), ptr(scen), ptr(pick)))
+    return scen, pick
+
+
+def tail_last_ms(ctx: SDContext) -> float:
+    """Device milliseconds of the last keep_tail_of_last_cut."""
+    ms = C.c_double()
+    check(ctx.lib.twosd_tail_last_ms(ctx.h, C.byref(ms)))
+    return ms.value
 
 
 def risk_last_ms(ctx: SDContext):
