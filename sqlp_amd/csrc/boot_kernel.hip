@@ -39,16 +39,14 @@
 //                        lanes = elements (e = lane, lane + 64) while the tile's scenarios go by one
 //                        at a time with wave-uniform picks and counts (v_readlane); 16 + 1
 //                        accumulators per element stay in VGPRs (KE = 2: 191 VGPRs, no scratch)
-//   boot_tweight_kernel, boot_thist_kernel, boot_treform_kernel<KE, GR>
-//                        the three above over a tail handle's compact list (twosd_tail_keep, risk.hip:
-//                        the nt scenarios of a cut scoring above eta, and their picks): the counts are
-//                        c_b(s) 1[s in the tail], a count still a function of the scenario's global
-//                        index (or group), and only the tail's rows of the deltas are read -- the shards
-//                        are reform_shards(nt) over the list.  Nothing is launched over an empty list
-//                        (the zero cut), and a call without tail handles launches what it always did.
+//   <..., LIST = true>   the three above instantiated over a tail handle's compact list (twosd_tail_keep,
+//                        risk.hip: the nt scenarios of a cut scoring above eta, and their picks): the
+//                        counts are c_b(s) 1[s in the tail], still a function of the scenario's global
+//                        index (or group); only the tail's rows of the deltas are read, in
+//                        reform_shards(nt) shards.  Nothing is launched over an empty list (the zero cut).
 // then reform.hip's stage, shared with the tail cut of risk.hip: S from the shards' partials, g, and
-// alpha, beta per (handle, replicate) normalised by W_jb.  boot_hist_kernel and boot_reform_kernel
-// stay the bootstrap's own: do not merge them with risk.hip's look-alikes (reform.hip's header).
+// alpha, beta per (handle, replicate) normalised by W_jb.  The rule for changing one of these bodies,
+// and why risk.hip's look-alikes stay separate kernels: reform.hip's header.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <algorithm>
@@ -102,14 +100,21 @@ __global__ void __launch_bounds__(256) boot_counts_kernel(int M, unsigned long l
 // out[0] += sum q_s, out[1 + b] += sum c_b(s) q_s over s < n; blockIdx.y = the Philox call Q of four
 // replicates, the last y the identity row.  Integer sums: any order gives the same bits.  One atomic
 // per block and replicate (a few blocks: every wave adding to the same 33 words took 0.5 ms).
-template <bool GR>
+// LIST (here and below): the walk is over the n entries of a tail handle's list (scen[i] ascending
+// scenario indices, picks[i] by list position), entry i with the weight and the count of scenario
+// scen[i] -- never of the list position: the row of a pick handle with -1 outside the list.  !LIST:
+// the scenarios 0 .. n - 1, scen unused.
+template <bool GR, bool LIST>
 __global__ void __launch_bounds__(256) boot_weight_kernel(int n, const double *__restrict__ w, double scale, int M,
                                                           unsigned long long seed, unsigned long long off,
-                                                          unsigned long long *__restrict__ out, unsigned G) {
+                                                          unsigned long long *__restrict__ out, unsigned G,
+                                                          const int *__restrict__ scen) {
     __shared__ unsigned long long sh[4][4];
     const int nq = (M + 3) / 4, Q = blockIdx.y;
     unsigned long long a[4] = {0ull, 0ull, 0ull, 0ull};
-    for (int s = blockIdx.x * 256 + threadIdx.x; s < n; s += gridDim.x * 256) {
+    for (int i = blockIdx.x * 256 + threadIdx.x; i < n; i += gridDim.x * 256) {
+        int s = i;
+        if constexpr (LIST) s = scen[i];
         const unsigned long long q = reform_q(w[s], scale);
         if (Q == nq) { a[0] += q; continue; }
         const Philox4 r = boot_words(boot_index<GR>(off, s, G), Q, seed);
@@ -138,93 +143,21 @@ __global__ void __launch_bounds__(256) boot_weight_kernel(int n, const double *_
 // row), blockIdx.z = a window of kBootVW vertices (a pick outside it is another block's).  Integer
 // sums: the atomics' order does not show in the result.
 constexpr int kBootVW = 2048;
-template <bool GR>
+template <bool GR, bool LIST>
 __global__ void __launch_bounds__(1024) boot_hist_kernel(int n, int nv, int nvs, int M, const int *__restrict__ picks,
                                                          const double *__restrict__ w, double scale, unsigned long long seed,
-                                                         unsigned long long off, unsigned long long *__restrict__ hist, unsigned G) {
+                                                         unsigned long long off, unsigned long long *__restrict__ hist, unsigned G,
+                                                         const int *__restrict__ scen) {
     __shared__ unsigned long long hl[4 * kBootVW];
     const int nq = (M + 3) / 4, Q = blockIdx.y;
     const int v0 = blockIdx.z * kBootVW, v1 = min(nv, v0 + kBootVW);
     for (int i = threadIdx.x; i < 4 * kBootVW; i += 1024) hl[i] = 0ull;
     __syncthreads();
-    for (int s = blockIdx.x * 1024 + threadIdx.x; s < n; s += gridDim.x * 1024) {
-        const int pick = picks[s];
-        if (pick < v0 || pick >= v1) continue;
-        const unsigned long long q = reform_q(w[s], scale);
-        if (!q) continue;
-        if (Q == nq) {
-            __hip_atomic_fetch_add(&hl[pick - v0], q, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-            continue;
-        }
-        const Philox4 r = boot_words(boot_index<GR>(off, s, G), Q, seed);
-#pragma unroll
-        for (int t = 0; t < 4; ++t) {
-            const int cnt = (4 * Q + t < M) ? boot_count_of_word(r.v[t]) : 0;
-            if (cnt)
-                __hip_atomic_fetch_add(&hl[t * kBootVW + pick - v0], (unsigned long long)cnt * q, __ATOMIC_RELAXED,
-                                       __HIP_MEMORY_SCOPE_WORKGROUP);
-        }
-    }
-    __syncthreads();
-    for (int i = threadIdx.x; i < 4 * kBootVW; i += 1024) {
-        const unsigned long long h = hl[i];
-        if (!h) continue;
-        const int row = Q == nq ? 0 : 1 + 4 * Q + i / kBootVW;
-        atomicAdd(&hist[(size_t)row * nvs + v0 + i % kBootVW], h);
-    }
-}
-
-// The tail handles' siblings of the two kernels above: the nt entries of a compact list (scen[i]
-// ascending scenario indices, picks[i] by list position) instead of the scenarios 0 .. n - 1.  The
-// weight and the count of entry i are those of scenario scen[i] -- the draw's index is the
-// scenario's (or its group's), never the list position -- so a row is the one a pick handle with
-// -1 outside the list would give.  Integer sums, as above.
-template <bool GR>
-__global__ void __launch_bounds__(256) boot_tweight_kernel(int nt, const int *__restrict__ scen, const double *__restrict__ w,
-                                                           double scale, int M, unsigned long long seed, unsigned long long off,
-                                                           unsigned long long *__restrict__ out, unsigned G) {
-    __shared__ unsigned long long sh[4][4];
-    const int nq = (M + 3) / 4, Q = blockIdx.y;
-    unsigned long long a[4] = {0ull, 0ull, 0ull, 0ull};
-    for (int i = blockIdx.x * 256 + threadIdx.x; i < nt; i += gridDim.x * 256) {
-        const int s = scen[i];
-        const unsigned long long q = reform_q(w[s], scale);
-        if (Q == nq) { a[0] += q; continue; }
-        const Philox4 r = boot_words(boot_index<GR>(off, s, G), Q, seed);
-#pragma unroll
-        for (int t = 0; t < 4; ++t) a[t] += (unsigned long long)boot_count_of_word(r.v[t]) * q;
-    }
-#pragma unroll
-    for (int t = 0; t < 4; ++t)
-        for (int o = 32; o > 0; o >>= 1) a[t] += __shfl_xor(a[t], o);
-    if ((threadIdx.x & 63) == 0)
-        for (int t = 0; t < 4; ++t) sh[threadIdx.x >> 6][t] = a[t];
-    __syncthreads();
-    if (threadIdx.x >= 4) return;
-    const int t = threadIdx.x;
-    const unsigned long long v = sh[0][t] + sh[1][t] + sh[2][t] + sh[3][t];
-    if (!v) return;
-    if (Q == nq) {
-        if (t == 0) atomicAdd(&out[0], v);
-    } else if (4 * Q + t < M) {
-        atomicAdd(&out[1 + 4 * Q + t], v);
-    }
-}
-
-template <bool GR>
-__global__ void __launch_bounds__(1024) boot_thist_kernel(int nt, int nv, int nvs, int M, const int *__restrict__ scen,
-                                                          const int *__restrict__ picks, const double *__restrict__ w, double scale,
-                                                          unsigned long long seed, unsigned long long off,
-                                                          unsigned long long *__restrict__ hist, unsigned G) {
-    __shared__ unsigned long long hl[4 * kBootVW];
-    const int nq = (M + 3) / 4, Q = blockIdx.y;
-    const int v0 = blockIdx.z * kBootVW, v1 = min(nv, v0 + kBootVW);
-    for (int i = threadIdx.x; i < 4 * kBootVW; i += 1024) hl[i] = 0ull;
-    __syncthreads();
-    for (int i = blockIdx.x * 1024 + threadIdx.x; i < nt; i += gridDim.x * 1024) {
+    for (int i = blockIdx.x * 1024 + threadIdx.x; i < n; i += gridDim.x * 1024) {
         const int pick = picks[i];
         if (pick < v0 || pick >= v1) continue;
-        const int s = scen[i];
+        int s = i;
+        if constexpr (LIST) s = scen[i];
         const unsigned long long q = reform_q(w[s], scale);
         if (!q) continue;
         if (Q == nq) {
@@ -257,7 +190,7 @@ struct BootParams {
     const double *dv, *w, *PK;
     const int *picks;
     double *slots;                       // nchunks x (M + 1) x k
-    const int *scen;                     // boot_treform_kernel: n is the list's length, picks go by list position
+    const int *scen;                     // LIST: n is the list's length, picks go by list position
 };
 
 // KE: elements per lane (k <= 64 KE).  GM: whose count a scenario carries --
@@ -267,8 +200,12 @@ struct BootParams {
 //   2  its group's, G a multiple of 64: off and every tile start are multiples of 64, so a tile lies
 //      inside one group and its 16 counts are wave-uniform -- one draw per tile, held in SGPRs, and
 //      the tile's terms are summed once and weighed by the 16 counts at the tile's end
-template <int KE, int GM>
+// LIST: the tiles are 64 entries of a tail handle's list, each lane draws the words of its own entry's
+// scenario (or of that scenario's group) and only the rows dv[scen_i] are read; the shards are
+// reform_shards(nt) over the list.  A tile of the list straddles groups whatever G is: no GM == 2.
+template <int KE, int GM, bool LIST>
 __global__ void __launch_bounds__(256) boot_reform_kernel(BootParams P) {
+    static_assert(!(LIST && GM == 2), "a tile of a tail handle's list never lies inside one group");
     __shared__ double comb[(kBootGroup + 1) * KE * 64];
     const int lane = threadIdx.x & 63;
     const int wid = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -285,10 +222,12 @@ __global__ void __launch_bounds__(256) boot_reform_kernel(BootParams P) {
         for (int u = 0; u < KE; ++u) acc[r][u] = 0.0;
 
     for (int t = t0 + wid; t < t1; t += 4) {
-        // lanes = the tile's scenarios
-        const int s = t * 64 + lane;
-        const bool valid = s < P.n;
-        const int pick = valid ? P.picks[s] : -1;
+        // lanes = the tile's scenarios (LIST: its list entries)
+        const int li = t * 64 + lane;
+        const bool valid = li < P.n;
+        int s = li;
+        if constexpr (LIST) s = valid ? P.scen[li] : 0;
+        const int pick = valid ? P.picks[li] : -1;
         const bool ok = pick >= 0 && pick < P.nv;          // a scenario without a pick weighs in W only
         const unsigned long long q = ok ? reform_q(P.w[s], P.scale) : 0ull;
         unsigned chi[kBootGroup];                           // high word of (double)count: 0 for count 0
@@ -325,9 +264,11 @@ __global__ void __launch_bounds__(256) boot_reform_kernel(BootParams P) {
             for (int u4 = 0; u4 < 4; ++u4) {
                 const int i = min(i0 + u4, nvalid - 1);
                 const int pv = __builtin_amdgcn_readlane(pk0, i);
+                const double *row = dvt + (size_t)i * P.k;
+                if constexpr (LIST) row = P.dv + (size_t)__builtin_amdgcn_readlane(s, i) * P.k;
 #pragma unroll
                 for (int u = 0; u < KE; ++u) {
-                    d[u4][u] = dvt[(size_t)i * P.k + ec[u]];
+                    d[u4][u] = row[ec[u]];
                     p[u4][u] = P.PK[(size_t)pv * P.k4 + ec[u]];
                 }
             }
@@ -367,120 +308,6 @@ __global__ void __launch_bounds__(256) boot_reform_kernel(BootParams P) {
                 for (int r = 0; r < kBootGroup; ++r) acc[r][u] = fma(__hiloint2double((int)chi[r], 0), tsum, acc[r][u]);
                 acc[kBootGroup][u] = idsum[u] + tsum;
             }
-        }
-    }
-    // the block's four waves combined in wave order
-    for (int wv = 0; wv < 4; ++wv) {
-        if (wid == wv) {
-#pragma unroll
-            for (int r = 0; r <= kBootGroup; ++r)
-#pragma unroll
-                for (int u = 0; u < KE; ++u) {
-                    double &d = comb[(r * KE + u) * 64 + lane];
-                    d = wv == 0 ? acc[r][u] : d + acc[r][u];
-                }
-        }
-        __syncthreads();
-    }
-    const int B = P.M + 1;
-    double *out = P.slots + (size_t)chunk * B * P.k;
-    for (int idx = threadIdx.x; idx < (kBootGroup + 1) * KE * 64; idx += 256) {
-        const int r = idx / (KE * 64), e = idx % (KE * 64);
-        const int row = r == kBootGroup ? (grp == 0 ? 0 : -1) : 1 + grp * kBootGroup + r;
-        if (row >= 0 && row < B && e < P.k) out[(size_t)row * P.k + e] = comb[idx];
-    }
-}
-
-// boot_reform_kernel's sibling over a tail handle's compact list (P.n entries, P.scen, P.picks by
-// list position): lanes = the 64 list entries of a tile for the draws -- each lane the Philox words of
-// its own scenario (GR: of its scenario's group; a tile of the list straddles groups whatever G is, so
-// there is no tile-uniform form) -- then lanes = elements while the tile's entries go by four at a
-// time, the rows dv[scen_i] and PK[pick_i] of the next four in flight.  Only the list's rows of dv are
-// read.  The shards are reform_shards(nt) over the list: the same bits on every run.  A sibling, not
-// an instantiation: reform.hip's header.
-template <int KE, bool GR>
-__global__ void __launch_bounds__(256) boot_treform_kernel(BootParams P) {
-    __shared__ double comb[(kBootGroup + 1) * KE * 64];
-    const int lane = threadIdx.x & 63;
-    const int wid = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int grp = blockIdx.x % P.ngroups, chunk = blockIdx.x / P.ngroups;
-    const int ntiles = (P.n + 63) >> 6;
-    const int t0 = chunk * P.tpb, t1 = min(ntiles, t0 + P.tpb);
-    int ec[KE];                       // this lane's elements, clamped to k - 1
-#pragma unroll
-    for (int u = 0; u < KE; ++u) ec[u] = min(lane + 64 * u, P.k - 1);
-    double acc[kBootGroup + 1][KE];
-#pragma unroll
-    for (int r = 0; r <= kBootGroup; ++r)
-#pragma unroll
-        for (int u = 0; u < KE; ++u) acc[r][u] = 0.0;
-
-    for (int t = t0 + wid; t < t1; t += 4) {
-        // lanes = the tile's list entries
-        const int li = t * 64 + lane;
-        const bool valid = li < P.n;
-        const int s = valid ? P.scen[li] : 0;
-        const int pick = valid ? P.picks[li] : -1;
-        const bool ok = pick >= 0 && pick < P.nv;
-        const unsigned long long q = ok ? reform_q(P.w[s], P.scale) : 0ull;
-        unsigned chi[kBootGroup];                           // high word of (double)count: 0 for count 0
-#pragma unroll
-        for (int qd = 0; qd < kBootGroup / 4; ++qd) {
-            const int Q = grp * (kBootGroup / 4) + qd;
-            Philox4 r;
-            r.v[0] = r.v[1] = r.v[2] = r.v[3] = 0u;
-            if (4 * Q < P.M) r = boot_words(boot_index<GR>(P.off, s, (unsigned)P.G), Q, P.seed);   // wave-uniform
-#pragma unroll
-            for (int tt = 0; tt < 4; ++tt) {
-                const int cnt = (4 * Q + tt < P.M) ? boot_count_of_word(r.v[tt]) : 0;
-                chi[4 * qd + tt] = (unsigned)__double2hiint((double)cnt);
-            }
-        }
-        const double qf = (double)q;
-        const int qlo = __double2loint(qf), qhi = __double2hiint(qf);
-        const int pk0 = ok ? pick : 0;
-        // lanes = elements; a lane past k reads element k - 1 again and its sums are never stored; a
-        // step past the tile's last entry reads that entry again with weight 0
-        const int nvalid = min(64, P.n - t * 64);
-        auto load4 = [&](int i0, double (&d)[4][KE], double (&p)[4][KE]) {
-#pragma unroll
-            for (int u4 = 0; u4 < 4; ++u4) {
-                const int i = min(i0 + u4, nvalid - 1);
-                const int pv = __builtin_amdgcn_readlane(pk0, i);
-                const int sv = __builtin_amdgcn_readlane(s, i);
-#pragma unroll
-                for (int u = 0; u < KE; ++u) {
-                    d[u4][u] = P.dv[(size_t)sv * P.k + ec[u]];
-                    p[u4][u] = P.PK[(size_t)pv * P.k4 + ec[u]];
-                }
-            }
-        };
-        auto work4 = [&](int i0, const double (&d)[4][KE], const double (&p)[4][KE]) {
-#pragma unroll
-            for (int u4 = 0; u4 < 4; ++u4) {
-                const int i = min(i0 + u4, 63);
-                const double wq = i0 + u4 < nvalid ? __hiloint2double(__builtin_amdgcn_readlane(qhi, i), __builtin_amdgcn_readlane(qlo, i)) : 0.0;
-                double term[KE];
-#pragma unroll
-                for (int u = 0; u < KE; ++u) term[u] = wq * p[u4][u] * d[u4][u];
-#pragma unroll
-                for (int r = 0; r < kBootGroup; ++r) {
-                    const double cd = __hiloint2double(__builtin_amdgcn_readlane((int)chi[r], i), 0);   // wave-uniform count
-#pragma unroll
-                    for (int u = 0; u < KE; ++u) acc[r][u] = fma(cd, term[u], acc[r][u]);
-                }
-#pragma unroll
-                for (int u = 0; u < KE; ++u) acc[kBootGroup][u] += term[u];
-            }
-        };
-        double da[4][KE], pa[4][KE], db[4][KE], pb[4][KE];
-        load4(0, da, pa);
-        for (int i0 = 0; i0 < nvalid; i0 += 8) {
-            if (i0 + 4 < nvalid) load4(i0 + 4, db, pb);
-            work4(i0, da, pa);
-            if (i0 + 4 >= nvalid) break;
-            if (i0 + 8 < nvalid) load4(i0 + 8, da, pa);
-            work4(i0 + 4, db, pb);
         }
     }
     // the block's four waves combined in wave order
@@ -551,6 +378,33 @@ static int boot_layout(twosd_ctx *c, int epi, int H, const int *handles, int M, 
     return TWOSD_OK;
 }
 
+// Kernel selection, one function per family.  G == 1 draws by the scenario, G > 1 by its group;
+// list: the walk is over a tail handle's list.
+using BootWeightFn = decltype(&boot_weight_kernel<false, false>);
+static BootWeightFn boot_weight_fn(int G, bool list) {
+    return G == 1 ? (list ? boot_weight_kernel<false, true> : boot_weight_kernel<false, false>)
+                  : (list ? boot_weight_kernel<true, true> : boot_weight_kernel<true, false>);
+}
+
+using BootHistFn = decltype(&boot_hist_kernel<false, false>);
+static BootHistFn boot_hist_fn(int G, bool list) {
+    return G == 1 ? (list ? boot_hist_kernel<false, true> : boot_hist_kernel<false, false>)
+                  : (list ? boot_hist_kernel<true, true> : boot_hist_kernel<true, false>);
+}
+
+// GM = 0 for G == 1; 2 where a tile lies inside one group (G a multiple of 64, never on a list); else 1
+using BootReformFn = void (*)(BootParams);
+template <int KE>
+static BootReformFn boot_reform_fn(int G, bool list) {
+    if (G == 1) return list ? boot_reform_kernel<KE, 0, true> : boot_reform_kernel<KE, 0, false>;
+    if (G % 64 == 0 && !list) return boot_reform_kernel<KE, 2, false>;
+    return list ? boot_reform_kernel<KE, 1, true> : boot_reform_kernel<KE, 1, false>;
+}
+
+static BootReformFn boot_reform_fn(int k, int G, bool list) {   // k <= 64: one element per lane
+    return k <= 64 ? boot_reform_fn<1>(G, list) : boot_reform_fn<2>(G, list);
+}
+
 // G > 1: the counts of a variance-reduced stream's groups (off and every scenario count are whole
 // groups: the callers check); the kernels then index their draws by off / G + s / G
 static int boot_partial_impl(twosd_ctx *c, int epi, const BootLayout &L, const int *handles, int M, unsigned long long seed,
@@ -564,16 +418,13 @@ static int boot_partial_impl(twosd_ctx *c, int epi, const BootLayout &L, const i
     HIPCHK(hipMemsetAsync(d_u64, 0, sizeof(unsigned long long) * L.n_u64, c->stream));
     const int nq = (M + 3) / 4;
     if (G > 1) off /= (unsigned long long)G;   // the one 64-bit division of a grouped call
-    auto weights = [&](int n, unsigned long long *out) {
-        if (n <= 0) return;
+    // scen: a tail handle's list (the LIST kernels walk its n entries), nullptr for the scenarios 0 .. n - 1
+    auto weights = [&](int n, const int *scen, unsigned long long *out) {
         const dim3 grid(std::max(1, std::min((n + 8191) / 8192, 32)), nq + 1);
-        if (G == 1)
-            hipLaunchKernelGGL(boot_weight_kernel<false>, grid, dim3(256), 0, c->stream, n, E.d_w.p, scale, M, seed, off, out, 1u);
-        else
-            hipLaunchKernelGGL(boot_weight_kernel<true>, grid, dim3(256), 0, c->stream, n, E.d_w.p, scale, M, seed, off, out,
-                               (unsigned)G);
+        hipLaunchKernelGGL(boot_weight_fn(G, scen != nullptr), grid, dim3(256), 0, c->stream, n, E.d_w.p, scale, M, seed, off, out,
+                           (unsigned)G, scen);
     };
-    weights(E.count, d_u64);
+    if (E.count > 0) weights(E.count, nullptr, d_u64);
     const int ngroups = std::max(1, (M + kBootGroup - 1) / kBootGroup);
     size_t slots_need = 1;
     for (int j = 0; j < L.H; ++j) {
@@ -585,75 +436,29 @@ static int boot_partial_impl(twosd_ctx *c, int epi, const BootLayout &L, const i
     }
     if ((rc = c->reform.slots.fit(slots_need))) return rc;   // once, before the first launch that writes it
     for (int j = 0; j < L.H; ++j) {
+        // the handle's words of the layout: W_j, the histogram rows and S, over its scenarios or over
+        // its tail's compact list (nothing outside the tail is read)
         const PickSet &h = c->reform.picks[handles[j]];
-        if (h.is_tail()) {
-            // the handle's words of the layout from its compact list: the weight, histogram and S
-            // kernels' siblings over nt entries (nothing outside the tail is read)
-            const int nt = h.nt;
-            double *Sj = d_f64 + (size_t)j * B * k;
-            if (nt == 0) {   // no launch over an empty list: W and the histogram rows stay 0, S is set to 0 -- the zero cut
-                if (k > 0) HIPCHK(hipMemsetAsync(Sj, 0, sizeof(double) * (size_t)B * k, c->stream));
-                continue;
-            }
-            const dim3 wgrid(std::max(1, std::min((nt + 8191) / 8192, 32)), nq + 1);
-            const dim3 hgrid(std::max(1, std::min((nt + 8191) / 8192, 64)), nq + 1, (h.nv + kBootVW - 1) / kBootVW);
-            unsigned long long *Wj = d_u64 + L.o_wj + (size_t)j * B, *Hj = d_u64 + L.o_hist + (size_t)j * B * L.nvs;
-            if (G == 1) {
-                hipLaunchKernelGGL(boot_tweight_kernel<false>, wgrid, dim3(256), 0, c->stream, nt, h.scen.p, E.d_w.p, scale, M, seed, off,
-                                   Wj, 1u);
-                hipLaunchKernelGGL(boot_thist_kernel<false>, hgrid, dim3(1024), 0, c->stream, nt, h.nv, L.nvs, M, h.scen.p, h.d.p,
-                                   E.d_w.p, scale, seed, off, Hj, 1u);
-            } else {
-                hipLaunchKernelGGL(boot_tweight_kernel<true>, wgrid, dim3(256), 0, c->stream, nt, h.scen.p, E.d_w.p, scale, M, seed, off,
-                                   Wj, (unsigned)G);
-                hipLaunchKernelGGL(boot_thist_kernel<true>, hgrid, dim3(1024), 0, c->stream, nt, h.nv, L.nvs, M, h.scen.p, h.d.p,
-                                   E.d_w.p, scale, seed, off, Hj, (unsigned)G);
-            }
-            if (k == 0) continue;
-            const ReformShards sh = reform_shards(nt);
-            BootParams P{};
-            P.n = nt; P.k = k; P.k4 = k4; P.nv = h.nv; P.M = M; P.ngroups = ngroups; P.tpb = sh.tpb; P.G = G;
-            P.scale = scale; P.seed = seed; P.off = off;
-            P.dv = E.d_dv; P.w = E.d_w; P.PK = PK; P.picks = h.d; P.scen = h.scen;
-            P.slots = c->reform.slots;
-            const dim3 rgrid(sh.nchunks * ngroups);
-            if (G == 1) {
-                if (k <= 64) hipLaunchKernelGGL((boot_treform_kernel<1, false>), rgrid, dim3(256), 0, c->stream, P);
-                else hipLaunchKernelGGL((boot_treform_kernel<2, false>), rgrid, dim3(256), 0, c->stream, P);
-            } else {
-                if (k <= 64) hipLaunchKernelGGL((boot_treform_kernel<1, true>), rgrid, dim3(256), 0, c->stream, P);
-                else hipLaunchKernelGGL((boot_treform_kernel<2, true>), rgrid, dim3(256), 0, c->stream, P);
-            }
-            reform_sum_shards(c, true, sh.nchunks, B * k, c->reform.slots.p, Sj);
+        const int entries = h.entries();
+        const int *scen = h.is_tail() ? h.scen.p : nullptr;
+        double *Sj = d_f64 + (size_t)j * B * k;
+        if (entries == 0) {   // no launch over an empty list: W and the histogram rows stay 0, S is set to 0 -- the zero cut
+            if (k > 0) HIPCHK(hipMemsetAsync(Sj, 0, sizeof(double) * (size_t)B * k, c->stream));
             continue;
         }
-        weights(h.n, d_u64 + L.o_wj + (size_t)j * B);
-        const dim3 hgrid(std::max(1, std::min((h.n + 8191) / 8192, 64)), nq + 1, (h.nv + kBootVW - 1) / kBootVW);
-        if (G == 1)
-            hipLaunchKernelGGL(boot_hist_kernel<false>, hgrid, dim3(1024), 0, c->stream, h.n, h.nv, L.nvs, M, h.d.p, E.d_w.p, scale, seed,
-                               off, d_u64 + L.o_hist + (size_t)j * B * L.nvs, 1u);
-        else
-            hipLaunchKernelGGL(boot_hist_kernel<true>, hgrid, dim3(1024), 0, c->stream, h.n, h.nv, L.nvs, M, h.d.p, E.d_w.p, scale, seed,
-                               off, d_u64 + L.o_hist + (size_t)j * B * L.nvs, (unsigned)G);
+        weights(entries, scen, d_u64 + L.o_wj + (size_t)j * B);
+        const dim3 hgrid(std::max(1, std::min((entries + 8191) / 8192, 64)), nq + 1, (h.nv + kBootVW - 1) / kBootVW);
+        hipLaunchKernelGGL(boot_hist_fn(G, scen != nullptr), hgrid, dim3(1024), 0, c->stream, entries, h.nv, L.nvs, M, h.d.p, E.d_w.p,
+                           scale, seed, off, d_u64 + L.o_hist + (size_t)j * B * L.nvs, (unsigned)G, scen);
         if (k == 0) continue;
-        const ReformShards sh = reform_shards(h.n);
+        const ReformShards sh = reform_shards(entries);
         BootParams P{};
-        P.n = h.n; P.k = k; P.k4 = k4; P.nv = h.nv; P.M = M; P.ngroups = ngroups; P.tpb = sh.tpb; P.G = G;
+        P.n = entries; P.k = k; P.k4 = k4; P.nv = h.nv; P.M = M; P.ngroups = ngroups; P.tpb = sh.tpb; P.G = G;
         P.scale = scale; P.seed = seed; P.off = off;
-        P.dv = E.d_dv; P.w = E.d_w; P.PK = PK; P.picks = h.d;
+        P.dv = E.d_dv; P.w = E.d_w; P.PK = PK; P.picks = h.d; P.scen = scen;
         P.slots = c->reform.slots;
-        const dim3 rgrid(sh.nchunks * ngroups);
-        if (G == 1) {
-            if (k <= 64) hipLaunchKernelGGL((boot_reform_kernel<1, 0>), rgrid, dim3(256), 0, c->stream, P);
-            else hipLaunchKernelGGL((boot_reform_kernel<2, 0>), rgrid, dim3(256), 0, c->stream, P);
-        } else if (G % 64 == 0) {   // a tile lies inside one group
-            if (k <= 64) hipLaunchKernelGGL((boot_reform_kernel<1, 2>), rgrid, dim3(256), 0, c->stream, P);
-            else hipLaunchKernelGGL((boot_reform_kernel<2, 2>), rgrid, dim3(256), 0, c->stream, P);
-        } else {
-            if (k <= 64) hipLaunchKernelGGL((boot_reform_kernel<1, 1>), rgrid, dim3(256), 0, c->stream, P);
-            else hipLaunchKernelGGL((boot_reform_kernel<2, 1>), rgrid, dim3(256), 0, c->stream, P);
-        }
-        reform_sum_shards(c, true, sh.nchunks, B * k, c->reform.slots.p, d_f64 + (size_t)j * B * k);
+        hipLaunchKernelGGL(boot_reform_fn(k, G, scen != nullptr), dim3(sh.nchunks * ngroups), dim3(256), 0, c->stream, P);
+        reform_sum_shards(c, true, sh.nchunks, B * k, c->reform.slots.p, Sj);
     }
     HIPCHK(hipGetLastError());
     return TWOSD_OK;

@@ -4,13 +4,17 @@
 // with per-vertex integer weights, shard partials of S and a total weight W per row; S, g and the
 // normalised cut are formed here, in reform_layout.h's layouts.  No floating-point atomics.
 //
-// Not here, on purpose: the streaming kernels boot_reform_kernel<KE, GM>, its sibling over a tail
-// handle's list boot_treform_kernel<KE, GR> and risk_treform_kernel<KE>, and the histogram kernels
-// boot_hist_kernel, boot_thist_kernel and risk_thist_kernel.  Their bodies look alike and are
-// not to be merged or templated over a count source: the tail kernel never loads the row of a
-// scenario outside the tail, the bootstrap kernel holds 17 accumulators per element at 191 VGPRs,
-// and how the compiler contracts wq * PK * dv + acc in a merged body -- every bit of both results
-// depends on it -- cannot be known without running it.
+// Not here, on purpose: the streaming kernels boot_reform_kernel<KE, GM, LIST> and
+// risk_treform_kernel<KE>, and the histogram kernels boot_hist_kernel<GR, LIST> and
+// risk_thist_kernel.  The bootstrap's walk over a tail handle's list is an instantiation (LIST) of
+// its kernels over all scenarios: one body each.  Every bit of S depends on how the compiler
+// contracts wq * PK * dv + acc and the bootstrap kernel sits at 191 VGPRs, so the rule for any
+// change to these bodies is: each instantiation's instruction stream and kernel descriptor equal
+// the parent commit's, compared on the CPU (tools/isa_same.py; profiles/reform_merge) -- equal
+// streams give equal bits and equal speed, and a difference is not to be argued away.  risk.hip's
+// two kernels remain separate kernels: they form one row, skip the scenarios outside the tail (a
+// skipped scenario's row is never loaded) and flag a scenario by its score, not by a list, so no
+// instantiation of the bootstrap's bodies has their instruction stream.
 #include <hip/hip_runtime.h>
 #include <algorithm>
 #include <vector>

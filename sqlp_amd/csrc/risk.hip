@@ -30,7 +30,8 @@
 //                        never loaded); the shard layout is reform_layout.h's (a function of N alone)
 // then reform.hip's stage, one handle and one row: S_e = the shards' partials in shard order (not the
 // bootstrap's eight segments), g, and alpha, beta normalised by W_t (W_t = 0: the zero cut).  The two
-// kernels above stay the tail's own: no merging with boot_kernel.hip's look-alikes (reform.hip's header).
+// kernels above stay the tail's own (one row, flags from scores, skipped rows), not instantiations of
+// boot_kernel.hip's templates: reform.hip's header has the reason and the rule for changing either.
 //
 // Tail handles (twosd_tail_keep).  The set the tail cut sums over -- the scenarios with
 // tail_flag, bit for bit -- as a compact list in the pick handles' table (ReformState::picks), so

@@ -1,6 +1,6 @@
 """Tail handles (sqlp_amd/csrc/risk.hip: twosd_tail_keep / _info / _get) and their re-formation
-under bootstrap weights (boot_kernel.hip: boot_tweight_kernel, boot_thist_kernel,
-boot_treform_kernel) against tests/boot_ref.py: the reference of a tail handle's row b is
+under bootstrap weights (boot_kernel.hip: the LIST instantiations of boot_weight_kernel,
+boot_hist_kernel and boot_reform_kernel) against tests/boot_ref.py: the reference of a tail handle's row b is
 boot_ref.reform(..., c = counts[:, b] * (max_val > eta)), the tail set taken on the host from the
 max_val the cut call returned.
 

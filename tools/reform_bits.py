@@ -13,7 +13,11 @@ groups of 64 (a tile inside one group) -- the three instantiations of the stream
 count must be whole groups, so under G = 64 lands holds 2496 scenarios with cuts kept at 832, 1600
 and 2496 (39 tiles, 10 shards) and the template 256.  The tail cut is taken of the last cut of the
 i.i.d. epigraphs (2500 and 300 scenarios) at eta below every score, at the 0.7 point of the scores
-and above every score.
+and above every score.  Every epigraph (each G) is then re-formed once more with pick handles and
+tail handles mixed -- [first cut, tail, last cut, tail, tail, tail], the tails cut_tail(keep=True) of
+the last cut at the scores' midrange, above every score (the empty list), at their 0.7 point and
+below every score (the full list: on lands more shards than summing segments); the four lengths
+stand in the case's name -- through the boot kernels' list instantiations.
 
 --tree PATH imports sqlp_amd and tests from another checkout (its library built in-tree).
 Prints one JSON line.  --out also writes it to a file."""
@@ -87,18 +91,29 @@ def main():
                     t = twosd.cut_tail(epi, eta)
                     out[f"{name} N={stages[-1]} cut_tail {what}"] = digest([t.alpha], t.beta, [t.tail_weight], [t.total_weight])
             total = epi.total_scenario_weight
-            for M in (1, 33):
-                key = f"{name} N={stages[-1]} G={G} M={M}"
-                R = twosd.reform_cuts(epi, handles, M, SEED, sampling=plan(G))
+
+            def both(key, hs, M):
+                R = twosd.reform_cuts(epi, hs, M, SEED, sampling=plan(G))
                 out[key + " reform_cuts"] = digest(R.alpha, R.beta, R.weight_mark, R.total_weight)
-                nu, nf = twosd.reform_partial_len(ctx, handles, M)
+                nu, nf = twosd.reform_partial_len(ctx, hs, M)
                 u = torch.zeros(nu, dtype=torch.int64, device="cuda")
                 f = torch.zeros(nf, dtype=torch.float64, device="cuda")
                 torch.cuda.synchronize()
-                twosd.reform_partial(epi, handles, M, SEED, 0, total, u.data_ptr(), f.data_ptr(), sampling=plan(G))
-                R = twosd.reform_finalize(ctx, handles, M, total, u.data_ptr(), f.data_ptr())
+                twosd.reform_partial(epi, hs, M, SEED, 0, total, u.data_ptr(), f.data_ptr(), sampling=plan(G))
+                R = twosd.reform_finalize(ctx, hs, M, total, u.data_ptr(), f.data_ptr())
                 out[key + " partial+finalize"] = digest(R.alpha, R.beta, R.weight_mark, R.total_weight)
-            for h in handles:
+
+            for M in (1, 33):
+                both(f"{name} N={stages[-1]} G={G} M={M}", handles, M)
+            # tail handles of the last cut: the full tail, the scores' midrange, their 0.7 point, the empty tail
+            srt = np.sort(mv)
+            etas = (float(srt[0]) - 1.0, 0.5 * float(srt[0] + srt[-1]), float(srt[(7 * len(srt)) // 10]), float(srt[-1]) + 1.0)
+            tails = [twosd.cut_tail(epi, eta, keep=True).picks for eta in etas]
+            nts = "/".join(str(twosd.tail_info(ctx, t).nt) for t in tails)
+            mixed = [handles[0], tails[1], handles[-1], tails[3], tails[2], tails[0]]
+            for M in (1, 33):
+                both(f"{name} N={stages[-1]} G={G} M={M} mixed, tails nt={nts}", mixed, M)
+            for h in handles + tails:
                 twosd.picks_release(ctx, h)
         ctx.close()
     line = json.dumps({"tree": os.path.relpath(tree, ROOT), "digests": out}, sort_keys=True)
